@@ -10,6 +10,13 @@ config 4 whole on the GPU (cfg4: the strong-scaling base) beside it.  N GPUs
 split over the ranks (strong scaling), one RCCL all-reduce of the count aggregates
 per sweep.
 
+A plain run sets up, warms up, times the --steps sweeps and prints the result line.
+--full adds everything else: the per-dispatch event sample (dispatch_event_ms and,
+with a communicator, allreduce_ms), the committed PMC records, the side records of
+the other configs and the CPU baselines.
+--dump-outputs DIR writes the state the timed chain ended in (what a caller of the
+resident sweeps receives from get_state) as DIR/positions.npy and DIR/pwms.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -150,7 +157,8 @@ def run_workload(ctx, w, lo, hi, steps, warmup, dist_ctx=None, dispatch_sample=1
     stream around the timed region; dispatch, a dict of per-dispatch event averages
     from `dispatch_sample` extra sweeps after the timed region (each event-attached
     dispatch completes with a release and widens the gap behind it by ~5 us, so the
-    timed region carries no per-launch events))."""
+    timed region carries no per-launch events; 0: none); dispatch["outputs"] is the
+    state after the last timed sweep (positions, PWMS), as get_state returns it)."""
     import torch
 
     from gibbssampling_amd import synthetic
@@ -209,7 +217,7 @@ def run_workload(ctx, w, lo, hi, steps, warmup, dist_ctx=None, dispatch_sample=1
     ctx.synchronize()  # the sticky device error check (after the clock: not sweep work)
     if dist_ctx is not None:
         elapsed = dist_ctx.max(elapsed)
-    pos1, _ = ctx.get_state()
+    pos1, pwms1 = ctx.get_state()
     s1 = ctx.stats()
     n_loc = max(1, len(pos0))
     kept = [int((pos0 >= 0).sum()), int((pos1 >= 0).sum()), s1["bg_picks"] - s0["bg_picks"],
@@ -235,6 +243,7 @@ def run_workload(ctx, w, lo, hi, steps, warmup, dist_ctx=None, dispatch_sample=1
         if nar:
             dispatch["allreduce_ms"] = arms / nar
     dispatch["chain"] = chain
+    dispatch["outputs"] = {"positions": pos1, "pwms": pwms1}
     if exchange is not None:
         dispatch["exchange"] = exchange
     return elapsed, region_ms / steps, dispatch
@@ -323,14 +332,23 @@ def main() -> int:
                          "doMotifSampling sweeps (.fs:1035-1037)")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
                     help="seconds of reference-faithful CPU work for cpu_baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--exchange", choices=["auto", "rccl", "ipc"], default="auto",
                     help="the aggregate vector's per-sweep exchange between ranks: an RCCL "
                          "all-reduce after each sweep, or summed inside the live/long sweep's "
                          "last workgroup over HIP IPC (gs_exchange_open; checked on the warmup "
                          "chain, RCCL if that fails); auto = ipc with several ranks, else rccl")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the config-3 roofline and config-4 records on one GPU")
+                    help="with --full: skip the config-3 roofline and config-4 records on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-dispatch event sample (dispatch_event_ms, "
+                         "and allreduce_ms under torch.distributed.run), the committed PMC "
+                         "records, the side records (configs 3, 4, 5, config 2 from uniform "
+                         "starts) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed sweep (rank 0's shard) as "
+                         "DIR/positions.npy and DIR/pwms.npy (float64)")
     args = ap.parse_args()
 
     # The one JSON line is the only thing on stdout: libraries (RCCL's version banner,
@@ -381,8 +399,15 @@ def main() -> int:
             xch_err = open_exchange(ctx, rank, world, dist_ctx.gloo)
 
     elapsed, kernel_ms, dispatch = run_workload(ctx, w, lo, hi, args.steps, args.warmup,
-                                                dist_ctx, regime=args.regime)
+                                                dist_ctx, regime=args.regime,
+                                                dispatch_sample=16 if args.full else 0)
     chain = dispatch.pop("chain")
+    outputs = dispatch.pop("outputs")
+    if args.dump_outputs and rank == 0:
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(dump / f"{name}.npy", np.asarray(a, np.float64))
     start_pos = chain.pop("start_pos")
     ms_per_step = elapsed * 1e3 / args.steps
     iters = args.steps / elapsed
@@ -397,7 +422,7 @@ def main() -> int:
     bytes_launch = (hi - lo) * (w.L + 24)  # scan kernel N*(L+24) per launch
     achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
     traffic, traffic_src, valu = None, None, None
-    if world == 1:
+    if world == 1 and args.full:
         rec = pmc_record(cfg, args.regime)
         if rec and not rec.get("stale") and rec.get("kernel") == kernel_name:
             traffic, traffic_src, valu = rec.get("traffic_bytes_per_launch"), rec["source"], rec.get("valu")
@@ -450,7 +475,7 @@ def main() -> int:
     ctx.close()
     del codes, offsets
 
-    if rank == 0 and world == 1 and not args.no_side and cfg == "cfg2":
+    if args.full and rank == 0 and world == 1 and not args.no_side and cfg == "cfg2":
         # the HBM-bound long-sequence scan (config 3), the strong-scaling base (config
         # 4, whole on one GPU), protein (config 5), each from getPWMOfRandomStarts'
         # output and from uniform starts; config 2 from uniform starts (collapsed)
@@ -460,7 +485,7 @@ def main() -> int:
         out["cfg2_uniform"] = side_record(device, "cfg2", args.steps, args.warmup,
                                           regimes=("uniform",))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         codes, offsets = synthetic.generate(w, lo, hi)
         # like for like: the CPU sweeps the snapshot the timed GPU chain started from
         pos = start_pos if start_pos is not None else synthetic.initial_positions(w, lo, hi)
