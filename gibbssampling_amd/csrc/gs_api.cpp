@@ -541,9 +541,11 @@ int gs_run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_
                 HIP_TRY(c, hipGraphLaunch(g, c->stream));
         }
     }
+    // PWMS after a chain are those of its last sweep: every sweep overwrites them and
+    // nothing reads them in between, so only the last direct launch computes them
     for (; t < n_sweeps; ++t)
         if ((rc = one_sweep(c, pc, cutoff, nullptr, seed,
-                            stream_sweep((uint64_t)(first_sweep + t)))))
+                            stream_sweep((uint64_t)(first_sweep + t)), t == n_sweeps - 1)))
             return rc;
     // the rest of the chain by the all-background kernel once a sweep saw the state
     return n_sweeps > 0 ? bg_check_note(c, pc, cutoff) : GS_OK;

@@ -332,7 +332,7 @@ int validate_pos(gs_ctx *c, int32_t W, const int32_t *pos);
 hipEvent_t get_event(gs_ctx *c);
 int allreduce_agg(gs_ctx *c, int idx);
 int launch_sweep(gs_ctx *c, int mode, double pc, double cutoff, const double *u_dev, uint64_t seed,
-                 uint64_t stream, int agg_in, int agg_out, int agg_zero);
+                 uint64_t stream, int agg_in, int agg_out, int agg_zero, bool want_pwms = true);
 bool use_dna(const gs_ctx *c);
 bool bg_wanted(const gs_ctx *c);
 bool bg_ready(gs_ctx *c, double pc, double cutoff);
@@ -353,7 +353,7 @@ int allreduce_vec(gs_ctx *c, int idx);
 int launch_dna(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed);
 int set_snapshot(gs_ctx *c, int32_t W, const int32_t *pos);
 int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed,
-              uint64_t stream);
+              uint64_t stream, bool want_pwms = true);
 bool graphs_wanted(gs_ctx *c);
 int graph_buffers(gs_ctx *c);
 hipGraphExec_t sweep_graph(gs_ctx *c, double pc, double cutoff, uint64_t seed);

@@ -236,8 +236,10 @@ int allreduce_agg(gs_ctx *c, int idx) {
     return GS_OK;
 }
 
+// want_pwms = false: the sweep's PWMS would be overwritten unread (a chain's sweeps
+// before its last, gs_api.cpp gs_run_sweeps): the kernel skips their folds and stores.
 int launch_sweep(gs_ctx *c, int mode, double pc, double cutoff, const double *u_dev, uint64_t seed,
-                 uint64_t stream, int agg_in, int agg_out, int agg_zero) {
+                 uint64_t stream, int agg_in, int agg_out, int agg_zero, bool want_pwms) {
     SweepArgs a{};
     int gl = gs_sweep_group_lanes(c->E, c->Lmax);
     if (c->tune.group_lanes > 0 && c->E + 1 <= c->tune.group_lanes &&
@@ -290,7 +292,7 @@ int launch_sweep(gs_ctx *c, int mode, double pc, double cutoff, const double *u_
     a.den = (double)(c->n_global - 1) + a.apc;
     a.pos_in = c->d_pos[c->cur_pos];
     a.pos_out = c->d_pos[1 - c->cur_pos];
-    a.pwms_out = c->d_pwms;
+    a.pwms_out = want_pwms ? c->d_pwms : nullptr;
     a.u_in = u_dev;
     a.seed = seed;
     a.stream = stream;
@@ -869,8 +871,9 @@ int set_snapshot(gs_ctx *c, int32_t W, const int32_t *pos) {
     return GS_OK;
 }
 
+// want_pwms = false reaches gs_sweep_kernel only: the other kernels always store PWMS
 int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed,
-              uint64_t stream) {
+              uint64_t stream, bool want_pwms) {
     int rc;
     if ((rc = bg_resolve(c))) return rc;
     if (bg_ready(c, pc, cutoff)) {
@@ -916,7 +919,7 @@ int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t
     c->vec_valid = false;
     const int i = c->cur_agg, o = (i + 1) % 3, z = (i + 2) % 3;
     if (c->n_local > 0) {
-        if ((rc = launch_sweep(c, 0, pc, cutoff, u_dev, seed, stream, i, o, z))) return rc;
+        if ((rc = launch_sweep(c, 0, pc, cutoff, u_dev, seed, stream, i, o, z, want_pwms))) return rc;
     } else {
         HIP_TRY(c, hipMemsetAsync(c->d_agg[o], 0, (size_t)kRepl * c->stride * 8, c->stream));
     }

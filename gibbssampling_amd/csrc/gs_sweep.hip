@@ -1509,8 +1509,14 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             TLINE(tl_w, 4);
             // ---- the picked window's exact weight ----
             // factors of column j (group lane j, padding columns hold 1.0), then the
-            // reference's left folds, uniform over the group
-            if (kind >= 0) {
+            // reference's left folds, uniform over the group.  Only pwms_out needs them:
+            // a sweep launched without it (null: a chain's sweeps before its last, whose
+            // PWMS the next sweep would overwrite unread; gs_api.cpp gs_run_sweeps) skips
+            // the factors, the folds and the batch end's log.  The kind = -6 recheck
+            // below lives in the fold and goes with it on those sweeps: it cannot fire
+            // while the certified bound holds (gs_stats [3] stays 0).
+            const bool pwms_on = KA(pwms_out) != nullptr;
+            if (pwms_on && kind >= 0) {
                 for (int j = li; j < W; j += GL) {
                     const int e = sym(sseq[pk + j]);
                     const double pe_e = pcv[e];
@@ -1522,7 +1528,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             wave_sync();
             double pw = 0.0;
             bool pw_log = false;
-            {
+            if (pwms_on) {
                 double S = 1.0, Gp = 1.0;
 #pragma unroll
                 for (int j = 0; j < WM; ++j) {
@@ -1699,7 +1705,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             if (keep && li == 0) {
                 if constexpr (kDyn) {  // stored now (.fs:737's log2 for a motif pick)
                     KA(pos_out)[n] = newp;
-                    KA(pwms_out)[n] = pw_log ? log_ool(pw * 1.0) / kLn2 : pw;  // (H = 1: the log out of line)
+                    if (pwms_on)
+                        KA(pwms_out)[n] = pw_log ? log_ool(pw * 1.0) / kLn2 : pw;  // (H = 1: the log out of line)
                 } else {
                     res[bsl] = SweepResult{newp, pw_log ? 1 : 0, pw};
                 }
@@ -1726,11 +1733,12 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             const int i = ((it * G) & ~63) + lane;
             if (mode == 0 && i < cnt) {
                 const SweepResult r = res[lane];
-                const double v = r.log ? log(r.pw * 1.0) / kLn2 : r.pw;  // .fs:737
+                double *const pwo = KA(pwms_out);  // (null: this sweep's PWMS are not wanted)
+                const double v = r.log ? log(r.pw * 1.0) / kLn2 : r.pw;  // .fs:737 (log: never without PWMS)
                 const int nb = n0 + i * wstride;
 #ifndef GS_DIAG_NOOUT  // (traffic attribution builds only: the results are not stored)
                 KA(pos_out)[nb] = r.pos;
-                KA(pwms_out)[nb] = v;
+                if (pwo) pwo[nb] = v;
 #else
                 asm volatile("" ::"v"(r.pos), "v"(v));
 #endif

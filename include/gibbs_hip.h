@@ -103,7 +103,10 @@ int gs_motif_sweep(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
 /* Device-resident chain of sweeps (the Gibbs iteration).  gs_state_set_positions
  * uploads a snapshot; gs_run_sweeps enqueues n_sweeps sweeps asynchronously, the
  * uniform of sequence n in sweep t being gs_uniform(seed, stream_sweep(t), n);
- * gs_state_get synchronises and downloads the latest snapshot. */
+ * gs_state_get synchronises and downloads the latest snapshot.  PWMS after a chain
+ * are those of its last sweep: every sweep overwrites them and nothing can read them
+ * in between, so the sweeps of one gs_run_sweeps call before its last compute
+ * positions and aggregates only (a call with n_sweeps = 0 leaves the PWMS as they are). */
 int gs_state_set_positions(gs_ctx *ctx, int32_t W, const int32_t *pos);
 int gs_run_sweeps(gs_ctx *ctx, double pseudo_count, double cut_off, int32_t n_sweeps,
                   uint64_t seed, int64_t first_sweep);
