@@ -144,6 +144,9 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_run_greedy": (C.c_int, [vp, f64, f64, i32, P(i32), P(f64)]),
         "gs_motif_greedy": (C.c_int, [vp, i32, f64, f64, i32, vp, vp, P(i32)]),
         "gs_motif_sampling": (C.c_int, [vp, i32, f64, f64, u64, i32, i32, vp, vp, P(i32)]),
+        "gs_motif_sampling_batch": (C.c_int, [vp, i32, f64, f64, vp, i32, i32, i32, vp, vp, vp,
+                                              vp]),
+        "gs_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_motif_sweep_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp]),
         "gs_motif_greedy_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, i32, vp, vp, vp,
                                             P(i32)]),
@@ -341,6 +344,32 @@ class Context:
                                                int(max_passes), _ptr(pos), _ptr(pwms),
                                                C.byref(passes)))
         return pos, pwms, passes.value
+
+    def motif_sampling_batch(self, W: int, pc: float, cutoff: float, seeds, init_mode: int = 0,
+                             max_passes: int = 1000):
+        """R independent doMotifSampling runs in one call, row r exactly
+        motif_sampling(W, pc, cutoff, seeds[r], ...): the chains' greedy passes run
+        as R concurrent workgroups -> (pos[R, N], pwms[R, N], passes[R], status[R]).
+        A chain that raises (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows
+        valid; errors of the call itself raise."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        pos = np.empty((R, self.n_local), np.int32)
+        pwms = np.empty((R, self.n_local), np.float64)
+        passes = np.zeros(R, np.int32)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_motif_sampling_batch(self.h, int(W), float(pc), float(cutoff), _ptr(seeds),
+                                              R, int(init_mode), int(max_passes), _ptr(pos),
+                                              _ptr(pwms), _ptr(passes), _ptr(status))
+        if st != GS_OK and not status.any():
+            self._check(st)
+        return pos, pwms, passes, status
+
+    def batch_last_ms(self):
+        """Device milliseconds of the last motif_sampling_batch: (first stages, greedy launch)."""
+        out = np.zeros(2, np.float64)
+        self._check(self.lib.gs_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
 
     # -- motifAmount >= 1 with Positions lists
     def _lists(self, cnt, pos, cap):

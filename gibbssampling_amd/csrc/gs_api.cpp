@@ -77,6 +77,322 @@ static void takeover_reset(gs_ctx *c) {
     c->note_pending = false;
 }
 
+// ---- gs_motif_sampling_batch: R chains, one greedy launch ----
+
+// getPWMOfRandomStarts on the stream: the draws' partial counts (mode 0, into the caller's
+// d_cpart of n_global * A * W int32), then the Jacobi pass over the snapshot just set
+// (d_agg[cur_agg]) -> d_pwms, d_pos[1].  No synchronisation.
+static int starts_enqueue(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, int32_t *d_cpart) {
+    const int A = c->A, AW = A * W;
+    if (mode == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_cpart, 0, (size_t)c->n_global * AW * 4, c->stream));
+        PartialArgs p{};
+        p.seq = c->d_seq;
+        p.doff = c->d_doff;
+        p.len = c->d_len;
+        p.n_local = c->n_local;
+        p.global_offset = c->global_offset;
+        p.n_global = c->n_global;
+        p.A = A;
+        p.W = W;
+        p.seed = seed;
+        p.cpart = d_cpart;
+        if (c->n_local > 0) {
+            int grid = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_global, c->n_cu * 8));
+            HIP_TRY(c, gs_starts_partial_launch(p, grid, c->stream));
+        }
+        if (c->comm)
+            RCCL_TRY(c, ncclAllReduce(d_cpart, d_cpart, (size_t)c->n_global * AW, ncclInt32,
+                                      ncclSum, c->comm, c->stream));
+    }
+    return starts_pass(c, mode, W, pc, seed, nullptr, d_cpart, c->d_agg[c->cur_agg], c->d_pwms,
+                       c->d_pos[1], c->use_ppm ? c->d_ppm_fixed : nullptr);
+}
+
+static const char *device_error_message(int code) {  // (as check_device_error)
+    return code == 2   ? "roulette wheel ran past the last category (.fs:752)"
+           : code == 3 ? "background count sum overflows int32 (.fs:117)"
+                       : "device error";
+}
+
+// The state buffers for W, kept when they are already there: alloc_state keys on
+// have_state, which is false between a batch's chains and after gs_random_starts, and
+// would free and reallocate buffers that enqueued work still names.
+static int ensure_state(gs_ctx *c, int32_t W) {
+    if (c->d_pos[0] && c->W == W) return GS_OK;
+    return alloc_state(c, W);
+}
+
+// The device-resident route to a snapshot (set_snapshot without its host side, single
+// device, no communicator): positions already on the device (d_src, valid by
+// construction: nothing is checked on the host, and they are never all []) go to
+// d_pos[0] on the stream, their aggregates to d_agg[0].  reset_err = false keeps a sticky
+// device error of the kernels that produced them.
+static int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool reset_err) {
+    int rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((rc = ensure_state(c, W))) return rc;
+    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+    c->note_pending = false;
+    if (!c->d_bg_note) HIP_TRY(c, hipMalloc(&c->d_bg_note, 4));
+    HIP_TRY(c, hipMemsetAsync(c->d_bg_note, 0, 4, c->stream));
+    if (d_src != c->d_pos[0] && c->n_local > 0)
+        HIP_TRY(c, hipMemcpyAsync(c->d_pos[0], d_src, (size_t)c->n_local * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+    c->cur_pos = 0;
+    for (auto &b : c->d_agg)
+        HIP_TRY(c, hipMemsetAsync(b, 0, (size_t)kRepl * c->stride * 8, c->stream));
+    if (reset_err) {
+        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+    }
+    if (c->n_local > 0)
+        if ((rc = launch_sweep(c, 1, 0.0, 0.0, nullptr, 0, 0, -1, 0, -1))) return rc;
+    c->cur_agg = 0;
+    c->rep_valid = true;
+    c->vec_valid = false;
+    c->dna_agree = true;
+    c->bg_agree = true;
+    HIP_TRY(c, hipMemsetAsync(c->d_gen_done, 0, kDoneBytes, c->stream));
+    c->ftab_agg = -1;
+    if (c->dna_ok) {
+        c->cur_aggv = 0;
+        HIP_TRY(c, hipMemsetAsync(c->d_rep, 0, (size_t)kRepl * c->stride * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_dna_done, 0, kDoneBytes, c->stream));
+        if (use_dna(c) && (rc = need_vec(c))) return rc;
+    }
+    c->have_state = true;
+    return GS_OK;
+}
+
+// The motif sampler's greedy arguments that do not name a chain's buffers, with the LDS
+// carve of greedy_run (gs_engine.cpp, site = 0): the workgroup part, the visit ring of
+// 2 * waves slots, one (PWM, PCV) table slice per wavefront.
+static int greedy_carve(gs_ctx *c, double pc, double cutoff, int32_t max_passes, GreedyArgs &a,
+                        int &waves_out, int64_t &lds_out) {
+    const int A = c->A, E = c->E, W = c->W, WM = gs_sweep_wm(W);
+    int64_t o = 0;
+    auto take = [&](int64_t b) {
+        int64_t q = o;
+        o = align16(o + b);
+        return (int32_t)q;
+    };
+    a.o_C = take(4 * (int64_t)A * W);
+    a.o_T = take(8 * (int64_t)A);
+    a.o_ppmG = take(8 * (int64_t)A * W);
+    a.o_ppmM = take(8 * (int64_t)A * W);
+    a.o_ctl = take(4 * 64);
+    const int64_t fixed = o;
+    a.ring_seq_bytes = (int32_t)(align16(c->Lmax) + align16(WM) + 32);
+    a.w_tab = 0;
+    int64_t wb = align16(16 * (int64_t)E * tab_stride(WM));
+    a.w_pcv = (int32_t)wb;
+    wb += 8 * 64;
+    a.wave_bytes = (int32_t)wb;
+    const int64_t per_wave = wb + 2 * (a.ring_seq_bytes + 4 * 3 + 8 + 4 * 64) + 64 + 32;
+    int waves = c->tune.greedy_waves;
+    while (waves > 1 && fixed + per_wave * waves > c->max_lds) --waves;
+    if ((int64_t)waves > c->n_local) waves = (int)std::max<int64_t>(1, c->n_local);
+    while (waves & (waves - 1)) waves &= waves - 1;  // a power of two (ring indexing)
+    const int R = 2 * waves;
+    a.o_ring = take((int64_t)R * a.ring_seq_bytes);
+    a.o_rt = take(4 * (int64_t)R);
+    a.o_rL = take(4 * (int64_t)R);
+    a.o_rp = take(4 * (int64_t)R);
+    a.o_rpw = take(8 * (int64_t)R);
+    a.o_rcomp = take(4 * 64 * (int64_t)R);
+    a.o_red = take(8 * 4 * (int64_t)waves);
+    a.o_wave = take((int64_t)waves * a.wave_bytes);
+    a.motif_coop = c->tune.motif_coop;
+    if (o > c->max_lds)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "longest sequence exceeds the greedy kernel's LDS budget (" +
+                        std::to_string(o) + " > " + std::to_string(c->max_lds) + " B)");
+    a.seq = c->d_seq;
+    a.doff = c->d_doff;
+    a.len = c->d_len;
+    a.comp = c->d_comp;
+    a.n = c->n_local;
+    a.A = A;
+    a.W = W;
+    a.E = E;
+    a.cells = c->cells;
+    a.stride = c->stride;
+    a.pc = pc;
+    a.cutoff = cutoff;
+    a.thr_lo = cutoff_threshold(cutoff);
+    a.apc = (double)A * pc;
+    a.den = (double)(c->n_global - 1) + a.apc;
+    a.max_passes = max_passes;
+    waves_out = waves;
+    lds_out = o;
+    return GS_OK;
+}
+
+namespace {
+// Device slabs of one batch call, freed on scope exit.
+struct BatchBufs {
+    int32_t *pos = nullptr, *passes = nullptr, *err = nullptr, *starts = nullptr, *cpart = nullptr;
+    double *pwms = nullptr;
+    int64_t *agg = nullptr;
+    unsigned long long *erri = nullptr;
+    ~BatchBufs() {
+        dfree(pos);
+        dfree(passes);
+        dfree(err);
+        dfree(starts);
+        dfree(cpart);
+        dfree(pwms);
+        dfree(agg);
+        dfree(erri);
+    }
+};
+}  // namespace
+
+// R independent doMotifSampling runs (.fs:1034-1038, motifAmount = 1).  Stage 1, chain
+// after chain on the context's single-chain state and stream, no host wait in between:
+// starts (seed r) -> snapshot of them -> sweep 0 of seed r -> device copies of positions,
+// PWMS, replica aggregates and the error words into slab r.  Stage 2: one launch of
+// gs_greedy_batch_kernel, workgroup r on slab r, every pass in-kernel.  One
+// synchronisation, then the slabs come down.  The caller validated the arguments.
+static int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds, int32_t R,
+                int32_t mode, int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                int32_t *passes_out, int32_t *status_out) {
+    int rc;
+    const int64_t n = c->n_local;
+    if (n == 0) {
+        for (int32_t r = 0; r < R; ++r) {
+            if (passes_out) passes_out[r] = 0;
+            if (status_out) status_out[r] = GS_OK;
+        }
+        return GS_OK;
+    }
+    if ((rc = ensure_state(c, W))) return rc;
+    GreedyArgs a{};
+    int waves = 0;
+    int64_t lds = 0;
+    if ((rc = greedy_carve(c, pc, cutoff, max_passes, a, waves, lds))) return rc;
+    const int64_t agg_elems = (int64_t)kRepl * c->stride;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    const int64_t bytes = (int64_t)R * (n * (4 + 8 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 16) +
+                          cpart_bytes;
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_batch: the chains' slabs take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a batch may hold: split the seeds over several calls");
+    BatchBufs b;
+    HIP_TRY(c, hipMalloc(&b.pos, (size_t)(R * n) * 4));
+    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)(R * n) * 8));
+    HIP_TRY(c, hipMalloc(&b.agg, (size_t)(R * agg_elems) * 8));
+    HIP_TRY(c, hipMalloc(&b.passes, (size_t)R * 4));
+    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 4));
+    HIP_TRY(c, hipMalloc(&b.erri, (size_t)R * 8));
+    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
+    if (mode == 0) {
+        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
+    } else {
+        HIP_TRY(c, hipMalloc(&b.starts, (size_t)(R * n) * 4));
+        hs.resize((size_t)(R * n));
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = 0; i < n; ++i)
+                hs[(size_t)(r * n + i)] =
+                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
+                                c->h_len[i] - W + 1);
+        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
+                                  c->stream));
+    }
+    hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
+    auto recycle = [&]() {
+        c->ev_pool.push_back(e0);
+        c->ev_pool.push_back(e1);
+        c->ev_pool.push_back(e2);
+    };
+    rc = [&]() -> int {
+        int rc2;
+        HIP_TRY(c, hipEventRecord(e0, c->stream));
+        for (int32_t r = 0; r < R; ++r) {
+            // the start vector the aggregate pass reads: the shared draws (mode 1), or any
+            // valid one (mode 0 takes only the composition totals from it)
+            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
+                return rc2;
+            // a target that raises (.fs:117) writes no start: every entry stays a valid one
+            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
+            // its error word stays set: the sweep skips, the chain's slab carries it
+            if ((rc2 = set_snapshot_dev(c, W, c->d_pos[1], false))) return rc2;
+            if (use_dna(c)) {  // (as gs_run_sweeps: the device sweep counter at sweep 0)
+                if ((rc2 = need_vec(c))) return rc2;
+                HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, 0ull, c->d_done_ctr, c->stream));
+            }
+            if ((rc2 = one_sweep(c, pc, cutoff, nullptr, seeds[r], stream_sweep(0), true)))
+                return rc2;
+            if ((rc2 = need_rep(c))) return rc2;
+            HIP_TRY(c, hipMemcpyAsync(b.pos + r * n, c->d_pos[c->cur_pos], (size_t)n * 4,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.pwms + r * n, c->d_pwms, (size_t)n * 8,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.agg + r * agg_elems, c->d_agg[c->cur_agg],
+                                      (size_t)agg_elems * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.err + r, c->d_err_code, 4, hipMemcpyDeviceToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.erri + r, c->d_err_index, 8, hipMemcpyDeviceToDevice,
+                                      c->stream));
+        }
+        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
+        HIP_TRY(c, hipEventRecord(e1, c->stream));
+        a.agg = b.agg;
+        a.pos = b.pos;
+        a.pwms = b.pwms;
+        a.passes_out = b.passes;
+        a.err_code = b.err;
+        a.err_index = b.erri;
+        a.exit_chunk = 0;
+        a.exit_out = nullptr;
+        HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
+        HIP_TRY(c, hipEventRecord(e2, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    // the context's single-chain buffers were the chains' scratch: no snapshot is left
+    c->have_state = false;
+    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+    c->note_pending = false;
+    c->ftab_agg = -1;
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
+        recycle();
+        return rc;
+    }
+    c->last_greedy_waves = waves;
+    float ms1 = 0.0f, ms2 = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms1, e0, e1));
+    HIP_TRY(c, hipEventElapsedTime(&ms2, e1, e2));
+    recycle();
+    c->batch_ms[0] = (double)ms1;
+    c->batch_ms[1] = (double)ms2;
+    std::vector<int32_t> herr((size_t)R), hpass((size_t)R);
+    std::vector<unsigned long long> hidx((size_t)R);
+    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pwms_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
+    int first = -1;
+    for (int32_t r = 0; r < R; ++r) {
+        if (passes_out) passes_out[r] = hpass[(size_t)r];
+        if (status_out) status_out[r] = herr[(size_t)r];
+        if (herr[(size_t)r] != 0 && first < 0) first = r;
+    }
+    if (first >= 0)
+        return fail(c, herr[(size_t)first],
+                    std::string(device_error_message(herr[(size_t)first])) + " (chain " +
+                        std::to_string(first) + ")",
+                    (int64_t)hidx[(size_t)first]);
+    return GS_OK;
+}
+
 extern "C" {
 
 const char *gs_version(void) { return kVersion; }
@@ -661,6 +977,38 @@ int gs_motif_sampling(gs_ctx *c, int32_t W, double pc, double cutoff, uint64_t s
     return gs_state_get(c, pos_out, pwms_out);
 }
 
+int gs_motif_sampling_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds,
+                            int32_t n_chains, int32_t init_mode, int32_t max_passes,
+                            int32_t *pos_out, double *pwms_out, int32_t *passes_out,
+                            int32_t *status_out) {
+    if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
+        return GS_E_ARG;
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!pos_out || !pwms_out))) return GS_E_ARG;
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_batch: every chain walks all targets in order "
+                    "(.fs:885-929): it needs all sequences on one device and no communicator");
+    if (c->use_pcv || c->use_ppm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_batch: the ByPCV / OfPPM twins are not batched (clear "
+                    "the fixed PCV / PPM, or loop gs_motif_sampling)");
+    takeover_reset(c);
+    return motif_batch(c, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, pos_out,
+                       pwms_out, passes_out, status_out);
+}
+
+int gs_batch_last_ms(const gs_ctx *c, double out[2]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->batch_ms[0];
+    out[1] = c->batch_ms[1];
+    return GS_OK;
+}
+
 int gs_counts(gs_ctx *c, int32_t W, const int32_t *pos, int64_t *C_out, int64_t *T_out) {
     if (!c || !C_out || !T_out || (c->n_local > 0 && !pos)) return GS_E_ARG;
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
@@ -737,28 +1085,8 @@ int gs_random_starts(gs_ctx *c, int32_t W, double pc, uint64_t seed, int32_t mod
     if (mode == 0) {
         const size_t bytes = (size_t)c->n_global * AW * 4;
         HIP_TRY(c, hipMalloc(&d_cpart, std::max<size_t>(bytes, 4)));
-        HIP_TRY(c, hipMemsetAsync(d_cpart, 0, bytes, c->stream));
-        PartialArgs p{};
-        p.seq = c->d_seq;
-        p.doff = c->d_doff;
-        p.len = c->d_len;
-        p.n_local = c->n_local;
-        p.global_offset = c->global_offset;
-        p.n_global = c->n_global;
-        p.A = A;
-        p.W = W;
-        p.seed = seed;
-        p.cpart = d_cpart;
-        if (c->n_local > 0) {
-            int grid = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_global, c->n_cu * 8));
-            HIP_TRY(c, gs_starts_partial_launch(p, grid, c->stream));
-        }
-        if (c->comm)
-            RCCL_TRY(c, ncclAllReduce(d_cpart, d_cpart, (size_t)c->n_global * AW, ncclInt32,
-                                      ncclSum, c->comm, c->stream));
     }
-    rc = starts_pass(c, mode, W, pc, seed, nullptr, d_cpart, c->d_agg[c->cur_agg], c->d_pwms,
-                     c->d_pos[1], c->use_ppm ? c->d_ppm_fixed : nullptr);
+    rc = starts_enqueue(c, mode, W, pc, seed, d_cpart);
     if (rc == GS_OK) HIP_TRY(c, hipStreamSynchronize(c->stream));
     dfree(d_cpart);
     if (rc) return rc;

@@ -105,6 +105,8 @@ hipError_t gs_agg_convert_launch(int64_t *rep, int64_t *vec, int32_t cells, int3
 hipError_t gs_starts_launch(const StartsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 hipError_t gs_greedy_launch(const GreedyArgs &a, int waves, size_t lds_bytes, hipStream_t stream,
                             hipEvent_t start, hipEvent_t stop);
+hipError_t gs_greedy_batch_launch(const GreedyArgs &a, int n_chains, int waves, size_t lds_bytes,
+                                  hipStream_t stream, hipEvent_t start, hipEvent_t stop);
 hipError_t gs_starts_partial_launch(const PartialArgs &a, int grid, hipStream_t s);
 hipError_t gs_site_shift_launch(const int32_t *pos, const int32_t *len, int32_t n, int32_t W,
                                 int32_t dir, int32_t *out, hipStream_t s);
@@ -222,6 +224,7 @@ struct gs_ctx {
     double *d_ppm_fixed = nullptr;  // [A][ppm_W]
     int32_t ppm_W = 0;
     int32_t last_greedy_waves = 0;
+    double batch_ms[2] = {0.0, 0.0};  // the last batch call: stage 1 (all chains), greedy launch
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG
     // draws of kGraphSweeps sweeps from a device sweep counter, d_u6) + kGraphSweeps x
@@ -319,6 +322,7 @@ struct MultiBufs {
 
 constexpr int64_t kArenaBudget = 4ll << 30;     // bytes of category arenas per launch
 constexpr int64_t kArenaMax = 1ll << 28;        // categories per target
+constexpr int64_t kBatchBytesMax = 4ll << 30;   // bytes of chain slabs per batch call
 
 void drop_graphs(gs_ctx *c);
 void free_state(gs_ctx *c);

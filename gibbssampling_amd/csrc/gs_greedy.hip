@@ -555,8 +555,26 @@ __device__ __forceinline__ void move_segment(const GreedyArgs &a, const Shared &
 // site sampler's getBestPWMSsWithStartPositions (.fs:554-585).
 // DT: the D table's element type (uint16_t when every D_k[b] <= K*W fits, halving the
 // site slice so more wavefronts fit in LDS; int32_t otherwise and for the motif sampler)
-template <bool SITE, int WM, typename DT>
+// BATCH (motif sampler only): R independent chains in one launch, workgroup r on chain
+// r's slab of the caller's buffers: pos / pwms at r * n elements, the aggregates at
+// r * kRepl * stride, passes_out / err words at r.  Sequences, descriptors, compositions
+// and the LDS carve are shared, nothing else is, so the workgroups never wait on each
+// other and any R may queue.  A chain whose err word is set (its stage 1, or an overflow
+// in its passes) ends alone.  A flag of this kernel, not a shared __device__ body behind
+// two entries: that form changed the single-chain kernel's register allocation (same
+// VGPRs, other SGPR spills), this one leaves its code as it was.
+template <bool SITE, int WM, typename DT, bool BATCH = false>
 __global__ void __launch_bounds__(512) gs_greedy_kernel(GreedyArgs a) {
+    static_assert(!(BATCH && SITE), "the site sampler's repetitions are not batched");
+    if constexpr (BATCH) {
+        const int64_t r = blockIdx.x;
+        a.pos += r * a.n;
+        a.pwms += r * a.n;
+        a.agg += r * ((int64_t)kRepl * a.stride);
+        a.passes_out += r;
+        a.err_code += r;
+        a.err_index += r;
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int WS = tab_stride(WM);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -850,6 +868,17 @@ static const void *greedy_kernel_ptr(int wm, bool site, bool d16) {
     return nullptr;
 }
 
+static const void *greedy_batch_kernel_ptr(int wm) {
+    switch (wm) {
+#define GS_CASE(N) \
+    case N:        \
+        return (const void *)&gs_greedy_kernel<false, N, int32_t, true>;
+        GS_FOR_EACH_WM(GS_CASE)
+#undef GS_CASE
+    }
+    return nullptr;
+}
+
 int gs_sweep_wm(int W);
 
 // One workgroup of `waves` wavefronts; lds_bytes from the host carve (gs_api.cpp).
@@ -861,4 +890,19 @@ hipError_t gs_greedy_launch(const GreedyArgs &a, int waves, size_t lds_bytes, hi
     void *params[] = {&args};
     return hipExtLaunchKernel(k, dim3(1), dim3(64 * waves), params, lds_bytes, stream, start, stop,
                               0);
+}
+
+// n_chains workgroups of `waves` wavefronts, chain r on slab r of a's buffers (dense: the
+// strides are a.n and kRepl * a.stride); a.exit_chunk must be 0 (every pass in-kernel)
+// and a.site 0.
+hipError_t gs_greedy_batch_launch(const GreedyArgs &a, int n_chains, int waves, size_t lds_bytes,
+                                  hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+    const void *k = greedy_batch_kernel_ptr(gs_sweep_wm(a.W));
+    if (!k || n_chains < 1 || a.site != 0 || a.exit_chunk != 0 || a.exit_out != nullptr ||
+        waves < 1 || waves > 8 || (waves & (waves - 1)))
+        return hipErrorInvalidValue;
+    GreedyArgs args = a;
+    void *params[] = {&args};
+    return hipExtLaunchKernel(k, dim3(n_chains), dim3(64 * waves), params, lds_bytes, stream,
+                              start, stop, 0);
 }

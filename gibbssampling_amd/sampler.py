@@ -169,10 +169,25 @@ class MotifSampler:
                                              motifLength: int, pseudoCount: float,
                                              cutOff: float, alphabet, sources,
                                              seed: int | None = None, init_mode: int = 0,
-                                             device: int = 0) -> list[MotifIndex]:
+                                             device: int = 0,
+                                             batch: bool = False) -> list[MotifIndex]:
         """Repeated doMotifSampling keeping the run of largest Σ PWMS (.fs:973-998);
-        run r uses seed + r."""
+        run r uses seed + r.  batch=True (motifAmount = 1) computes every run
+        r = 0 … numberOfRepetitions in one Context.motif_sampling_batch call, the runs'
+        greedy passes side by side on the GPU, and replays the same loop over them:
+        the same result, all runs paid for even when the loop stops early."""
         base = _seed(seed)
+        if batch:
+            if motifAmount != 1:
+                raise _native.ArgumentError(
+                    _native.GS_E_ARG, "batch=True runs the single-position chains only "
+                    "(motifAmount = 1)")
+            ctx = _bind(alphabet, sources, device)
+            return _replay_repetitions(
+                numberOfRepetitions,
+                _batched_runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength,
+                              pseudoCount, cutOff, base, init_mode),
+                lambda xs: sum(x.PWMS for x in xs), [createMotifIndex(0.0, [])])
         return _best_of_repetitions(
             numberOfRepetitions,
             lambda r: MotifSampler.doMotifSampling(motifAmount, motifLength, pseudoCount,
@@ -314,11 +329,35 @@ def _seed(seed: int | None) -> int:
     return int(seed) & (2**64 - 1)
 
 
+def _batched_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
+                  init_mode: int) -> Callable[[int], list]:
+    """Runs r = 0 … count - 1 of doMotifSampling (seed base + r) by one batch call,
+    as a run(r) lookup for _replay_repetitions.  A run that raised raises when the
+    loop asks for it, as the sequential loop would."""
+    pos, pwms, _, status = ctx.motif_sampling_batch(
+        motifLength, pseudoCount, cutOff, [base + r for r in range(count)], init_mode, UNBOUNDED)
+
+    def run(r: int) -> list:
+        if status[r] != _native.GS_OK:
+            raise _native._ERRORS.get(int(status[r]), _native.DeviceError)(
+                int(status[r]), f"run {r} of the batch failed")
+        return _motif_indices(pos[r], pwms[r])
+    return run
+
+
 def _best_of_repetitions(numberOfRepetitions: int, run: Callable[[int], list], ic: Callable,
                          initial_best: list) -> list:
     """The repetition loop shared by getMotifsWithBestInformationContent(s)
-    (.fs:615-640, .fs:973-998): stop after numberOfRepetitions or when a run equals
-    the best; a run whose Σ score beats the best replaces it (one step later)."""
+    (.fs:615-640, .fs:973-998), each run computed when the loop reaches it."""
+    return _replay_repetitions(numberOfRepetitions, run, ic, initial_best)
+
+
+def _replay_repetitions(numberOfRepetitions: int, run: Callable[[int], list], ic: Callable,
+                        initial_best: list) -> list:
+    """The loop of .fs:615-640 / .fs:973-998 over a run(r) lookup (computed on demand, or
+    a finished table of runs 0 … numberOfRepetitions): stop after numberOfRepetitions or
+    when a run equals the best; a run whose Σ score beats the best replaces it (one
+    step later)."""
     n, acc, best = 0, [], initial_best
     while True:
         if n > numberOfRepetitions or acc == best:

@@ -142,6 +142,22 @@ int gs_motif_greedy(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
 int gs_motif_sampling(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
                       uint64_t seed, int32_t init_mode, int32_t max_passes, int32_t *pos_out,
                       double *pwms_out, int32_t *passes_out);
+/* R independent doMotifSampling runs (.fs:1034-1038, motifAmount = 1): chain r is exactly
+ * gs_motif_sampling(ctx, W, pc, cut_off, seeds[r], init_mode, max_passes, ...).
+ * pos_out / pwms_out: [n_chains][n_local] row-major; passes_out, status_out: [n_chains]
+ * (both nullable).  Returns the status of the lowest-index failing chain (gs_error_index:
+ * its sequence), GS_OK if none; the other chains' rows are still valid.
+ * The chains' first stages run back to back on the context's stream, their greedy passes
+ * as one launch of n_chains workgroups, with one synchronisation in all.  n_chains == 0
+ * does nothing.  GS_E_UNSUPPORTED: sharded sequences or a communicator, a fixed PCV or
+ * PPM, or chain slabs beyond 4 GiB.  The context holds no snapshot afterwards. */
+int gs_motif_sampling_batch(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+                            const uint64_t *seeds, int32_t n_chains, int32_t init_mode,
+                            int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                            int32_t *passes_out, int32_t *status_out);
+/* Device times of the last gs_motif_sampling_batch, ms: out[0] the chains' first stages
+ * (starts, snapshot, sweep, copies), out[1] the batched greedy launch. */
+int gs_batch_last_ms(const gs_ctx *ctx, double out[2]);
 
 /* --- motifAmount >= 1 with Positions lists ---------- */
 /* MotifIndex (.fs:712-716) with Positions lists: entry n is (cnt[n], pos[n*cap ..
