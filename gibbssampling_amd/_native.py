@@ -157,6 +157,8 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_site_scan": (C.c_int, [vp, i32, f64, vp, vp, vp]),
         "gs_site_refine": (C.c_int, [vp, i32, f64, i32, i32, vp, vp, P(i32)]),
         "gs_site_sampling": (C.c_int, [vp, i32, f64, u64, i32, i32, vp, vp, vp]),
+        "gs_site_sampling_batch": (C.c_int, [vp, i32, f64, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "gs_site_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_counts": (C.c_int, [vp, i32, vp, vp, vp]),
         "gs_random_starts": (C.c_int, [vp, i32, f64, u64, i32, vp, vp]),
         "gs_best_pwms": (C.c_int, [vp, i32, f64, i32, vp, vp, P(f64), P(i32)]),
@@ -481,6 +483,34 @@ class Context:
                                               int(init_mode), int(max_passes), _ptr(pos),
                                               _ptr(score), _ptr(passes)))
         return pos, score, passes
+
+    def site_sampling_batch(self, W: int, pc: float, seeds, init_mode: int = 0,
+                            max_passes: int = 1000):
+        """R independent doSiteSampling runs in one call, row r exactly
+        site_sampling(W, pc, seeds[r], ...): the chains' Gauss–Seidel passes run as R
+        concurrent workgroups, their shifted passes side by side ->
+        (pos[R, N], score[R, N], passes[R, 3], status[R]).  A chain that raises
+        (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows valid; errors of the
+        call itself raise."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        pos = np.empty((R, self.n_local), np.int32)
+        score = np.empty((R, self.n_local), np.float64)
+        passes = np.zeros((R, 3), np.int32)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_site_sampling_batch(self.h, int(W), float(pc), _ptr(seeds), R,
+                                             int(init_mode), int(max_passes), _ptr(pos),
+                                             _ptr(score), _ptr(passes), _ptr(status))
+        if st != GS_OK and not status.any():
+            self._check(st)
+        return pos, score, passes, status
+
+    def site_batch_last_ms(self):
+        """Device milliseconds of the last site_sampling_batch: (starts, Gauss–Seidel
+        launch, shifted passes)."""
+        out = np.zeros(3, np.float64)
+        self._check(self.lib.gs_site_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def counts(self, W: int, pos, A: int):
         pos = np.ascontiguousarray(pos, dtype=np.int32)

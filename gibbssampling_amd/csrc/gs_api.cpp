@@ -165,11 +165,12 @@ static int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool res
     return GS_OK;
 }
 
-// The motif sampler's greedy arguments that do not name a chain's buffers, with the LDS
-// carve of greedy_run (gs_engine.cpp, site = 0): the workgroup part, the visit ring of
-// 2 * waves slots, one (PWM, PCV) table slice per wavefront.
-static int greedy_carve(gs_ctx *c, double pc, double cutoff, int32_t max_passes, GreedyArgs &a,
-                        int &waves_out, int64_t &lds_out) {
+// The greedy arguments that do not name a chain's buffers, with the LDS carve of
+// greedy_run (gs_engine.cpp): the workgroup part, the visit ring of 2 * waves slots, one
+// slice per wavefront: the (PWM, PCV) table and the PCV (site = 0, the motif sampler), or
+// the D table, the others' background and the composition (site = 1, the site sampler).
+static int greedy_carve(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes,
+                        GreedyArgs &a, int &waves_out, int64_t &lds_out) {
     const int A = c->A, E = c->E, W = c->W, WM = gs_sweep_wm(W);
     int64_t o = 0;
     auto take = [&](int64_t b) {
@@ -184,11 +185,24 @@ static int greedy_carve(gs_ctx *c, double pc, double cutoff, int32_t max_passes,
     a.o_ctl = take(4 * 64);
     const int64_t fixed = o;
     a.ring_seq_bytes = (int32_t)(align16(c->Lmax) + align16(WM) + 32);
-    a.w_tab = 0;
-    int64_t wb = align16(16 * (int64_t)E * tab_stride(WM));
-    a.w_pcv = (int32_t)wb;
-    wb += 8 * 64;
+    int64_t wb = 0;
+    if (site) {
+        a.w_dt = 0;
+        // D_k[b] <= (k + 1) W <= Lmax W: two bytes an entry when that fits
+        a.dt16 = (int64_t)c->Lmax * W < 65536 && c->tune.site_dt16 ? 1 : 0;
+        wb = align16((a.dt16 ? 2 : 4) * (int64_t)c->Lmax * A);
+        a.w_bg = (int32_t)wb;
+        wb += 8 * 64;
+        a.w_comp = (int32_t)wb;
+        wb += 4 * 64;
+    } else {
+        a.w_tab = 0;
+        wb = align16(16 * (int64_t)E * tab_stride(WM));
+        a.w_pcv = (int32_t)wb;
+        wb += 8 * 64;
+    }
     a.wave_bytes = (int32_t)wb;
+    a.site = site;
     const int64_t per_wave = wb + 2 * (a.ring_seq_bytes + 4 * 3 + 8 + 4 * 64) + 64 + 32;
     int waves = c->tune.greedy_waves;
     while (waves > 1 && fixed + per_wave * waves > c->max_lds) --waves;
@@ -203,7 +217,9 @@ static int greedy_carve(gs_ctx *c, double pc, double cutoff, int32_t max_passes,
     a.o_rcomp = take(4 * 64 * (int64_t)R);
     a.o_red = take(8 * 4 * (int64_t)waves);
     a.o_wave = take((int64_t)waves * a.wave_bytes);
-    a.motif_coop = c->tune.motif_coop;
+    a.site_coop = site && c->tune.site_coop ? 1 : 0;
+    a.motif_coop = site ? 0 : c->tune.motif_coop;
+    a.coop_rate = site ? c->tune.coop_rate : 0.0f;
     if (o > c->max_lds)
         return fail(c, GS_E_UNSUPPORTED,
                     "longest sequence exceeds the greedy kernel's LDS budget (" +
@@ -236,7 +252,12 @@ struct BatchBufs {
     double *pwms = nullptr;
     int64_t *agg = nullptr;
     unsigned long long *erri = nullptr;
+    // the site batch's shifted passes: start vectors, stage pass counts, pass control
+    int32_t *shifted = nullptr, *stage_passes = nullptr, *ctl = nullptr;
     ~BatchBufs() {
+        dfree(shifted);
+        dfree(stage_passes);
+        dfree(ctl);
         dfree(pos);
         dfree(passes);
         dfree(err);
@@ -271,7 +292,7 @@ static int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uin
     GreedyArgs a{};
     int waves = 0;
     int64_t lds = 0;
-    if ((rc = greedy_carve(c, pc, cutoff, max_passes, a, waves, lds))) return rc;
+    if ((rc = greedy_carve(c, 0, pc, cutoff, max_passes, a, waves, lds))) return rc;
     const int64_t agg_elems = (int64_t)kRepl * c->stride;
     const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
     const int64_t bytes = (int64_t)R * (n * (4 + 8 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 16) +
@@ -382,6 +403,193 @@ static int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uin
     int first = -1;
     for (int32_t r = 0; r < R; ++r) {
         if (passes_out) passes_out[r] = hpass[(size_t)r];
+        if (status_out) status_out[r] = herr[(size_t)r];
+        if (herr[(size_t)r] != 0 && first < 0) first = r;
+    }
+    if (first >= 0)
+        return fail(c, herr[(size_t)first],
+                    std::string(device_error_message(herr[(size_t)first])) + " (chain " +
+                        std::to_string(first) + ")",
+                    (int64_t)hidx[(size_t)first]);
+    return GS_OK;
+}
+
+// R independent doSiteSampling runs (.fs:697-701), DESIGN.md §9.11.  Stage 1, chain after
+// chain on the context's single-chain state and stream, no host wait in between: starts
+// (seed r) -> snapshot of them -> device copies of positions, scores, replica aggregates
+// and the error words into slab r.  Stage 2: getBestPWMSsWithStartPositions of every
+// chain as one launch of the star site engine, workgroup r on slab r, every pass
+// in-kernel.  Stage 3: the shifted passes (-1 to completion, then +1), every running
+// chain in the same launches, one synchronisation per pass for all chains.  The caller
+// validated the arguments.
+static int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
+                      int32_t max_passes, int32_t *pos_out, double *score_out,
+                      int32_t *passes_out, int32_t *status_out) {
+    int rc;
+    const int64_t n = c->n_local;
+    if (n == 0) {
+        for (int32_t r = 0; r < R; ++r) {
+            if (passes_out) passes_out[3 * r] = passes_out[3 * r + 1] = passes_out[3 * r + 2] = 0;
+            if (status_out) status_out[r] = GS_OK;
+        }
+        return GS_OK;
+    }
+    if ((rc = ensure_state(c, W))) return rc;
+    GreedyArgs a{};
+    int waves = 0;
+    int64_t lds = 0;
+    if ((rc = greedy_carve(c, 1, pc, 0.0, max_passes, a, waves, lds))) return rc;
+    const int64_t agg_elems = (int64_t)kRepl * c->stride;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    // per chain: positions, scores, shifted starts (and the shared draws), aggregates,
+    // Gauss–Seidel passes, error words, stage passes [3], pass control [3]
+    const int64_t bytes =
+        (int64_t)R * (n * (4 + 8 + 4 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 4 + 4 + 8 + 12 + 12) +
+        cpart_bytes;
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_site_sampling_batch: the chains' slabs take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a batch may hold: split the seeds over several calls");
+    BatchBufs b;
+    HIP_TRY(c, hipMalloc(&b.pos, (size_t)(R * n) * 4));
+    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)(R * n) * 8));
+    HIP_TRY(c, hipMalloc(&b.shifted, (size_t)(R * n) * 4));
+    HIP_TRY(c, hipMalloc(&b.agg, (size_t)(R * agg_elems) * 8));
+    HIP_TRY(c, hipMalloc(&b.passes, (size_t)R * 4));
+    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 4));
+    HIP_TRY(c, hipMalloc(&b.erri, (size_t)R * 8));
+    HIP_TRY(c, hipMalloc(&b.stage_passes, (size_t)R * 12));
+    HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * 12));
+    int32_t *d_run = b.ctl, *d_moved = b.ctl + R, *d_left = b.ctl + 2 * (int64_t)R;
+    // the shifted scans' arguments: the chains' slabs, the D table in LDS
+    StartsArgs sa{};
+    int64_t slds = 0;
+    if ((rc = starts_pass(c, 2, W, pc, 0, b.shifted, nullptr, b.agg, b.pwms, b.pos, nullptr, &sa,
+                          &slds)))
+        return rc;
+    if (sa.dt_global)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_site_sampling_batch: the scan's D table of the longest sequence does "
+                    "not fit in LDS (loop gs_site_sampling)");
+    sa.err_code = b.err;
+    sa.err_index = b.erri;
+    const int scan_blocks =
+        (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)c->n_cu * 8 + R - 1) / R));
+    const int agg_blocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
+    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
+    if (mode == 0) {
+        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
+    } else {
+        HIP_TRY(c, hipMalloc(&b.starts, (size_t)(R * n) * 4));
+        hs.resize((size_t)(R * n));
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = 0; i < n; ++i)
+                hs[(size_t)(r * n + i)] =
+                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
+                                c->h_len[i] - W + 1);
+        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
+                                  c->stream));
+    }
+    hipEvent_t ev[4] = {get_event(c), get_event(c), get_event(c), get_event(c)};
+    auto recycle = [&]() {
+        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
+    };
+    std::vector<int32_t> left((size_t)R);
+    rc = [&]() -> int {
+        int rc2;
+        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+        for (int32_t r = 0; r < R; ++r) {
+            // (as motif_batch) the start vector the aggregate pass reads
+            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
+                return rc2;
+            // a target that raises (.fs:117) writes no start: every entry stays a valid one
+            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
+            // the acc of the refinements (site_upload): the starts, their aggregates
+            if ((rc2 = set_snapshot_dev(c, W, c->d_pos[1], false))) return rc2;
+            HIP_TRY(c, hipMemcpyAsync(b.pos + r * n, c->d_pos[0], (size_t)n * 4,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.pwms + r * n, c->d_pwms, (size_t)n * 8,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.agg + r * agg_elems, c->d_agg[c->cur_agg],
+                                      (size_t)agg_elems * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.err + r, c->d_err_code, 4, hipMemcpyDeviceToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b.erri + r, c->d_err_index, 8, hipMemcpyDeviceToDevice,
+                                      c->stream));
+        }
+        // the context's own error words end clear, whatever the last chain's were
+        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(b.stage_passes, 0, (size_t)R * 12, c->stream));
+        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+        a.agg = b.agg;
+        a.pos = b.pos;
+        a.pwms = b.pwms;
+        a.passes_out = b.passes;
+        a.err_code = b.err;
+        a.err_index = b.erri;
+        a.exit_chunk = 0;
+        a.exit_out = nullptr;
+        HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
+        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+        const int32_t dirs[2] = {-1, 1};
+        for (int st = 0; st < 2; ++st) {
+            HIP_TRY(c, gs_site_batch_ctl_launch(R, 0, 1 + st, max_passes, d_run, d_moved, b.err,
+                                                b.stage_passes, d_left, c->stream));
+            for (int32_t pass = 1; pass <= max_passes; ++pass) {
+                HIP_TRY(c, hipMemsetAsync(b.agg, 0, (size_t)(R * agg_elems) * 8, c->stream));
+                HIP_TRY(c, gs_site_batch_pass_launch(sa, (size_t)slds, R, dirs[st], c->E, c->d_comp,
+                                                     d_run, d_moved, b.shifted, agg_blocks,
+                                                     scan_blocks, c->stream));
+                HIP_TRY(c, gs_site_batch_ctl_launch(R, pass, 1 + st, max_passes, d_run, d_moved,
+                                                    b.err, b.stage_passes, d_left, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(left.data(), d_left, (size_t)R * 4, hipMemcpyDeviceToHost,
+                                          c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                if (std::all_of(left.begin(), left.end(), [](int32_t v) { return v == 0; })) break;
+            }
+        }
+        HIP_TRY(c, hipEventRecord(ev[3], c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    // the context's single-chain buffers were the chains' scratch: no snapshot is left
+    c->have_state = false;
+    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+    c->note_pending = false;
+    c->ftab_agg = -1;
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
+        recycle();
+        return rc;
+    }
+    c->last_greedy_waves = waves;
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+        c->site_batch_ms[i] = (double)ms;
+    }
+    recycle();
+    std::vector<int32_t> herr((size_t)R), hpass((size_t)R), hstage((size_t)R * 3);
+    std::vector<unsigned long long> hidx((size_t)R);
+    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hstage.data(), b.stage_passes, (size_t)R * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(score_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
+    int first = -1;
+    for (int32_t r = 0; r < R; ++r) {
+        if (passes_out) {
+            passes_out[3 * r] = hpass[(size_t)r];
+            passes_out[3 * r + 1] = hstage[(size_t)r * 3 + 1];
+            passes_out[3 * r + 2] = hstage[(size_t)r * 3 + 2];
+        }
         if (status_out) status_out[r] = herr[(size_t)r];
         if (herr[(size_t)r] != 0 && first < 0) first = r;
     }
@@ -1231,6 +1439,37 @@ int gs_site_sampling(gs_ctx *c, int32_t W, double pc, uint64_t seed, int32_t ini
         }
     }
     return site_download(c, pos_out, score_out);
+}
+
+int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t n_chains,
+                           int32_t init_mode, int32_t max_passes, int32_t *pos_out,
+                           double *score_out, int32_t *passes_out, int32_t *status_out) {
+    if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
+        return GS_E_ARG;
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!pos_out || !score_out))) return GS_E_ARG;
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_site_sampling_batch: getBestPWMSsWithStartPositions walks every target "
+                    "in order (.fs:554-585): it needs all sequences on one device and no "
+                    "communicator");
+    if (c->use_pcv || c->use_ppm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_site_sampling_batch: the WithBPV / OfPPM twins are not batched (clear "
+                    "the fixed PCV / PPM, or loop gs_site_sampling)");
+    takeover_reset(c);
+    return site_batch(c, W, pc, seeds, n_chains, init_mode, max_passes, pos_out, score_out,
+                      passes_out, status_out);
+}
+
+int gs_site_batch_last_ms(const gs_ctx *c, double out[3]) {
+    if (!c || !out) return GS_E_ARG;
+    for (int i = 0; i < 3; ++i) out[i] = c->site_batch_ms[i];
+    return GS_OK;
 }
 
 int gs_profile_enable(gs_ctx *c, int32_t enable) {

@@ -107,6 +107,14 @@ hipError_t gs_greedy_launch(const GreedyArgs &a, int waves, size_t lds_bytes, hi
                             hipEvent_t start, hipEvent_t stop);
 hipError_t gs_greedy_batch_launch(const GreedyArgs &a, int n_chains, int waves, size_t lds_bytes,
                                   hipStream_t stream, hipEvent_t start, hipEvent_t stop);
+hipError_t gs_site_batch_ctl_launch(int32_t n_chains, int32_t pass, int32_t stage,
+                                    int32_t max_passes, int32_t *run, int32_t *moved,
+                                    const int32_t *err, int32_t *passes, int32_t *out,
+                                    hipStream_t s);
+hipError_t gs_site_batch_pass_launch(const StartsArgs &a, size_t lds_bytes, int32_t n_chains,
+                                     int32_t dir, int32_t E, const int32_t *comp,
+                                     const int32_t *run, int32_t *moved, int32_t *shifted,
+                                     int agg_blocks, int scan_blocks, hipStream_t s);
 hipError_t gs_starts_partial_launch(const PartialArgs &a, int grid, hipStream_t s);
 hipError_t gs_site_shift_launch(const int32_t *pos, const int32_t *len, int32_t n, int32_t W,
                                 int32_t dir, int32_t *out, hipStream_t s);
@@ -225,6 +233,7 @@ struct gs_ctx {
     int32_t ppm_W = 0;
     int32_t last_greedy_waves = 0;
     double batch_ms[2] = {0.0, 0.0};  // the last batch call: stage 1 (all chains), greedy launch
+    double site_batch_ms[3] = {0.0, 0.0, 0.0};  // the last site batch: starts, Gauss–Seidel launch, shifted passes
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG
     // draws of kGraphSweeps sweeps from a device sweep counter, d_u6) + kGraphSweeps x

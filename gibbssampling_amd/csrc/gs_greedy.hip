@@ -555,7 +555,7 @@ __device__ __forceinline__ void move_segment(const GreedyArgs &a, const Shared &
 // site sampler's getBestPWMSsWithStartPositions (.fs:554-585).
 // DT: the D table's element type (uint16_t when every D_k[b] <= K*W fits, halving the
 // site slice so more wavefronts fit in LDS; int32_t otherwise and for the motif sampler)
-// BATCH (motif sampler only): R independent chains in one launch, workgroup r on chain
+// BATCH: R independent chains in one launch (either sampler), workgroup r on chain
 // r's slab of the caller's buffers: pos / pwms at r * n elements, the aggregates at
 // r * kRepl * stride, passes_out / err words at r.  Sequences, descriptors, compositions
 // and the LDS carve are shared, nothing else is, so the workgroups never wait on each
@@ -565,7 +565,6 @@ __device__ __forceinline__ void move_segment(const GreedyArgs &a, const Shared &
 // VGPRs, other SGPR spills), this one leaves its code as it was.
 template <bool SITE, int WM, typename DT, bool BATCH = false>
 __global__ void __launch_bounds__(512) gs_greedy_kernel(GreedyArgs a) {
-    static_assert(!(BATCH && SITE), "the site sampler's repetitions are not batched");
     if constexpr (BATCH) {
         const int64_t r = blockIdx.x;
         a.pos += r * a.n;
@@ -868,11 +867,13 @@ static const void *greedy_kernel_ptr(int wm, bool site, bool d16) {
     return nullptr;
 }
 
-static const void *greedy_batch_kernel_ptr(int wm) {
+static const void *greedy_batch_kernel_ptr(int wm, bool site, bool d16) {
     switch (wm) {
 #define GS_CASE(N) \
     case N:        \
-        return (const void *)&gs_greedy_kernel<false, N, int32_t, true>;
+        return !site ? (const void *)&gs_greedy_kernel<false, N, int32_t, true> \
+               : d16 ? (const void *)&gs_greedy_kernel<true, N, uint16_t, true> \
+                     : (const void *)&gs_greedy_kernel<true, N, int32_t, true>;
         GS_FOR_EACH_WM(GS_CASE)
 #undef GS_CASE
     }
@@ -893,12 +894,12 @@ hipError_t gs_greedy_launch(const GreedyArgs &a, int waves, size_t lds_bytes, hi
 }
 
 // n_chains workgroups of `waves` wavefronts, chain r on slab r of a's buffers (dense: the
-// strides are a.n and kRepl * a.stride); a.exit_chunk must be 0 (every pass in-kernel)
-// and a.site 0.
+// strides are a.n and kRepl * a.stride); a.exit_chunk must be 0 (every pass in-kernel).
+// a.site 1: the site sampler's getBestPWMSsWithStartPositions of every chain.
 hipError_t gs_greedy_batch_launch(const GreedyArgs &a, int n_chains, int waves, size_t lds_bytes,
                                   hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
-    const void *k = greedy_batch_kernel_ptr(gs_sweep_wm(a.W));
-    if (!k || n_chains < 1 || a.site != 0 || a.exit_chunk != 0 || a.exit_out != nullptr ||
+    const void *k = greedy_batch_kernel_ptr(gs_sweep_wm(a.W), a.site != 0, a.dt16 != 0);
+    if (!k || n_chains < 1 || a.exit_chunk != 0 || a.exit_out != nullptr ||
         waves < 1 || waves > 8 || (waves & (waves - 1)))
         return hipErrorInvalidValue;
     GreedyArgs args = a;

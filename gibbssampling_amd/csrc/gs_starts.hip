@@ -398,6 +398,218 @@ gs_site_accept_kernel(const double *tmp_score, const int32_t *tmp_pos, double *s
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(moved, __popcll(b));
 }
 
+// ---- gs_site_sampling_batch: the shifted passes of R chains at once ----
+//
+// Chain r owns slab r of every per-chain buffer: acc positions / scores and the shifted
+// start vector at r * n, the aggregates at r * kRepl * stride, run / moved / error words
+// at r.  Chain and block are linearised in blockIdx.x (r = blockIdx.x / blocks per chain),
+// a chain whose run flag is clear costs an early return per block, and no workgroup waits
+// on another: the pass boundary is the kernel boundary.
+struct SiteBatchArgs {
+    const int32_t *run;      // [R] 1 while the chain's stage goes on
+    int32_t *moved;          // [R] targets whose start changed in this pass
+    const int32_t *comp;     // [n][E+1] static symbol histograms
+    const int32_t *acc_pos;  // [R][n]
+    int32_t *shifted;        // [R][n] the pass's start vector of the others
+    int64_t *agg;            // [R][kRepl * stride], zeroed before the pass
+    int32_t E, dir;
+    int32_t blocks;          // workgroups per chain of the launch
+};
+
+// Pass control, one thread per chain.  pass 0 opens a stage: every chain without an error
+// runs.  pass >= 1 closes that pass: a running chain records it, and ends at a pass that
+// moved nothing, at max_passes, or with its error word set.  out[r]: the chain's moves
+// when it goes on, 0 when it does not (the host stops at all zero).
+extern "C" __global__ void __launch_bounds__(256)
+gs_site_batch_ctl_kernel(int32_t n_chains, int32_t pass, int32_t stage, int32_t max_passes,
+                         int32_t *run, int32_t *moved, const int32_t *err, int32_t *passes,
+                         int32_t *out) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_chains) return;
+    if (pass == 0) {
+        run[r] = err[r] == 0 ? 1 : 0;
+        moved[r] = 0;
+        return;
+    }
+    if (!run[r]) {
+        out[r] = 0;
+        return;
+    }
+    const int m = moved[r];
+    moved[r] = 0;
+    passes[r * 3 + stage] = pass;
+    const bool fin = m == 0 || pass >= max_passes || err[r] != 0;
+    if (fin) run[r] = 0;
+    out[r] = fin ? 0 : m;
+}
+
+// The shifted start vector of a running chain (the rule of gs_site_shift_kernel) and its
+// aggregates: C[a][j] the segment counts, T[a] composition minus segment counts, summed
+// in LDS, then one 64-bit atomic per non-zero cell into replica 0 of the chain's slab
+// (the other replicas stay zero: the consumers sum over replicas).
+extern "C" __global__ void __launch_bounds__(256)
+gs_site_batch_agg_kernel(StartsArgs a, SiteBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int64_t r = blockIdx.x / b.blocks;
+    const int j0 = blockIdx.x - (int)r * b.blocks;
+    if (!b.run[r]) return;
+    const int A = a.A, W = a.W, AW = A * W, n = a.n_local, CS = b.E + 1;
+    unsigned long long *sT = (unsigned long long *)lds;  // [A]
+    int32_t *sC = (int32_t *)(lds + 8 * A);               // [A][W]
+    const int32_t *pos = b.acc_pos + r * n;
+    int32_t *sh = b.shifted + r * n;
+    for (int c = threadIdx.x; c < AW; c += 256) sC[c] = 0;
+    for (int c = threadIdx.x; c < A; c += 256) sT[c] = 0ull;
+    __syncthreads();
+    for (int64_t i = (int64_t)j0 * 256 + threadIdx.x; i < n; i += (int64_t)b.blocks * 256) {
+        const int L = a.len[i], p = pos[i];
+        const int q = b.dir > 0 ? (p <= L - W - 1 ? p + 1 : p) : (p > 0 ? p - 1 : p);
+        sh[i] = q;
+        const uint8_t *s = a.seq + a.doff[i] + q;
+        for (int j = 0; j < W; ++j) {
+            const int e = s[j];
+            if (e < A) {
+                atomicAdd(&sC[e * W + j], 1);
+                atomicAdd(&sT[e], ~0ull);
+            }
+        }
+        for (int x = 0; x < A; ++x)
+            atomicAdd(&sT[x], (unsigned long long)(long long)b.comp[i * CS + x]);
+    }
+    __syncthreads();
+    unsigned long long *g = (unsigned long long *)(b.agg + r * ((int64_t)kRepl * a.stride));
+    for (int c = threadIdx.x; c < AW; c += 256)
+        if (sC[c]) atomicAdd(&g[c], (unsigned long long)(long long)sC[c]);
+    for (int c = threadIdx.x; c < A; c += 256)
+        if (sT[c]) atomicAdd(&g[AW + c], sT[c]);
+}
+
+// getBestPWMSs of the targets of a running chain against its shifted start vector
+// (gs_starts_kernel's mode-2 body, the D table in LDS), with the accept
+// `fst tmp > fst acc.[n]` (.fs:509, .fs:544) fused: a target's accept touches only its
+// own acc entry, every other target reads the pass-start aggregates and start vector.
+// a's per-chain pointers (agg, starts, score_out / pos_out = the acc, the error words)
+// name slab 0.
+__global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, SiteBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int64_t r = blockIdx.x / b.blocks;
+    const int j0 = blockIdx.x - (int)r * b.blocks;
+    if (!b.run[r]) return;
+    a.agg += r * ((int64_t)kRepl * a.stride);
+    a.starts += r * a.n_local;
+    a.score_out += r * a.n_local;
+    a.pos_out += r * a.n_local;
+    a.err_code += r;
+    a.err_index += r;
+    const int lane = threadIdx.x;
+    const int A = a.A, W = a.W, AW = A * W;
+    double *ppm = (double *)(lds + a.o_ppm);            // [A][W]
+    int32_t *Dt = (int32_t *)(lds + a.o_Dt);            // [Lmax+1][A]
+    int32_t *cg = (int32_t *)(lds + a.o_cg);            // [A*W] + [A*W] scratch
+    int64_t *compall = (int64_t *)(lds + a.o_compall);  // [A]
+    int64_t *bg0 = (int64_t *)(lds + a.o_bg);           // [A]
+    int32_t *comp = (int32_t *)(lds + a.o_comp);        // [128]
+    uint8_t *sseq = (uint8_t *)(lds + a.o_seq);
+
+    for (int c = lane; c < a.cells; c += 64) {
+        int64_t s = 0;
+#pragma unroll
+        for (int q = 0; q < kRepl; ++q) s += a.agg[(int64_t)q * a.stride + c];
+        if (c < AW)
+            cg[c] = (int32_t)s;
+        else
+            compall[c - AW] = s;
+    }
+    __syncthreads();
+    if (lane < A) {
+        int64_t s = 0;
+        for (int j = 0; j < W; ++j) s += cg[lane * W + j];
+        compall[lane] += s;
+    }
+    __syncthreads();
+    for (int n = j0; n < a.n_local; n += b.blocks) {
+        const int L = a.len[n];
+        stage_sequence(a.seq + a.doff[n], L, sseq, comp, lane);
+        const int q = a.starts[n];
+        for (int c = lane; c < AW; c += 64) {
+            const int x = c / W, j = c - x * W;
+            const int32_t v = cg[c] - (sseq[q + j] == x ? 1 : 0);
+            ppm[c] = ((double)v + a.pc) / a.den;  // normalizePPM (.fs:257-260)
+            cg[AW + c] = v;
+        }
+        __syncthreads();
+        int64_t bsum = 0;
+        if (lane < A) {
+            int64_t s = 0;
+            for (int j = 0; j < W; ++j) s += cg[AW + lane * W + j];
+            const int64_t v = compall[lane] - comp[lane] - s;
+            bg0[lane] = v;
+            bsum = v;
+        }
+        bsum = wave_sum_i64(bsum);
+        __syncthreads();
+        double best;
+        int bestk;
+        bool overflow;
+        best_pwms_scan(sseq, L, W, A, ppm, bg0, bsum, comp, Dt, a.pc, a.apc, nullptr, lane, best,
+                       bestk, overflow);
+        if (overflow) {  // (.fs:117): this chain's error words, the chain ends alone
+            if (lane == 0) {
+                atomicCAS(a.err_code, 0, 3);
+                atomicMin(a.err_index, (unsigned long long)(a.global_offset + n));
+            }
+            continue;
+        }
+        if (lane == 0) {
+            const double sc = log(best) / kLn2;
+            if (sc > a.score_out[n]) {
+                a.score_out[n] = sc;
+                if (bestk != a.pos_out[n]) atomicAdd(&b.moved[r], 1);
+                a.pos_out[n] = bestk;
+            }
+        }
+    }
+}
+
+hipError_t gs_site_batch_ctl_launch(int32_t n_chains, int32_t pass, int32_t stage,
+                                    int32_t max_passes, int32_t *run, int32_t *moved,
+                                    const int32_t *err, int32_t *passes, int32_t *out,
+                                    hipStream_t s) {
+    if (n_chains <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gs_site_batch_ctl_kernel, dim3((n_chains + 255) / 256), dim3(256), 0, s,
+                       n_chains, pass, stage, max_passes, run, moved, err, passes, out);
+    return hipGetLastError();
+}
+
+// One shifted pass of every running chain: the start vectors and their aggregates, then
+// the scans with the accept.  a as for gs_site_batch_scan_kernel (mode 2, the D table in
+// LDS, lds_bytes its carve); agg_blocks / scan_blocks workgroups per chain.
+hipError_t gs_site_batch_pass_launch(const StartsArgs &a, size_t lds_bytes, int32_t n_chains,
+                                     int32_t dir, int32_t E, const int32_t *comp,
+                                     const int32_t *run, int32_t *moved, int32_t *shifted,
+                                     int agg_blocks, int scan_blocks, hipStream_t s) {
+    if (n_chains <= 0 || a.n_local <= 0) return hipSuccess;
+    if (a.dt_global || agg_blocks < 1 || scan_blocks < 1 ||
+        (int64_t)n_chains * (agg_blocks > scan_blocks ? agg_blocks : scan_blocks) > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    SiteBatchArgs b{};
+    b.run = run;
+    b.moved = moved;
+    b.comp = comp;
+    b.acc_pos = a.pos_out;
+    b.shifted = shifted;
+    b.agg = const_cast<int64_t *>(a.agg);
+    b.E = E;
+    b.dir = dir;
+    b.blocks = agg_blocks;
+    hipLaunchKernelGGL(gs_site_batch_agg_kernel, dim3(n_chains * agg_blocks), dim3(256),
+                       (size_t)a.A * (8 + 4 * a.W), s, a, b);
+    b.blocks = scan_blocks;
+    hipLaunchKernelGGL(gs_site_batch_scan_kernel, dim3(n_chains * scan_blocks), dim3(64), lds_bytes,
+                       s, a, b);
+    return hipGetLastError();
+}
+
 hipError_t gs_starts_launch(const StartsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     if (a.dt_global)
         hipLaunchKernelGGL(gs_starts_kernel<true>, dim3(grid), dim3(64), lds_bytes, s, a);

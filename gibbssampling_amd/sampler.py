@@ -345,6 +345,22 @@ def _batched_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
     return run
 
 
+def _batched_site_runs(ctx, count: int, motifLength, pseudoCount, base: int,
+                       init_mode: int) -> Callable[[int], list]:
+    """Runs r = 0 … count - 1 of doSiteSampling (seed base + r) by one batch call, as a
+    run(r) lookup for _replay_repetitions.  A run that raised raises when the loop asks
+    for it, as the sequential loop would."""
+    pos, score, _, status = ctx.site_sampling_batch(
+        motifLength, pseudoCount, [base + r for r in range(count)], init_mode, UNBOUNDED)
+
+    def run(r: int) -> list:
+        if status[r] != _native.GS_OK:
+            raise _native._ERRORS.get(int(status[r]), _native.DeviceError)(
+                int(status[r]), f"run {r} of the batch failed")
+        return _pairs(score[r], pos[r])
+    return run
+
+
 def _best_of_repetitions(numberOfRepetitions: int, run: Callable[[int], list], ic: Callable,
                          initial_best: list) -> list:
     """The repetition loop shared by getMotifsWithBestInformationContent(s)
@@ -428,10 +444,19 @@ class SiteSampler:
     def getMotifsWithBestInformationContent(numberOfRepetitions: int, motifLength: int,
                                             pseudoCount: float, alphabet, sources,
                                             seed: int | None = None, init_mode: int = 0,
-                                            device: int = 0):
+                                            device: int = 0, batch: bool = False):
         """Repeated doSiteSampling keeping the run of largest Σ score (.fs:615-640);
-        run r uses seed + r."""
+        run r uses seed + r.  batch=True computes every run r = 0 … numberOfRepetitions
+        in one Context.site_sampling_batch call and replays the same loop over them: the
+        same result, all runs paid for even when the loop stops early."""
         base = _seed(seed)
+        if batch:
+            ctx = _bind(alphabet, sources, device)
+            return _replay_repetitions(
+                numberOfRepetitions,
+                _batched_site_runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength,
+                                   pseudoCount, base, init_mode),
+                lambda xs: sum(s for s, _ in xs), [(0.0, 0)])
         return _best_of_repetitions(
             numberOfRepetitions,
             lambda r: SiteSampler.doSiteSampling(motifLength, pseudoCount, alphabet, sources,

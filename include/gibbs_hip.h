@@ -256,6 +256,25 @@ int gs_site_refine(gs_ctx *ctx, int32_t W, double pseudo_count, int32_t shift,
 int gs_site_sampling(gs_ctx *ctx, int32_t W, double pseudo_count, uint64_t seed,
                      int32_t init_mode, int32_t max_passes, int32_t *pos_out,
                      double *score_out, int32_t *passes_out);
+/* R independent doSiteSampling runs (.fs:697-701): chain r is exactly
+ * gs_site_sampling(ctx, W, pc, seeds[r], init_mode, max_passes, ...).
+ * pos_out / score_out: [n_chains][n_local] row-major; passes_out: [n_chains][3],
+ * status_out: [n_chains] (both nullable).  Returns the status of the lowest-index failing
+ * chain (gs_error_index: its sequence), GS_OK if none; the other chains' rows are still
+ * valid.  The chains' starts run back to back on the context's stream, their Gauss–Seidel
+ * passes as one launch of n_chains workgroups, their shifted passes together with one
+ * synchronisation per pass for all chains.  n_chains == 0 does nothing.
+ * GS_E_UNSUPPORTED: sharded sequences or a communicator, a fixed PCV or PPM, chain slabs
+ * beyond 4 GiB, or sequences too long for the star site engine's or the scan's LDS carve
+ * (loop gs_site_sampling).  The context holds no snapshot afterwards. */
+int gs_site_sampling_batch(gs_ctx *ctx, int32_t W, double pseudo_count, const uint64_t *seeds,
+                           int32_t n_chains, int32_t init_mode, int32_t max_passes,
+                           int32_t *pos_out, double *score_out,
+                           int32_t *passes_out /* [n_chains][3], nullable */,
+                           int32_t *status_out /* [n_chains], nullable */);
+/* Device times of the last gs_site_sampling_batch, ms: out[0] the chains' starts, out[1]
+ * the batched Gauss–Seidel launch, out[2] the shifted passes (both directions). */
+int gs_site_batch_last_ms(const gs_ctx *ctx, double out[3]);
 
 /* --- counter RNG (identical on host, device and in the oracle) -------- */
 double gs_uniform(uint64_t seed, uint64_t stream, uint64_t index);
