@@ -47,7 +47,7 @@ TUNING_ALIASES = {
     "GS_GREEDY_EXIT_CHUNK": "greedy_exit_chunk", "GS_GREEDY_EXIT_RATIO": "greedy_exit_ratio",
     "GS_GREEDY_WAVES": "greedy_waves", "GS_MULTI_GREEDY_THREADS": "multi_greedy_threads",
     "GS_MULTI_SPEC_SLOTS": "multi_spec_slots", "GS_GREEDY_SWITCH": "greedy_switch",
-    "GS_SITE_SWITCH": "site_switch",
+    "GS_SITE_SWITCH": "site_switch", "GS_MULTI_BATCH_FILL": "multi_batch_fill",
 }
 
 
@@ -152,6 +152,10 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
                                             P(i32)]),
         "gs_motif_sampling_multi": (C.c_int, [vp, i32, i32, f64, f64, u64, i32, i32, i32, vp, vp,
                                               vp, P(i32)]),
+        "gs_motif_sampling_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, vp, i32, i32, i32, i32,
+                                                    vp, vp, vp, vp, vp]),
+        "gs_multi_batch_last_ms": (C.c_int, [vp, vp]),
+        "gs_multi_batch_last_info": (C.c_int, [vp, vp]),
         "gs_set_fixed_pcv": (C.c_int, [vp, vp]),
         "gs_set_fixed_ppm": (C.c_int, [vp, vp, i32]),
         "gs_site_scan": (C.c_int, [vp, i32, f64, vp, vp, vp]),
@@ -426,6 +430,47 @@ class Context:
                                                      _ptr(co), _ptr(po), _ptr(pw),
                                                      C.byref(passes)))
         return co, po, pw, passes.value
+
+    def motif_sampling_multi_batch(self, motif_amount: int, W: int, pc: float, cutoff: float,
+                                   seeds, init_mode: int = 0, max_passes: int = 1000,
+                                   cap: int | None = None):
+        """R independent doMotifSampling runs with any motifAmount in one call, row r
+        exactly motif_sampling_multi(motif_amount, W, pc, cutoff, seeds[r], ...): sweep 0
+        over all (chain, target) pairs at once, the chains' greedy passes side by side ->
+        (cnt[R, N], pos[R, N, cap], pwms[R, N], passes[R], status[R]).  A chain that
+        raises (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows valid; errors
+        of the call itself raise."""
+        cap = int(cap or motif_amount)
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        cnt = np.zeros((R, self.n_local), np.int32)
+        pos = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
+        pwms = np.zeros((R, self.n_local), np.float64)
+        passes = np.zeros(R, np.int32)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_motif_sampling_multi_batch(
+            self.h, int(motif_amount), int(W), float(pc), float(cutoff), _ptr(seeds), R,
+            int(init_mode), int(max_passes), cap, _ptr(cnt), _ptr(pos), _ptr(pwms), _ptr(passes),
+            _ptr(status))
+        if st != GS_OK and not status.any():
+            self._check(st)
+        return cnt, pos, pwms, passes, status
+
+    def multi_batch_last_ms(self):
+        """Device milliseconds of the last motif_sampling_multi_batch: (starts, sweep,
+        greedy passes)."""
+        out = np.zeros(3, np.float64)
+        self._check(self.lib.gs_multi_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def multi_batch_last_info(self) -> dict:
+        """Rounds of the last motif_sampling_multi_batch: sweep rounds after the first
+        (arena growth), greedy restart rounds, chains restarted in all, speculative slots
+        per chain of the first greedy round."""
+        out = np.zeros(4, np.int32)
+        self._check(self.lib.gs_multi_batch_last_info(self.h, _ptr(out)))
+        return dict(zip(("sweep_rounds", "restart_rounds", "chains_restarted", "slots"),
+                        (int(v) for v in out)))
 
     def set_fixed_pcv(self, pcv49) -> None:
         """The caller's ProbabilityCompositeVector (49 slots) for the ByPCV / WithBPV

@@ -47,6 +47,7 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(greedy_waves, v >= 1 && v <= 8),
     GS_TUNING_FIELD(multi_greedy_threads, v >= 64 && v <= 1024 && (int)v % 64 == 0),
     GS_TUNING_FIELD(multi_spec_slots, v >= 1 && v <= 4096),
+    GS_TUNING_FIELD(multi_batch_fill, v >= 1 && v <= 4096),
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(site_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(ftab_mode, v == 0 || v == 1 || v == 2),
@@ -598,6 +599,353 @@ static int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, in
                     std::string(device_error_message(herr[(size_t)first])) + " (chain " +
                         std::to_string(first) + ")",
                     (int64_t)hidx[(size_t)first]);
+    return GS_OK;
+}
+
+namespace {
+// Device slabs of one list-path batch call (row r = chain r), freed on scope exit.
+struct MultiBatchBufs {
+    int32_t *cnt[3] = {nullptr, nullptr, nullptr};  // starts as lists, sweep output, live
+    int32_t *pos[3] = {nullptr, nullptr, nullptr};
+    double *pwms[2] = {nullptr, nullptr};           // sweep output, live
+    int64_t *agg[2] = {nullptr, nullptr};           // of the starts, live
+    unsigned long long *err = nullptr;
+    uint64_t *seeds = nullptr;
+    SpecCtl *ctl = nullptr;
+    SpecRes *res = nullptr;
+    int32_t *ovf = nullptr, *pairs = nullptr, *chains = nullptr, *starts = nullptr, *cpart = nullptr;
+    ~MultiBatchBufs() {
+        for (auto &q : cnt) dfree(q);
+        for (auto &q : pos) dfree(q);
+        for (auto &q : pwms) dfree(q);
+        for (auto &q : agg) dfree(q);
+        dfree(err);
+        dfree(seeds);
+        dfree(ctl);
+        dfree(res);
+        dfree(ovf);
+        dfree(pairs);
+        dfree(chains);
+        dfree(starts);
+        dfree(cpart);
+    }
+};
+
+// Speculative slots per chain of the list batch's greedy: the GPU is
+// filled by chains first, so the width falls with R from multi_batch_fill (2) scoring
+// workgroups per CU in all, about what is resident at once; never more than the single
+// chain's width, and the arenas stay under kArenaBudget.
+int32_t multi_batch_slots(const gs_ctx *c, int64_t chains, int64_t slot_bytes) {
+    int64_t s = std::min<int64_t>(c->n_local, c->tune.multi_spec_slots);
+    s = std::min<int64_t>(s, ((int64_t)c->tune.multi_batch_fill * c->n_cu + chains - 1) / chains);
+    s = std::min<int64_t>(s, kArenaBudget / (chains * slot_bytes));
+    return (int32_t)std::max<int64_t>(1, s);
+}
+}  // namespace
+
+// R independent doMotifSampling runs with Positions lists (.fs:1034-1038, any
+// motifAmount), DESIGN.md §9.12.  Stage 1, chain after chain on the context's
+// single-chain state and stream, no host wait in between: starts (seed r) as the lists
+// of slab r.  Stage 2: the aggregates of every chain's starts and sweep 0 over the
+// (chain, target) pairs, one host wait per arena round for all chains.  Stage 3: the
+// greedy passes, speculative steps of two launches for all chains, one host wait per
+// kSpecBatch steps; chains whose arena overflowed start again from the kept sweep output
+// with a larger one.  One download.  The caller validated the arguments.
+static int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff,
+                       const uint64_t *seeds, int32_t R, int32_t mode, int32_t max_passes,
+                       int32_t cap, int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
+                       int32_t *passes_out, int32_t *status_out) {
+    int rc;
+    const int64_t n = c->n_local;
+    for (int i = 0; i < 3; ++i) c->multi_batch_ms[i] = 0.0;
+    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = 0;
+    if (n == 0) {
+        for (int32_t r = 0; r < R; ++r) {
+            if (passes_out) passes_out[r] = 0;
+            if (status_out) status_out[r] = GS_OK;
+        }
+        return GS_OK;
+    }
+    MultiArgs a{};
+    const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, true);
+    if ((rc = multi_lds_check(c, lds))) return rc;
+    if ((rc = ensure_state(c, W))) return rc;
+    const int32_t cells = c->A * W + c->A;
+    const int64_t sweep_arena = std::max<int64_t>(2048, 4 * (int64_t)a.kmax);
+    const int64_t greedy_arena = std::max<int64_t>(4096, 8 * (int64_t)a.kmax);
+    auto slot_bytes = [&](int64_t arena) { return (2 * (int64_t)a.kmax + 3 * arena) * 8; };
+    const int64_t sweep_grid0 = std::max<int64_t>(
+        1, std::min<int64_t>(std::min<int64_t>((int64_t)R * n, (int64_t)c->n_cu * 8),
+                             kArenaBudget / slot_bytes(sweep_arena)));
+    if ((int64_t)R * slot_bytes(greedy_arena) > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_multi_batch: one arena per chain takes more than a batch "
+                    "may hold: split the seeds over several calls");
+    const int32_t slots0 = multi_batch_slots(c, R, slot_bytes(greedy_arena));
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    // per chain: three list slabs, two PWMS slabs, two aggregate rows, error word, seed,
+    // control block, chain index, speculation results; per pair: overflow and rescoring
+    // lists (and the shared draws); the first rounds' arenas
+    const int64_t bytes =
+        (int64_t)R * (n * (3 * (4 + 4 * (int64_t)cap) + 16 + 8 + (mode == 1 ? 4 : 0)) +
+                      (int64_t)cells * 16 + 8 + 8 + (int64_t)sizeof(SpecCtl) + 4 +
+                      (int64_t)slots0 * (int64_t)sizeof(SpecRes)) +
+        cpart_bytes +
+        std::max(sweep_grid0 * slot_bytes(sweep_arena), (int64_t)R * slots0 * slot_bytes(greedy_arena));
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_multi_batch: the chains' slabs take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a batch may hold: split the seeds over several calls");
+    MultiBatchBufs b;
+    const int64_t rows = (int64_t)R * n;
+    for (auto &q : b.cnt) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 4));
+    for (auto &q : b.pos) HIP_TRY(c, hipMalloc(&q, (size_t)(rows * cap) * 4));
+    for (auto &q : b.pwms) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 8));
+    for (auto &q : b.agg) HIP_TRY(c, hipMalloc(&q, (size_t)R * cells * 8));
+    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 8));
+    HIP_TRY(c, hipMalloc(&b.seeds, (size_t)R * 8));
+    HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * sizeof(SpecCtl)));
+    HIP_TRY(c, hipMalloc(&b.res, (size_t)R * slots0 * sizeof(SpecRes)));
+    HIP_TRY(c, hipMalloc(&b.ovf, (size_t)(rows + 1) * 4));
+    HIP_TRY(c, hipMalloc(&b.pairs, (size_t)rows * 4));
+    HIP_TRY(c, hipMalloc(&b.chains, (size_t)R * 4));
+    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
+    if (mode == 0) {
+        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
+    } else {
+        HIP_TRY(c, hipMalloc(&b.starts, (size_t)rows * 4));
+        hs.resize((size_t)rows);
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = 0; i < n; ++i)
+                hs[(size_t)(r * n + i)] =
+                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
+                                c->h_len[i] - W + 1);
+        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
+                                  c->stream));
+    }
+    std::vector<int32_t> live((size_t)R);  // the chains of a greedy round
+    for (int32_t r = 0; r < R; ++r) live[(size_t)r] = r;
+    HIP_TRY(c, hipMemcpyAsync(b.seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(b.chains, live.data(), (size_t)R * 4, hipMemcpyHostToDevice,
+                              c->stream));
+    MultiBatchArgs ba{};
+    ba.n_chains = R;
+    ba.slots = slots0;
+    ba.cells = cells;
+    ba.chains = b.chains;
+    ba.seeds = b.seeds;
+    ba.err = b.err;
+    ba.ctl = b.ctl;
+    ba.res = b.res;
+    ba.ovf_count = b.ovf;
+    ba.ovf_list = b.ovf + 1;
+    a.u = nullptr;
+    a.stream = stream_sweep(0);
+    a.max_passes = max_passes;
+    a.targets = nullptr;
+    a.n_targets = 0;
+    const int agg_blocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
+    std::vector<SpecCtl> hctl((size_t)R);
+    std::vector<unsigned long long> herr((size_t)R);
+    int32_t info[4] = {0, 0, 0, slots0};
+    // chains whose categories pass kArenaMax: their word takes kMultiErrUnsupported
+    auto give_up = [&](const std::vector<int32_t> &chains) -> int {
+        for (int32_t r : chains) {
+            const unsigned long long w = ((unsigned long long)c->global_offset << 4) |
+                                         (unsigned long long)kMultiErrUnsupported;
+            HIP_TRY(c, hipMemcpyAsync(b.err + r, &w, 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        return GS_OK;
+    };
+    hipEvent_t ev[4] = {get_event(c), get_event(c), get_event(c), get_event(c)};
+    auto recycle = [&]() {
+        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
+    };
+    rc = [&]() -> int {
+        int rc2;
+        // ---- stage 1: every chain's starts, as lists ----
+        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+        for (int32_t r = 0; r < R; ++r) {
+            // (as motif_batch) the start vector the aggregate pass reads
+            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
+                return rc2;
+            // a target that raises (.fs:117) writes no start: every entry stays a valid one
+            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
+            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
+            HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, cap, b.cnt[0] + r * n,
+                                                   b.pos[0] + r * n * cap, c->d_err_code,
+                                                   c->d_err_index, b.err + r, b.ctl + r,
+                                                   c->stream));
+        }
+        // the context's own error words end clear, whatever the last chain's were
+        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+        // ---- stage 2: aggregates of the starts, sweep 0 of every chain ----
+        a.cnt_in = b.cnt[0];
+        a.pos_in = b.pos[0];
+        a.cnt_out = b.cnt[1];
+        a.pos_out = b.pos[1];
+        a.pwms_out = b.pwms[0];
+        a.agg = b.agg[0];
+        a.agg_rw = b.agg[1];
+        HIP_TRY(c, hipMemsetAsync(b.agg[0], 0, (size_t)R * cells * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(b.pos[1], 0xff, (size_t)(rows * cap) * 4, c->stream));
+        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[0], agg_blocks, c->stream));
+        ba.pairs = nullptr;
+        ba.n_pairs = rows;
+        for (int64_t arena = sweep_arena;;) {
+            int64_t grid = std::min<int64_t>(ba.n_pairs, (int64_t)c->n_cu * 8);
+            grid = std::max<int64_t>(1, std::min<int64_t>(grid, kArenaBudget / slot_bytes(arena)));
+            if ((rc2 = multi_scratch(c, a, grid, arena))) return rc2;
+            HIP_TRY(c, hipMemsetAsync(b.ovf, 0, 4, c->stream));
+            HIP_TRY(c, gs_multi_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
+            int32_t novf = 0;
+            HIP_TRY(c, hipMemcpyAsync(&novf, b.ovf, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (novf == 0) break;
+            if (arena * 16 > kArenaMax) {
+                std::vector<int32_t> pairs((size_t)novf), chains;
+                HIP_TRY(c, hipMemcpy(pairs.data(), b.ovf + 1, (size_t)novf * 4,
+                                     hipMemcpyDeviceToHost));
+                for (int32_t p : pairs) chains.push_back((int32_t)(p / n));
+                std::sort(chains.begin(), chains.end());
+                chains.erase(std::unique(chains.begin(), chains.end()), chains.end());
+                if ((rc2 = give_up(chains))) return rc2;
+                break;
+            }
+            arena *= 16;
+            ++info[0];
+            HIP_TRY(c, hipMemcpyAsync(b.pairs, b.ovf + 1, (size_t)novf * 4,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            ba.pairs = b.pairs;
+            ba.n_pairs = novf;
+        }
+        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+        // ---- stage 3: greedy passes from the sweep's lists (kept for restarts) ----
+        HIP_TRY(c, hipMemcpyAsync(b.cnt[2], b.cnt[1], (size_t)rows * 4, hipMemcpyDeviceToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(b.pos[2], b.pos[1], (size_t)(rows * cap) * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(b.pwms[1], b.pwms[0], (size_t)rows * 8, hipMemcpyDeviceToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(b.agg[1], 0, (size_t)R * cells * 8, c->stream));
+        HIP_TRY(c, gs_multi_batch_ctl_launch(ba, R, c->stream));
+        a.cnt_in = a.cnt_out = b.cnt[2];
+        a.pos_in = a.pos_out = b.pos[2];
+        a.pwms_out = b.pwms[1];
+        a.agg = b.agg[1];
+        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[1], agg_blocks, c->stream));
+        const int64_t step_limit = ((int64_t)n + 1) * max_passes + kSpecBatch;
+        std::vector<int32_t> next;
+        for (int64_t arena = greedy_arena;; arena *= 16) {
+            // the chains of this arena size, as many at a time as the arena budget holds
+            const int64_t group = std::max<int64_t>(1, kArenaBudget / slot_bytes(arena));
+            next.clear();
+            for (size_t g0 = 0; g0 < live.size(); g0 += (size_t)group) {
+                const int32_t ng = (int32_t)std::min<size_t>((size_t)group, live.size() - g0);
+                ba.n_chains = ng;
+                ba.slots = std::min(slots0, multi_batch_slots(c, ng, slot_bytes(arena)));
+                if (arena != greedy_arena || ng != R) {
+                    HIP_TRY(c, hipMemcpyAsync(b.chains, live.data() + g0, (size_t)ng * 4,
+                                              hipMemcpyHostToDevice, c->stream));
+                    if (arena != greedy_arena) {
+                        HIP_TRY(c, gs_multi_batch_restart_launch(ba, (int32_t)n, cap, b.cnt[1],
+                                                                 b.pos[1], b.pwms[0], b.cnt[2],
+                                                                 b.pos[2], b.pwms[1], b.agg[1],
+                                                                 c->stream));
+                        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[1], agg_blocks,
+                                                             c->stream));
+                    }
+                }
+                if ((rc2 = multi_scratch(c, a, (int64_t)ng * ba.slots, arena))) return rc2;
+                bool running = true;
+                for (int64_t steps = 0; running && steps <= step_limit; steps += kSpecBatch) {
+                    HIP_TRY(c, gs_multi_batch_spec_launch(a, ba, c->tune.multi_greedy_threads,
+                                                          (size_t)lds, kSpecBatch, c->stream));
+                    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b.ctl, (size_t)R * sizeof(SpecCtl),
+                                              hipMemcpyDeviceToHost, c->stream));
+                    HIP_TRY(c, hipStreamSynchronize(c->stream));
+                    running = false;
+                    for (int32_t i = 0; i < ng; ++i)
+                        running |= !hctl[(size_t)live[g0 + (size_t)i]].done;
+                }
+                if (running) return fail(c, GS_E_HIP, "list-path greedy made no progress");
+                HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost));
+                for (int32_t i = 0; i < ng; ++i) {
+                    const int32_t r = live[g0 + (size_t)i];
+                    if (herr[(size_t)r] != ~0ull && (int)(herr[(size_t)r] & 15ull) == kMultiErrArena)
+                        next.push_back(r);
+                }
+            }
+            if (next.empty()) break;
+            if (arena * 16 > kArenaMax) {
+                if ((rc2 = give_up(next))) return rc2;
+                break;
+            }
+            ++info[1];
+            info[2] += (int32_t)next.size();
+            live = next;
+        }
+        HIP_TRY(c, hipEventRecord(ev[3], c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    // the context's single-chain buffers were the chains' scratch: no snapshot is left
+    c->have_state = false;
+    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+    c->note_pending = false;
+    c->ftab_agg = -1;
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
+        recycle();
+        return rc;
+    }
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+        c->multi_batch_ms[i] = (double)ms;
+    }
+    recycle();
+    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = info[i];
+    // ---- stage 4: one download ----
+    HIP_TRY(c, hipMemcpyAsync(cnt_out, b.cnt[2], (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pos_out, b.pos[2], (size_t)(rows * cap) * 4, hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pwms_out, b.pwms[1], (size_t)rows * 8, hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b.ctl, (size_t)R * sizeof(SpecCtl), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int first = -1, first_status = GS_OK;
+    for (int32_t r = 0; r < R; ++r) {
+        const unsigned long long e = herr[(size_t)r];
+        const int st = (int)(e & 15ull);
+        const int status = e == ~0ull                    ? GS_OK
+                           : st == 2                     ? GS_E_ROULETTE_OVERRUN
+                           : st == 3                     ? GS_E_OVERFLOW
+                           : st == kMultiErrUnsupported ? GS_E_UNSUPPORTED
+                                                         : GS_E_HIP;
+        if (passes_out) passes_out[r] = hctl[(size_t)r].pass;
+        if (status_out) status_out[r] = status;
+        if (status != GS_OK && first < 0) {
+            first = r;
+            first_status = status;
+        }
+    }
+    if (first >= 0)
+        return fail(c, first_status,
+                    std::string(first_status == GS_E_UNSUPPORTED
+                                    ? "a sequence has more than 2^28 motif combinations "
+                                      "(.fs:727-742)"
+                                    : device_error_message(first_status)) +
+                        " (chain " + std::to_string(first) + ")",
+                    (int64_t)(herr[(size_t)first] >> 4));
     return GS_OK;
 }
 
@@ -1469,6 +1817,47 @@ int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seed
 int gs_site_batch_last_ms(const gs_ctx *c, double out[3]) {
     if (!c || !out) return GS_E_ARG;
     for (int i = 0; i < 3; ++i) out[i] = c->site_batch_ms[i];
+    return GS_OK;
+}
+
+int gs_motif_sampling_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                  double cutoff, const uint64_t *seeds, int32_t n_chains,
+                                  int32_t init_mode, int32_t max_passes, int32_t cap,
+                                  int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
+                                  int32_t *passes_out, int32_t *status_out) {
+    if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
+        return GS_E_ARG;
+    if (motif_amount < 1 || motif_amount > kMultiMaxAmount || cap < motif_amount ||
+        cap > kMultiMaxAmount)
+        return fail(c, GS_E_ARG, "motifAmount / list capacity out of range");
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!cnt_out || !pos_out || !pwms_out))) return GS_E_ARG;
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_multi_batch: every chain walks all targets in order "
+                    "(.fs:885-929): it needs all sequences on one device and no communicator");
+    if (c->use_pcv || c->use_ppm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_multi_batch: the ByPCV / OfPPM twins are not batched "
+                    "(clear the fixed PCV / PPM, or loop gs_motif_sampling_multi)");
+    takeover_reset(c);
+    return multi_batch(c, motif_amount, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, cap,
+                       cnt_out, pos_out, pwms_out, passes_out, status_out);
+}
+
+int gs_multi_batch_last_ms(const gs_ctx *c, double out[3]) {
+    if (!c || !out) return GS_E_ARG;
+    for (int i = 0; i < 3; ++i) out[i] = c->multi_batch_ms[i];
+    return GS_OK;
+}
+
+int gs_multi_batch_last_info(const gs_ctx *c, int32_t out[4]) {
+    if (!c || !out) return GS_E_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = c->multi_batch_info[i];
     return GS_OK;
 }
 

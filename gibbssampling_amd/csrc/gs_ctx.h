@@ -50,6 +50,7 @@ struct gs_tuning {
     int32_t greedy_waves = 8;  // speculation width of the greedy kernel (targets scored per step)
     int32_t multi_greedy_threads = 512;  // list-path greedy: threads per workgroup (64 .. 1024, multiple of 64)
     int32_t multi_spec_slots = 256;  // list-path greedy: visits scored per speculative step
+    int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
     int32_t ftab_mode = 0;  // four-symbol sweep's workgroup tables: 0 built by every workgroup, 1 by a table kernel before the sweep, 2 handed over by the previous sweep's last workgroup (one GPU; else 1); 1 and 2 need the -DGS_FTAB build
     int32_t site_switch = 4;  // the same for the site sampler (cfg2: 4 / 16 / 2 -> 231 / 245 / 252 ms)
@@ -122,6 +123,40 @@ hipError_t gs_multi_agg_launch(const MultiArgs &a, int64_t *out, int n_cu, hipSt
 hipError_t gs_multi_sweep_launch(const MultiArgs &a, int grid, size_t lds, hipStream_t s);
 hipError_t gs_multi_spec_launch(const MultiArgs &a, int threads, size_t lds, int steps,
                                 hipStream_t s);
+// What gs_motif_sampling_multi_batch adds to MultiArgs (a second by-value kernel
+// argument, gs_multi.hip): R chains side by side, chain r on row r of every slab.  The
+// MultiArgs beside it names the slabs' bases (cnt/pos/pwms rows of n_local targets,
+// agg / agg_rw rows of `cells`); the kernels run the single-chain device functions on a
+// chain-offset copy of it.
+constexpr int kMultiErrUnsupported = 14;  // chain status: more than kArenaMax categories
+struct MultiBatchArgs {
+    int32_t n_chains;            // chains of this launch (entries of `chains`)
+    int32_t slots;               // speculative slots per chain (rows of res)
+    int32_t cells;               // A*W + A aggregate cells per chain
+    const int32_t *chains;       // [n_chains]: the chain of every launch index
+    const uint64_t *seeds;       // [R]
+    unsigned long long *err;     // [R]: packed (global index << 4) | status, atomicMin
+    SpecCtl *ctl;                // [R]; done also marks a chain that raised
+    SpecRes *res;                // [R][slots]
+    const int32_t *pairs;        // sweep: linear (chain * n_local + target) indices, or null: all
+    int64_t n_pairs;
+    int32_t *ovf_list, *ovf_count;   // sweep: pairs whose categories overflowed the arena
+};
+hipError_t gs_multi_batch_lists_launch(const int32_t *pos, int32_t n, int32_t cap, int32_t *cnt,
+                                       int32_t *lst, const int32_t *err_code,
+                                       const unsigned long long *err_index,
+                                       unsigned long long *err, SpecCtl *ctl, hipStream_t s);
+hipError_t gs_multi_batch_agg_launch(const MultiArgs &a, const MultiBatchArgs &b, int64_t *out,
+                                     int blocks_per_chain, hipStream_t s);
+hipError_t gs_multi_batch_sweep_launch(const MultiArgs &a, const MultiBatchArgs &b, int grid,
+                                       size_t lds, hipStream_t s);
+hipError_t gs_multi_batch_ctl_launch(const MultiBatchArgs &b, int32_t n_all, hipStream_t s);
+hipError_t gs_multi_batch_restart_launch(const MultiBatchArgs &b, int32_t n, int32_t cap,
+                                         const int32_t *cnt0, const int32_t *pos0,
+                                         const double *pw0, int32_t *cnt, int32_t *pos,
+                                         double *pw, int64_t *agg, hipStream_t s);
+hipError_t gs_multi_batch_spec_launch(const MultiArgs &a, const MultiBatchArgs &b, int threads,
+                                      size_t lds, int steps, hipStream_t s);
 hipError_t gs_single_lists_launch(const int32_t *pos, int32_t n, int32_t *cnt, int32_t *lst,
                                   int to_lists, hipStream_t s);
 hipError_t gs_count_diff_launch(const int32_t *a, const int32_t *b, int32_t n, int32_t *out,
@@ -234,6 +269,8 @@ struct gs_ctx {
     int32_t last_greedy_waves = 0;
     double batch_ms[2] = {0.0, 0.0};  // the last batch call: stage 1 (all chains), greedy launch
     double site_batch_ms[3] = {0.0, 0.0, 0.0};  // the last site batch: starts, Gauss–Seidel launch, shifted passes
+    double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
+    int32_t multi_batch_info[4] = {0, 0, 0, 0};  // ... sweep arena rounds, greedy restart rounds, chains restarted, slots
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG
     // draws of kGraphSweeps sweeps from a device sweep counter, d_u6) + kGraphSweeps x

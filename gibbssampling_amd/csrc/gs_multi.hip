@@ -48,6 +48,7 @@
 #include <algorithm>
 
 #include "gs_common.h"
+#include "gs_ctx.h"
 #include "gs_wave.h"
 
 using namespace gs;
@@ -464,6 +465,7 @@ struct GPick {
 
 // The greedy's head of the stable descending sort (.fs:917-920), every thread of
 // the workgroup.  Returns status 0 / kMultiErrArena.
+template <int kCopy = 0>
 __device__ int greedy_pick(const MultiArgs &a, const Slot &sl, int K, GPick &out, Best *red,
                            int *shared_i, double *ppar, int32_t *lpar) {
     const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
@@ -829,5 +831,362 @@ hipError_t gs_count_diff_launch(const int32_t *a, const int32_t *b, int32_t n, i
     if (n <= 0) return hipSuccess;
     const int grid = std::min((n + 255) / 256, 1024);
     hipLaunchKernelGGL(gs_count_diff_kernel, dim3(grid), dim3(256), 0, s, a, b, n, out);
+    return hipGetLastError();
+}
+
+// ---- R chains side by side (gs_motif_sampling_multi_batch) ----
+// Chain r lives on row r of every slab MultiArgs names; the kernels below are the
+// single-chain kernels' bodies on a chain-offset copy of it, indexed by blockIdx.x
+// alone.  No workgroup waits on another: the kernel boundary is the only
+// synchronisation, and a chain that is done (or raised) returns at once.
+namespace {
+
+__device__ __forceinline__ MultiArgs chain_args(const MultiArgs &a0, const MultiBatchArgs &b,
+                                                int r) {
+    MultiArgs a = a0;
+    const int64_t row = (int64_t)r * a0.n_local;
+    a.cnt_in = a0.cnt_in + row;
+    a.pos_in = a0.pos_in + row * a0.cap_in;
+    a.cnt_out = a0.cnt_out + row;
+    a.pos_out = a0.pos_out + row * a0.cap_out;
+    a.pwms_out = a0.pwms_out + row;
+    a.agg = a0.agg + (int64_t)r * b.cells;
+    a.agg_rw = a0.agg_rw + (int64_t)r * b.cells;
+    a.err = b.err + r;
+    a.seed = b.seeds[r];
+    a.spec_ctl = b.ctl + r;
+    a.spec_res = b.res + (int64_t)r * b.slots;
+    a.spec_slots = b.slots;
+    return a;
+}
+
+}  // namespace
+
+// A chain's starts (d_pos[1] of the single-chain state) as its input lists: cnt = 1,
+// pos[0] = start, the rest -1.  The two error words of its starts become the chain's
+// packed word; a chain that raised there (.fs:117) is done for every later kernel.
+extern "C" __global__ void __launch_bounds__(256)
+gs_multi_batch_lists_kernel(const int32_t *pos, int32_t n, int32_t cap, int32_t *cnt, int32_t *lst,
+                            const int32_t *err_code, const unsigned long long *err_index,
+                            unsigned long long *err, SpecCtl *ctl) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        cnt[i] = 1;
+        lst[(int64_t)i * cap] = pos[i];
+        for (int j = 1; j < cap; ++j) lst[(int64_t)i * cap + j] = -1;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int code = *err_code;
+        *err = code ? (*err_index << 4) | (unsigned long long)(code & 15) : ~0ull;
+        *ctl = SpecCtl{0, 0, 0, code != 0};
+    }
+}
+
+// gs_multi_agg_kernel per chain: gridDim.x / n_chains workgroups on every chain's lists
+// (a.cnt_in, a.pos_in), into row r of the zeroed `out`.
+extern "C" __global__ void __launch_bounds__(256)
+gs_multi_batch_agg_kernel(MultiArgs a, MultiBatchArgs b, int64_t *out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    unsigned long long *acc = (unsigned long long *)lds;
+    const int A = a.A, W = a.W, cells = A * W + A;
+    const int bpc = gridDim.x / b.n_chains;
+    const int c = blockIdx.x / bpc, blk = blockIdx.x - c * bpc;
+    const int r = b.chains[c];
+    if (b.ctl[r].done) return;
+    const int32_t *cnt_in = a.cnt_in + (int64_t)r * a.n_local;
+    const int32_t *pos_in = a.pos_in + (int64_t)r * a.n_local * a.cap_in;
+    for (int x = threadIdx.x; x < cells; x += blockDim.x) acc[x] = 0ull;
+    __syncthreads();
+    for (int n = blk * blockDim.x + threadIdx.x; n < a.n_local; n += bpc * blockDim.x) {
+        const uint8_t *s = a.seq + a.doff[n];
+        const int cnt = cnt_in[n];
+        for (int i = 0; i < cnt; ++i) {
+            const int p = pos_in[(int64_t)n * a.cap_in + i];
+            for (int x = 0; x < A; ++x)
+                atomicAdd(&acc[A * W + x], (unsigned long long)a.comp[(int64_t)n * (a.E + 1) + x]);
+            for (int j = 0; j < W; ++j) {
+                const int e = s[p + j];
+                if (e < A) {
+                    atomicAdd(&acc[e * W + j], 1ull);
+                    atomicAdd(&acc[A * W + e], ~0ull);  // -1
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < cells; x += blockDim.x)
+        if (acc[x]) atomicAdd((unsigned long long *)&out[(int64_t)r * cells + x], acc[x]);
+}
+
+// gs_multi_sweep_kernel over the linearised (chain, target) pairs: the uniform of pair
+// (r, n) is uniform(seeds[r], a.stream, global_offset + n); errors go into chain r's
+// own word, arena overflows into one list of pair indices.
+extern "C" __global__ void __launch_bounds__(64)
+gs_multi_batch_sweep_kernel(MultiArgs a0, MultiBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double *tab = (double *)(lds + a0.o_tab);
+    double *pcv = (double *)(lds + a0.o_pcv);
+    uint8_t *sseq = lds + a0.o_seq;
+    __shared__ int flag;
+    const int lane = threadIdx.x;
+    const Slot sl = slot_of(a0, blockIdx.x, lds);
+    const int AW = a0.A * a0.W;
+    for (int64_t i = blockIdx.x; i < b.n_pairs; i += gridDim.x) {
+        const int64_t pair = b.pairs ? (int64_t)b.pairs[i] : i;
+        const int r = (int)(pair / a0.n_local);
+        const int n = (int)(pair - (int64_t)r * a0.n_local);
+        if (b.ctl[r].done) continue;  // raised in its starts
+        const MultiArgs a = chain_args(a0, b, r);
+        const int64_t *C = a.agg, *T = a.agg + AW;
+        const int L = a.len[n];
+        const int K = L - a.W + 1;
+        const int64_t gidx = a.global_offset + n;
+        __syncthreads();
+        stage(a.seq + a.doff[n], L, sseq);
+        __syncthreads();
+        const int cnt = a.cnt_in[n];
+        const int32_t *pos = a.pos_in + (int64_t)n * a.cap_in;
+        const int st = prepare_target(a, n, L, sseq, cnt, pos, C, T, tab, pcv, sl, &flag);
+        if (st) {
+            if (lane == 0) raise_err(a, gidx, st);
+            continue;
+        }
+        int lo, hi;
+        const int total = build_levels(a, sl, K, a.M - 1, lane, &lo, &hi);
+        if (total < 0) {
+            if (lane == 0) b.ovf_list[atomicAdd(b.ovf_count, 1)] = (int32_t)pair;
+            continue;
+        }
+        const int plo = a.M == 1 ? -1 : lo, phi = a.M == 1 ? 0 : hi;
+        const double u = uniform(a.seed, a.stream, (uint64_t)gidx);
+        const RPick pk = roulette(a, sl, K, total, plo, phi, u, lane);
+        if (pk.c == -2) {
+            if (lane == 0) raise_err(a, gidx, 2);  // list index past the end (.fs:752)
+            continue;
+        }
+        if (lane == 0) {
+            int32_t *po = a.pos_out + (int64_t)n * a.cap_out;
+            if (pk.c == -1)
+                emit(sl, pk.j, pk.q, pk.w, a.cnt_out + n, po, a.pwms_out + n);
+            else
+                emit(sl, -1, pk.c < K ? -1 : pk.c - K, pk.c < K ? sl.G[pk.c] : sl.wgt[pk.c - K],
+                     a.cnt_out + n, po, a.pwms_out + n);
+        }
+    }
+}
+
+// The chains' control blocks before their greedy passes: a chain whose starts or sweep
+// raised is done from the start.
+extern "C" __global__ void __launch_bounds__(256)
+gs_multi_batch_ctl_kernel(MultiBatchArgs b, int32_t n_all) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_all) b.ctl[r] = SpecCtl{0, 0, 0, b.err[r] != ~0ull};
+}
+
+// Chains whose greedy overflowed its arena start again from the kept sweep output: one
+// workgroup per chain copies its rows, zeroes its live aggregates and clears its
+// control block and error word (gs_multi_batch_agg_kernel rebuilds the aggregates).
+extern "C" __global__ void __launch_bounds__(256)
+gs_multi_batch_restart_kernel(MultiBatchArgs b, int32_t n, int32_t cap, const int32_t *cnt0,
+                              const int32_t *pos0, const double *pw0, int32_t *cnt, int32_t *pos,
+                              double *pw, int64_t *agg) {
+    const int r = b.chains[blockIdx.x];
+    const int64_t row = (int64_t)r * n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        cnt[row + i] = cnt0[row + i];
+        pw[row + i] = pw0[row + i];
+    }
+    for (int64_t i = threadIdx.x; i < (int64_t)n * cap; i += blockDim.x)
+        pos[row * cap + i] = pos0[row * cap + i];
+    for (int x = threadIdx.x; x < b.cells; x += blockDim.x) agg[(int64_t)r * b.cells + x] = 0;
+    if (threadIdx.x == 0) {
+        b.ctl[r] = SpecCtl{0, 0, 0, 0};
+        b.err[r] = ~0ull;
+    }
+}
+
+// gs_multi_spec_score_kernel for n_chains x slots workgroups: workgroup (c, w) scores
+// visit base + w of chain chains[c] against that chain's live aggregates, in the arena
+// slot of its own linear index.
+extern "C" __global__ void __launch_bounds__(1024)
+gs_multi_batch_score_kernel(MultiArgs a0, MultiBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double *tab = (double *)(lds + a0.o_tab);
+    double *pcv = (double *)(lds + a0.o_pcv);
+    uint8_t *sseq = lds + a0.o_seq;
+    int64_t *agg = (int64_t *)(lds + a0.o_agg);
+    __shared__ int flag;
+    __shared__ int shared_i[4];
+    __shared__ Best red[kMaxWaves];
+    __shared__ double ppar[kParentBlock];
+    __shared__ int32_t lpar[kParentBlock];
+    const int c = (int)blockIdx.x / b.slots, w = (int)blockIdx.x - c * b.slots;
+    const int r = b.chains[c];
+    const SpecCtl ctl = b.ctl[r];
+    const int tid = threadIdx.x;
+    const int n = ctl.base + w;
+    if (ctl.done || n >= a0.n_local) return;
+    const MultiArgs a = chain_args(a0, b, r);
+    const int A = a.A, W = a.W, AW = A * W;
+    const Slot sl = slot_of(a, blockIdx.x, lds);
+    for (int x = tid; x < AW + A; x += blockDim.x) agg[x] = a.agg_rw[x];
+    const int L = a.len[n];
+    const int K = L - W + 1;
+    stage(a.seq + a.doff[n], L, sseq);
+    __syncthreads();
+    const int32_t *lst = a.pos_out + (int64_t)n * a.cap_out;
+    const int cnt = a.cnt_out[n];
+    int st = prepare_target(a, n, L, sseq, cnt, lst, agg, agg + AW, tab, pcv, sl, &flag);
+    GPick pk{};
+    if (!st) st = greedy_pick<1>(a, sl, K, pk, red, shared_i, ppar, lpar);
+    if (tid == 0) {
+        SpecRes &res = a.spec_res[w];
+        res.status = st;
+        if (!st) {
+            emit(sl, pk.level == 2 ? pk.j : -1, pk.level == 0 ? -1 : pk.idx, pk.pwms, &res.cnt,
+                 res.pos, &res.pw);
+            res.accept = res.pw > a.pwms_out[n];  // tmp.PWMS > acc.[n].PWMS (.fs:923)
+            bool same = res.cnt == cnt;
+            for (int i = 0; same && i < cnt; ++i) same = res.pos[i] == lst[i];
+            res.moved = res.accept && !same;
+        }
+    }
+}
+
+// gs_multi_spec_commit_kernel, one workgroup per chain: commits into the chain's own
+// lists and aggregates, raises into its own word and sets only its own `done`.
+extern "C" __global__ void __launch_bounds__(64)
+gs_multi_batch_commit_kernel(MultiArgs a0, MultiBatchArgs b) {
+    const int r = b.chains[blockIdx.x];
+    SpecCtl *ctl = b.ctl + r;
+    const SpecCtl c0 = *ctl;
+    if (c0.done) return;
+    const MultiArgs a = chain_args(a0, b, r);
+    const int lane = threadIdx.x;
+    const int A = a.A, W = a.W, AW = A * W;
+    const int base = c0.base, nres = min(a.spec_slots, a.n_local - base);
+    // the first visit that moves (or failed): everything before it stands
+    int first = nres;
+    for (int w0 = 0; w0 < nres; w0 += 64) {
+        const int w = w0 + lane;
+        const bool f = w < nres && (a.spec_res[w].moved || a.spec_res[w].status);
+        const unsigned long long m = __ballot(f);
+        if (m) {
+            first = w0 + __ffsll((long long)m) - 1;
+            break;
+        }
+    }
+    for (int w = lane; w < first; w += 64)
+        if (a.spec_res[w].accept) a.pwms_out[base + w] = a.spec_res[w].pw;  // same list
+    int nbase = base + nres, changed = c0.changed;
+    if (first < nres) {
+        const SpecRes &res = a.spec_res[first];
+        const int n = base + first;
+        if (res.status) {  // raised (or overflowed its arena): this chain stops here
+            if (lane == 0) {
+                raise_err(a, a.global_offset + n, res.status);
+                ctl->done = 1;
+            }
+            return;
+        }
+        // move the target's contribution from its old list to the new one
+        int32_t *lst = a.pos_out + (int64_t)n * a.cap_out;
+        const int cnt = a.cnt_out[n];
+        const uint8_t *s = a.seq + a.doff[n];
+        unsigned long long *C = (unsigned long long *)a.agg_rw, *T = C + AW;
+        if (lane < W) {
+            for (int i = 0; i < cnt; ++i) {
+                const int e = s[lst[i] + lane];
+                if (e < A) {
+                    atomicAdd(&C[e * W + lane], ~0ull);
+                    atomicAdd(&T[e], 1ull);
+                }
+            }
+            for (int i = 0; i < res.cnt; ++i) {
+                const int e = s[res.pos[i] + lane];
+                if (e < A) {
+                    atomicAdd(&C[e * W + lane], 1ull);
+                    atomicAdd(&T[e], ~0ull);
+                }
+            }
+        }
+        if (lane < A) {
+            const int64_t ce = a.comp[(int64_t)n * (a.E + 1) + lane];
+            atomicAdd(&T[lane], (unsigned long long)(ce * (int64_t)(res.cnt - cnt)));
+        }
+        __syncthreads();
+        if (lane < res.cnt) lst[lane] = res.pos[lane];
+        if (lane == 0) {
+            a.cnt_out[n] = res.cnt;
+            a.pwms_out[n] = res.pw;
+        }
+        changed = 1;
+        nbase = n + 1;
+    }
+    if (lane == 0) {
+        SpecCtl cn = c0;
+        cn.base = nbase;
+        cn.changed = changed;
+        if (nbase >= a.n_local) {  // a pass ends (.fs:887-889)
+            ++cn.pass;
+            if (!cn.changed || cn.pass >= a.max_passes)
+                cn.done = 1;
+            else {
+                cn.base = 0;
+                cn.changed = 0;
+            }
+        }
+        *ctl = cn;
+    }
+}
+
+hipError_t gs_multi_batch_lists_launch(const int32_t *pos, int32_t n, int32_t cap, int32_t *cnt,
+                                       int32_t *lst, const int32_t *err_code,
+                                       const unsigned long long *err_index,
+                                       unsigned long long *err, SpecCtl *ctl, hipStream_t s) {
+    const int grid = std::max(1, std::min((n + 255) / 256, 1024));
+    hipLaunchKernelGGL(gs_multi_batch_lists_kernel, dim3(grid), dim3(256), 0, s, pos, n, cap, cnt,
+                       lst, err_code, err_index, err, ctl);
+    return hipGetLastError();
+}
+
+hipError_t gs_multi_batch_agg_launch(const MultiArgs &a, const MultiBatchArgs &b, int64_t *out,
+                                     int blocks_per_chain, hipStream_t s) {
+    if (a.n_local <= 0 || b.n_chains <= 0) return hipSuccess;
+    const size_t lds = 8 * (size_t)(a.A * a.W + a.A);
+    hipLaunchKernelGGL(gs_multi_batch_agg_kernel, dim3(b.n_chains * blocks_per_chain), dim3(256),
+                       lds, s, a, b, out);
+    return hipGetLastError();
+}
+
+hipError_t gs_multi_batch_sweep_launch(const MultiArgs &a, const MultiBatchArgs &b, int grid,
+                                       size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(gs_multi_batch_sweep_kernel, dim3(grid), dim3(64), lds, s, a, b);
+    return hipGetLastError();
+}
+
+hipError_t gs_multi_batch_ctl_launch(const MultiBatchArgs &b, int32_t n_all, hipStream_t s) {
+    hipLaunchKernelGGL(gs_multi_batch_ctl_kernel, dim3((n_all + 255) / 256), dim3(256), 0, s, b,
+                       n_all);
+    return hipGetLastError();
+}
+
+hipError_t gs_multi_batch_restart_launch(const MultiBatchArgs &b, int32_t n, int32_t cap,
+                                         const int32_t *cnt0, const int32_t *pos0,
+                                         const double *pw0, int32_t *cnt, int32_t *pos,
+                                         double *pw, int64_t *agg, hipStream_t s) {
+    hipLaunchKernelGGL(gs_multi_batch_restart_kernel, dim3(b.n_chains), dim3(256), 0, s, b, n, cap,
+                       cnt0, pos0, pw0, cnt, pos, pw, agg);
+    return hipGetLastError();
+}
+
+// `steps` speculative steps of every chain of b.chains (score + commit each), enqueued
+// without host syncs.
+hipError_t gs_multi_batch_spec_launch(const MultiArgs &a, const MultiBatchArgs &b, int threads,
+                                      size_t lds, int steps, hipStream_t s) {
+    for (int i = 0; i < steps; ++i) {
+        hipLaunchKernelGGL(gs_multi_batch_score_kernel, dim3(b.n_chains * b.slots), dim3(threads),
+                           lds, s, a, b);
+        hipLaunchKernelGGL(gs_multi_batch_commit_kernel, dim3(b.n_chains), dim3(64), 0, s, a, b);
+    }
     return hipGetLastError();
 }

@@ -6,6 +6,7 @@ reference raises (see _native.py for the mapping).
 """
 from __future__ import annotations
 
+import functools
 import os
 from dataclasses import dataclass
 from typing import Callable, Sequence
@@ -175,7 +176,8 @@ class MotifSampler:
         run r uses seed + r.  batch=True (motifAmount = 1) computes every run
         r = 0 … numberOfRepetitions in one Context.motif_sampling_batch call, the runs'
         greedy passes side by side on the GPU, and replays the same loop over them:
-        the same result, all runs paid for even when the loop stops early."""
+        the same result, all runs paid for even when the loop stops early.  With Positions
+        lists (motifAmount >= 2) that is getMotifsWithBestInformationContentsBatched."""
         base = _seed(seed)
         if batch:
             if motifAmount != 1:
@@ -193,6 +195,28 @@ class MotifSampler:
             lambda r: MotifSampler.doMotifSampling(motifAmount, motifLength, pseudoCount,
                                                    cutOff, alphabet, sources, base + r,
                                                    init_mode, device),
+            lambda xs: sum(x.PWMS for x in xs), [createMotifIndex(0.0, [])])
+
+    @staticmethod
+    def getMotifsWithBestInformationContentsBatched(numberOfRepetitions: int, motifAmount: int,
+                                                    motifLength: int, pseudoCount: float,
+                                                    cutOff: float, alphabet, sources,
+                                                    seed: int | None = None, init_mode: int = 0,
+                                                    device: int = 0) -> list[MotifIndex]:
+        """getMotifsWithBestInformationContents with every run r = 0 … numberOfRepetitions
+        computed by one call, for any motifAmount: Context.motif_sampling_batch for
+        motifAmount = 1, Context.motif_sampling_multi_batch (Positions lists) above, then
+        the loop of .fs:973-998 replayed over the runs: the result of the loop, all runs
+        paid for even when it stops early."""
+        if not 1 <= motifAmount <= 16:
+            raise _native.ArgumentError(_native.GS_E_ARG, "motifAmount must be in [1, 16]")
+        ctx = _bind(alphabet, sources, device)
+        runs = _batched_runs if motifAmount == 1 else \
+            functools.partial(_batched_list_runs, motifAmount=motifAmount)
+        return _replay_repetitions(
+            numberOfRepetitions,
+            runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength, pseudoCount, cutOff,
+                 _seed(seed), init_mode),
             lambda xs: sum(x.PWMS for x in xs), [createMotifIndex(0.0, [])])
 
     # ---- the caller's background (…ByPCV, .fs:788-881) and profile (…OfPPM) twins
@@ -342,6 +366,22 @@ def _batched_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
             raise _native._ERRORS.get(int(status[r]), _native.DeviceError)(
                 int(status[r]), f"run {r} of the batch failed")
         return _motif_indices(pos[r], pwms[r])
+    return run
+
+
+def _batched_list_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
+                       init_mode: int, motifAmount: int) -> Callable[[int], list]:
+    """_batched_runs with Positions lists (motifAmount >= 2): one
+    Context.motif_sampling_multi_batch call."""
+    cnt, pos, pwms, _, status = ctx.motif_sampling_multi_batch(
+        motifAmount, motifLength, pseudoCount, cutOff, [base + r for r in range(count)],
+        init_mode, UNBOUNDED)
+
+    def run(r: int) -> list:
+        if status[r] != _native.GS_OK:
+            raise _native._ERRORS.get(int(status[r]), _native.DeviceError)(
+                int(status[r]), f"run {r} of the batch failed")
+        return _motif_lists(cnt[r], pos[r], pwms[r])
     return run
 
 

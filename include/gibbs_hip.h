@@ -184,6 +184,33 @@ int gs_motif_sampling_multi(gs_ctx *ctx, int32_t motif_amount, int32_t W, double
                             double cut_off, uint64_t seed, int32_t init_mode, int32_t max_passes,
                             int32_t cap, int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
                             int32_t *passes_out);
+/* R independent doMotifSampling runs (.fs:1034-1038) with Positions lists: chain r is exactly
+ * gs_motif_sampling_multi(ctx, motif_amount, W, pc, cut_off, seeds[r], init_mode, max_passes,
+ * cap, ...).  Returns the status of the lowest-index failing chain (gs_error_index: its
+ * sequence), GS_OK if none; the other chains' rows are still valid, list entries past cnt
+ * unspecified.  A chain with more than 2^28 categories gets GS_E_UNSUPPORTED in its own
+ * status_out entry and the other chains finish.  The chains' starts run back to back on the
+ * context's stream, sweep 0 over all (chain, target) pairs at once, the greedy passes as
+ * speculative steps of two launches for all chains; the host waits once per arena round and
+ * once per 32 steps.  n_chains == 0 does nothing.  GS_E_ARG before any launch: motif_amount
+ * or cap outside 1 .. 16, cap < motif_amount, max_passes < 1, a bad W or init_mode, a null
+ * output.  GS_E_UNSUPPORTED: sharded sequences or a communicator, a fixed PCV or PPM, chain
+ * slabs (arenas included) beyond 4 GiB, sequences too long for the list path's LDS carve.
+ * The context holds no snapshot afterwards and its error words are clear. */
+int gs_motif_sampling_multi_batch(gs_ctx *ctx, int32_t motif_amount, int32_t W, double pseudo_count,
+                                  double cut_off, const uint64_t *seeds, int32_t n_chains,
+                                  int32_t init_mode, int32_t max_passes, int32_t cap,
+                                  int32_t *cnt_out,    /* [n_chains][n_local]      */
+                                  int32_t *pos_out,    /* [n_chains][n_local][cap] */
+                                  double *pwms_out,    /* [n_chains][n_local]      */
+                                  int32_t *passes_out, /* [n_chains], nullable     */
+                                  int32_t *status_out  /* [n_chains], nullable     */);
+/* Device times of the last gs_motif_sampling_multi_batch, ms: starts, sweep, greedy passes. */
+int gs_multi_batch_last_ms(const gs_ctx *ctx, double out[3]);
+/* Its rounds: out[0] sweep rounds after the first (arena growth), out[1] greedy restart
+ * rounds, out[2] chains restarted in all, out[3] speculative slots per chain of the first
+ * greedy round. */
+int gs_multi_batch_last_info(const gs_ctx *ctx, int32_t out[4]);
 
 /* Global aggregates of a snapshot (parity hook): C[a*W+j] = number of motif
  * segments with alphabet[a] at column j (the PFM of .fs:955-962 over ALL
@@ -354,7 +381,7 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * admissible: the all-background sweep kernel), bg_G, bg_force_replay (tests:
  * its picks by the exact sequential replay), graph_mode, site_coop, coop_rate, motif_coop,
  * site_dt16, site_exit_chunk, site_exit_ratio, greedy_exit_chunk,
- * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots,
+ * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots, multi_batch_fill,
  * greedy_switch, site_switch.  GS_E_ARG for an unknown name or a value out of
  * range.  Set before gs_set_sequences (launch geometry is fixed there). */
 int gs_set_tuning(gs_ctx *ctx, const char *name, double value);
