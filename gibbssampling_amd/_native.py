@@ -156,6 +156,9 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
                                                     vp, vp, vp, vp, vp]),
         "gs_multi_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_multi_batch_last_info": (C.c_int, [vp, vp]),
+        "gs_motif_run_batch": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, vp, vp,
+                                         vp]),
+        "gs_run_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_set_fixed_pcv": (C.c_int, [vp, vp]),
         "gs_set_fixed_ppm": (C.c_int, [vp, vp, i32]),
         "gs_site_scan": (C.c_int, [vp, i32, f64, vp, vp, vp]),
@@ -471,6 +474,48 @@ class Context:
         self._check(self.lib.gs_multi_batch_last_info(self.h, _ptr(out)))
         return dict(zip(("sweep_rounds", "restart_rounds", "chains_restarted", "slots"),
                         (int(v) for v in out)))
+
+    def motif_run_batch(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds, pos=None,
+                        init_mode: int = 0, first_sweep: int = 0, u=None, strict: bool = False):
+        """R independent chains of n_sweeps sweeps in one call, row r exactly
+        motif_run(W, pc, cutoff, n_sweeps, seeds[r], start r, first_sweep): one launch a
+        sweep over all (chain, target) pairs -> (pos[R, N], pwms[R, N], status[R]).  The
+        starts are the rows of `pos` (-1 = Positions []; implies init_mode -1) or those of
+        random_starts(W, pc, seeds[r], init_mode).  u[R, n_sweeps, N] replaces the counter
+        RNG's uniforms.  pwms is unspecified for n_sweeps = 0.  A chain that raises
+        (status[r] != 0) leaves the other rows valid; errors of the call itself raise, and
+        with strict=True so does a chain's (the lowest-index failing chain's status, the
+        exception's index its sequence)."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        if pos is not None:
+            init_mode = -1
+            pos = np.array(pos, dtype=np.int32, copy=True)
+            if pos.shape != (R, self.n_local):
+                raise ArgumentError(GS_E_ARG, "pos needs one row per seed, one entry per sequence")
+        else:
+            if init_mode not in (0, 1):
+                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
+            pos = np.full((R, self.n_local), -1, np.int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (R, max(int(n_sweeps), 0), self.n_local):
+                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_motif_run_batch(self.h, int(W), float(pc), float(cutoff), int(n_sweeps),
+                                         _ptr(seeds), R, int(first_sweep), int(init_mode), _ptr(u),
+                                         _ptr(pos), _ptr(pwms), _ptr(status))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        return pos, pwms, status
+
+    def run_batch_last_ms(self):
+        """Device milliseconds of the last motif_run_batch: (starts and their aggregates,
+        sweeps)."""
+        out = np.zeros(2, np.float64)
+        self._check(self.lib.gs_run_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
 
     def set_fixed_pcv(self, pcv49) -> None:
         """The caller's ProbabilityCompositeVector (49 slots) for the ByPCV / WithBPV

@@ -48,6 +48,8 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(multi_greedy_threads, v >= 64 && v <= 1024 && (int)v % 64 == 0),
     GS_TUNING_FIELD(multi_spec_slots, v >= 1 && v <= 4096),
     GS_TUNING_FIELD(multi_batch_fill, v >= 1 && v <= 4096),
+    GS_TUNING_FIELD(run_batch_clear, v == 0 || v == 1),
+    GS_TUNING_FIELD(run_batch_blocks, v >= 1 && v <= 32),
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(site_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(ftab_mode, v == 0 || v == 1 || v == 2),
@@ -944,6 +946,210 @@ static int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff
                                     ? "a sequence has more than 2^28 motif combinations "
                                       "(.fs:727-742)"
                                     : device_error_message(first_status)) +
+                        " (chain " + std::to_string(first) + ")",
+                    (int64_t)(herr[(size_t)first] >> 4));
+    return GS_OK;
+}
+
+namespace {
+// Device slabs of one chain batch (row r = chain r), freed on scope exit.
+struct RunBatchBufs {
+    int32_t *pos[2] = {nullptr, nullptr};
+    double *pwms = nullptr, *u = nullptr;
+    int64_t *agg[3] = {nullptr, nullptr, nullptr};  // rows, then the chains' skip words
+    unsigned long long *err = nullptr;
+    uint64_t *seeds = nullptr;
+    SpecCtl *ctl = nullptr;
+    int32_t *cnt = nullptr, *starts = nullptr, *cpart = nullptr;
+    ~RunBatchBufs() {
+        for (auto &q : pos) dfree(q);
+        for (auto &q : agg) dfree(q);
+        dfree(pwms);
+        dfree(u);
+        dfree(err);
+        dfree(seeds);
+        dfree(ctl);
+        dfree(cnt);
+        dfree(starts);
+        dfree(cpart);
+    }
+};
+}  // namespace
+
+// R independent chains of T synchronous sweeps (motifAmount = 1), DESIGN.md §9.13.  Stage
+// 1: the chains' starts, uploaded rows (mode -1) or, chain after chain on the context's
+// single-chain state and stream as in multi_batch, those of getPWMOfRandomStarts; then the
+// aggregates of every chain's starts.  Stage 2: T launches of gs_run_batch_sweep_kernel
+// over the (chain, target) pairs back to back, positions double-buffered, the aggregate
+// rows rotating over three buffers (the next one zeroed by a memset before the sweep that
+// fills it, or by the sweep before: tune.run_batch_clear).  One synchronisation, one
+// download.  The caller validated the arguments.
+static int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T,
+                     const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode,
+                     const double *u, int32_t *pos_inout, double *pwms_out, int32_t *status_out) {
+    int rc;
+    const int64_t n = c->n_local;
+    c->run_batch_ms[0] = c->run_batch_ms[1] = 0.0;
+    if (status_out)
+        for (int32_t r = 0; r < R; ++r) status_out[r] = GS_OK;
+    if (n == 0) return GS_OK;
+    MultiArgs a{};
+    const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
+    if ((rc = multi_lds_check(c, lds))) return rc;
+    const int32_t cells = c->A * W + c->A;
+    const int64_t rows = (int64_t)R * n, agg_elems = (int64_t)R * cells + R;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    const int64_t u_elems = u ? rows * T : 0;
+    int blocks = 0;
+    HIP_TRY(c, gs_run_batch_occupancy(&blocks, (size_t)lds));
+    blocks = std::max(1, std::min(blocks, c->tune.run_batch_blocks));
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)c->n_cu * blocks));
+    // per chain: two position rows, a PWMS row, three aggregate rows and skip words, error
+    // word, seed, control block (and the shared draws); the explicit uniforms; the window
+    // scores of a workgroup when they do not fit in LDS
+    const int64_t bytes = (int64_t)R * (n * (8 + 8 + (mode == 1 ? 4 : 0)) + 3 * 8 * ((int64_t)cells + 1) +
+                                        8 + 8 + (int64_t)sizeof(SpecCtl)) +
+                          n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax;
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_run_batch: the chains' slabs take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a batch may hold: split the seeds over several calls");
+    if (mode >= 0 && (rc = ensure_state(c, W))) return rc;
+    if ((rc = multi_scratch(c, a, grid, 0))) return rc;
+    RunBatchBufs b;
+    for (auto &q : b.pos) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 4));
+    for (auto &q : b.agg) HIP_TRY(c, hipMalloc(&q, (size_t)agg_elems * 8));
+    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)rows * 8));
+    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 8));
+    HIP_TRY(c, hipMalloc(&b.seeds, (size_t)R * 8));
+    if (u_elems > 0) {
+        HIP_TRY(c, hipMalloc(&b.u, (size_t)u_elems * 8));
+        HIP_TRY(c, hipMemcpyAsync(b.u, u, (size_t)u_elems * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(b.seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+    for (auto &q : b.agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
+    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
+    RunBatchArgs ba{};
+    ba.n_chains = R;
+    ba.cells = cells;
+    ba.seeds = b.seeds;
+    ba.err = b.err;
+    ba.n_pairs = rows;
+    ba.u_stride = (int64_t)T * n;
+    const bool clear_in_kernel = c->tune.run_batch_clear == 1;
+    const int agg_blocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
+    hipEvent_t ev[3] = {get_event(c), get_event(c), get_event(c)};
+    rc = [&]() -> int {
+        int rc2;
+        // ---- stage 1: every chain's starts and their aggregates ----
+        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+        if (mode < 0) {
+            HIP_TRY(c, hipMemcpyAsync(b.pos[0], pos_inout, (size_t)rows * 4, hipMemcpyHostToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemsetAsync(b.err, 0xff, (size_t)R * 8, c->stream));
+        } else {
+            HIP_TRY(c, hipMalloc(&b.cnt, (size_t)n * 4));
+            HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * sizeof(SpecCtl)));
+            if (mode == 0) {
+                HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
+            } else {
+                HIP_TRY(c, hipMalloc(&b.starts, (size_t)rows * 4));
+                hs.resize((size_t)rows);
+                for (int32_t r = 0; r < R; ++r)
+                    for (int64_t i = 0; i < n; ++i)
+                        hs[(size_t)(r * n + i)] =
+                            uniform_int(seeds[r], stream_init_shared(),
+                                        (uint64_t)(c->global_offset + i), c->h_len[i] - W + 1);
+                HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
+                                          c->stream));
+            }
+            for (int32_t r = 0; r < R; ++r) {
+                // (as multi_batch) the start vector the aggregate pass reads
+                if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
+                if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
+                    return rc2;
+                // a target that raises (.fs:117) writes no start: every entry stays a valid one
+                HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
+                if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
+                // lists of capacity 1 are the position rows; a chain that raised keeps its word
+                HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, 1, b.cnt,
+                                                       b.pos[0] + r * n, c->d_err_code,
+                                                       c->d_err_index, b.err + r, b.ctl + r,
+                                                       c->stream));
+            }
+            // the context's own error words end clear, whatever the last chain's were
+            HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+            HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+        }
+        ba.pos_in = b.pos[0];
+        ba.agg_out = b.agg[0];
+        HIP_TRY(c, gs_run_batch_agg_launch(a, ba, agg_blocks, c->stream));
+        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+        // ---- stage 2: T sweeps of every chain, no host wait in between ----
+        for (int32_t t = 0; t < T; ++t) {
+            const int cur = t % 3, nxt = (t + 1) % 3, aft = (t + 2) % 3;
+            // buffer nxt is zero from the start (t < 2), from sweep t - 1, or from here
+            if (!clear_in_kernel && t >= 2)
+                HIP_TRY(c, hipMemsetAsync(b.agg[nxt], 0, (size_t)agg_elems * 8, c->stream));
+            ba.pos_in = b.pos[t & 1];
+            ba.pos_out = b.pos[(t + 1) & 1];
+            ba.pwms_out = t == T - 1 ? b.pwms : nullptr;
+            ba.agg_in = b.agg[cur];
+            ba.agg_out = b.agg[nxt];
+            ba.agg_clear = clear_in_kernel && t >= 1 ? b.agg[aft] : nullptr;
+            ba.u = b.u ? b.u + (int64_t)t * n : nullptr;
+            a.stream = stream_sweep((uint64_t)(first_sweep + t));
+            HIP_TRY(c, gs_run_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
+        }
+        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    if (mode >= 0) {
+        // the context's single-chain buffers were the chains' scratch: no snapshot is left
+        c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+        c->note_pending = false;
+        c->ftab_agg = -1;
+    }
+    c->have_state = false;
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
+    else
+        for (int i = 0; i < 2; ++i) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+                c->run_batch_ms[i] = (double)ms;
+        }
+    for (hipEvent_t e : ev) c->ev_pool.push_back(e);
+    if (rc) return rc;
+    // ---- stage 3: one download ----
+    std::vector<unsigned long long> herr((size_t)R);
+    if (T > 0 || mode >= 0)
+        HIP_TRY(c, hipMemcpyAsync(pos_inout, b.pos[T & 1], (size_t)rows * 4, hipMemcpyDeviceToHost,
+                                  c->stream));
+    if (T > 0)
+        HIP_TRY(c, hipMemcpyAsync(pwms_out, b.pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipMemcpyAsync(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int first = -1, first_status = GS_OK;
+    for (int32_t r = 0; r < R; ++r) {
+        const unsigned long long e = herr[(size_t)r];
+        const int st = (int)(e & 15ull);
+        const int status = e == ~0ull ? GS_OK
+                           : st == 2  ? GS_E_ROULETTE_OVERRUN
+                           : st == 3  ? GS_E_OVERFLOW
+                                      : GS_E_HIP;
+        if (status_out) status_out[r] = status;
+        if (status != GS_OK && first < 0) {
+            first = r;
+            first_status = status;
+        }
+    }
+    if (first >= 0)
+        return fail(c, first_status,
+                    std::string(device_error_message((int)(herr[(size_t)first] & 15ull))) +
                         " (chain " + std::to_string(first) + ")",
                     (int64_t)(herr[(size_t)first] >> 4));
     return GS_OK;
@@ -1858,6 +2064,41 @@ int gs_multi_batch_last_ms(const gs_ctx *c, double out[3]) {
 int gs_multi_batch_last_info(const gs_ctx *c, int32_t out[4]) {
     if (!c || !out) return GS_E_ARG;
     for (int i = 0; i < 4; ++i) out[i] = c->multi_batch_info[i];
+    return GS_OK;
+}
+
+int gs_motif_run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                       const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                       int32_t init_mode, const double *u, int32_t *pos_inout, double *pwms_out,
+                       int32_t *status_out) {
+    if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
+        return GS_E_ARG;
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!pos_inout || !pwms_out))) return GS_E_ARG;
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_run_batch: a chain's aggregates are summed on one device: it needs "
+                    "all sequences there and no communicator");
+    if (c->use_pcv || c->use_ppm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_run_batch: the ByPCV / OfPPM twins are not batched (clear the "
+                    "fixed PCV / PPM, or loop gs_motif_run)");
+    if (init_mode == -1)
+        for (int32_t r = 0; r < n_chains; ++r)
+            if ((rc = validate_pos(c, W, pos_inout + (int64_t)r * c->n_local))) return rc;
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    takeover_reset(c);
+    return run_batch(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep, init_mode, u,
+                     pos_inout, pwms_out, status_out);
+}
+
+int gs_run_batch_last_ms(const gs_ctx *c, double out[2]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->run_batch_ms[0];
+    out[1] = c->run_batch_ms[1];
     return GS_OK;
 }
 

@@ -51,6 +51,8 @@ struct gs_tuning {
     int32_t multi_greedy_threads = 512;  // list-path greedy: threads per workgroup (64 .. 1024, multiple of 64)
     int32_t multi_spec_slots = 256;  // list-path greedy: visits scored per speculative step
     int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
+    int32_t run_batch_clear = 1;  // chain batch: the next aggregate rows zeroed by a memset before each sweep (0) or a third row cleared in-kernel (1: 1 - 3 % faster at 200 and 2 000 sequences)
+    int32_t run_batch_blocks = 32;  // chain batch: cap on the one-wavefront workgroups per CU of its sweep launches (8 / 16 / 32, i.e. what fits: 18.1 / 12.6 / 11.3 ms for 64 chains x 200 sweeps x 200 sequences)
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
     int32_t ftab_mode = 0;  // four-symbol sweep's workgroup tables: 0 built by every workgroup, 1 by a table kernel before the sweep, 2 handed over by the previous sweep's last workgroup (one GPU; else 1); 1 and 2 need the -DGS_FTAB build
     int32_t site_switch = 4;  // the same for the site sampler (cfg2: 4 / 16 / 2 -> 231 / 245 / 252 ms)
@@ -157,6 +159,29 @@ hipError_t gs_multi_batch_restart_launch(const MultiBatchArgs &b, int32_t n, int
                                          double *pw, int64_t *agg, hipStream_t s);
 hipError_t gs_multi_batch_spec_launch(const MultiArgs &a, const MultiBatchArgs &b, int threads,
                                       size_t lds, int steps, hipStream_t s);
+// What gs_motif_run_batch adds to MultiArgs (gs_multi.hip): R chains of
+// single positions (-1 = Positions []) side by side, one sweep of all chains a launch.  An
+// aggregate buffer holds the chains' rows ([n_chains][cells] int64, C then T) followed by
+// one word a chain: set once the chain raised, so that its later sweeps are skipped.
+struct RunBatchArgs {
+    int32_t n_chains, cells;
+    const uint64_t *seeds;       // [R]
+    unsigned long long *err;     // [R]: packed (global index << 4) | status, atomicMin
+    const int32_t *pos_in;       // [R][n_local]: the snapshot
+    int32_t *pos_out;            // [R][n_local]
+    double *pwms_out;            // [R][n_local], or null: not the chains' last sweep
+    const int64_t *agg_in;       // the snapshot's buffer
+    int64_t *agg_out;            // the next snapshot's, zero at launch, filled by this sweep
+    int64_t *agg_clear;          // a third buffer to zero for the sweep after, or null
+    const double *u;             // explicit uniforms of this sweep: u[r * u_stride + n], or null
+    int64_t u_stride;
+    int64_t n_pairs;             // n_chains * n_local
+};
+hipError_t gs_run_batch_agg_launch(const MultiArgs &a, const RunBatchArgs &b, int blocks_per_chain,
+                                   hipStream_t s);
+hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, int grid, size_t lds,
+                                     hipStream_t s);
+hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds);
 hipError_t gs_single_lists_launch(const int32_t *pos, int32_t n, int32_t *cnt, int32_t *lst,
                                   int to_lists, hipStream_t s);
 hipError_t gs_count_diff_launch(const int32_t *a, const int32_t *b, int32_t n, int32_t *out,
@@ -270,6 +295,7 @@ struct gs_ctx {
     double batch_ms[2] = {0.0, 0.0};  // the last batch call: stage 1 (all chains), greedy launch
     double site_batch_ms[3] = {0.0, 0.0, 0.0};  // the last site batch: starts, Gauss–Seidel launch, shifted passes
     double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
+    double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
     int32_t multi_batch_info[4] = {0, 0, 0, 0};  // ... sweep arena rounds, greedy restart rounds, chains restarted, slots
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG

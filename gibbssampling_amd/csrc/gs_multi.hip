@@ -1190,3 +1190,137 @@ hipError_t gs_multi_batch_spec_launch(const MultiArgs &a, const MultiBatchArgs &
     }
     return hipGetLastError();
 }
+
+// ---- R chains of synchronous sweeps (gs_motif_run_batch) ----
+// motifAmount = 1 with single positions (-1 = Positions []): build_levels would build
+// nothing (top = 0), so a sweep needs no arena, no overflow round and no host wait.  An
+// aggregate buffer holds the chains' rows followed by one skip word a chain (RunBatchArgs).
+// The kernel boundary is the only synchronisation: a sweep reads b.agg_in, written before
+// its launch, and adds into b.agg_out, read after it.
+
+// The aggregates of every chain's positions into row r of the zeroed b.agg_out
+// (gs_multi_batch_agg_kernel's pattern: gridDim.x / n_chains workgroups a chain, LDS first);
+// a chain that raised in its starts gets its skip word instead.
+extern "C" __global__ void __launch_bounds__(256)
+gs_run_batch_agg_kernel(MultiArgs a, RunBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    unsigned long long *acc = (unsigned long long *)lds;
+    const int A = a.A, W = a.W, cells = b.cells;
+    const int bpc = gridDim.x / b.n_chains;
+    const int r = blockIdx.x / bpc, blk = blockIdx.x - r * bpc;
+    if (b.err[r] != ~0ull) {
+        if (blk == 0 && threadIdx.x == 0) b.agg_out[(int64_t)b.n_chains * cells + r] = 1;
+        return;
+    }
+    const int32_t *pos = b.pos_in + (int64_t)r * a.n_local;
+    for (int x = threadIdx.x; x < cells; x += blockDim.x) acc[x] = 0ull;
+    __syncthreads();
+    for (int n = blk * blockDim.x + threadIdx.x; n < a.n_local; n += bpc * blockDim.x) {
+        const int p = pos[n];
+        if (p < 0) continue;
+        const uint8_t *s = a.seq + a.doff[n];
+        for (int x = 0; x < A; ++x)
+            atomicAdd(&acc[A * W + x], (unsigned long long)a.comp[(int64_t)n * (a.E + 1) + x]);
+        for (int j = 0; j < W; ++j) {
+            const int e = s[p + j];
+            if (e < A) {
+                atomicAdd(&acc[e * W + j], 1ull);
+                atomicAdd(&acc[A * W + e], ~0ull);  // -1
+            }
+        }
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < cells; x += blockDim.x)
+        if (acc[x]) atomicAdd((unsigned long long *)&b.agg_out[(int64_t)r * cells + x], acc[x]);
+}
+
+// One sweep (.fs:935-970) of every chain over the linearised (chain, target) pairs, one
+// wavefront a pair: the uniform of pair (r, n) is uniform(seeds[r], a.stream, global n) or
+// b.u[r * u_stride + n].  After its pick a pair adds its new segment's C cells and
+// comp - segment T cells to the chain's row of the next snapshot's aggregates.  A chain
+// that raises keeps the lowest (index, status) of the sweep in its word of b.err and sets
+// its skip word of b.agg_out, which the later sweeps hand on.
+extern "C" __global__ void __launch_bounds__(64)
+gs_run_batch_sweep_kernel(MultiArgs a, RunBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double *tab = (double *)(lds + a.o_tab);
+    double *pcv = (double *)(lds + a.o_pcv);
+    uint8_t *sseq = lds + a.o_seq;
+    __shared__ int flag;
+    const int lane = threadIdx.x;
+    const Slot sl = slot_of(a, blockIdx.x, lds);
+    const int A = a.A, W = a.W, AW = A * W, cells = b.cells;
+    const int64_t rows = (int64_t)b.n_chains * cells;
+    for (int64_t pair = blockIdx.x; pair < b.n_pairs; pair += gridDim.x) {
+        const int r = (int)(pair / a.n_local);
+        const int n = (int)(pair - (int64_t)r * a.n_local);
+        if (n == 0 && b.agg_clear) {  // the row the sweep after this one fills
+            for (int x = lane; x < cells; x += 64) b.agg_clear[(int64_t)r * cells + x] = 0;
+            if (lane == 0) b.agg_clear[rows + r] = 0;
+        }
+        if (b.agg_in[rows + r]) {  // raised in its starts or in an earlier sweep
+            if (n == 0 && lane == 0) b.agg_out[rows + r] = 1;
+            continue;
+        }
+        const int64_t *C = b.agg_in + (int64_t)r * cells, *T = C + AW;
+        const int64_t row = (int64_t)r * a.n_local;
+        const int L = a.len[n];
+        const int K = L - W + 1;
+        const int64_t gidx = a.global_offset + n;
+        __syncthreads();
+        stage(a.seq + a.doff[n], L, sseq);
+        __syncthreads();
+        const int32_t *pos = b.pos_in + row + n;
+        const int st = prepare_target(a, n, L, sseq, *pos >= 0, pos, C, T, tab, pcv, sl, &flag);
+        const double u = b.u ? b.u[(int64_t)r * b.u_stride + n]
+                             : uniform(b.seeds[r], a.stream, (uint64_t)gidx);
+        RPick pk{-2, -1, -1, 0.0};
+        // the categories: [(G_k, [])] ++ the passing (log2 (S_k * 1.0), [k]), the last
+        // level's children of the root (.fs:759-784 with motifAmount = 1)
+        if (!st) pk = roulette(a, sl, K, 0, -1, 0, u, lane);
+        if (st || pk.c == -2) {  // .fs:117 / list index past the end (.fs:752)
+            if (lane == 0) {
+                atomicMin(b.err + r, ((unsigned long long)gidx << 4) | (unsigned long long)(st ? st : 2));
+                b.agg_out[rows + r] = 1;
+            }
+            continue;
+        }
+        const int pnew = pk.c == -1 ? pk.j : -1;
+        if (lane == 0) {
+            b.pos_out[row + n] = pnew;
+            if (b.pwms_out) b.pwms_out[row + n] = pk.c == -1 ? pk.w : sl.G[pk.c];
+        }
+        if (pnew >= 0) {
+            unsigned long long *Cn = (unsigned long long *)(b.agg_out + (int64_t)r * cells);
+            for (int j = lane; j < W; j += 64) {
+                const int e = sseq[pnew + j];
+                if (e < A) atomicAdd(&Cn[e * W + j], 1ull);
+            }
+            if (lane < A) {
+                int64_t t = a.comp[(int64_t)n * (a.E + 1) + lane];
+                for (int j = 0; j < W; ++j) t -= sseq[pnew + j] == lane;
+                if (t) atomicAdd(&Cn[AW + lane], (unsigned long long)t);
+            }
+        }
+    }
+}
+
+hipError_t gs_run_batch_agg_launch(const MultiArgs &a, const RunBatchArgs &b, int blocks_per_chain,
+                                   hipStream_t s) {
+    if (a.n_local <= 0 || b.n_chains <= 0) return hipSuccess;
+    const size_t lds = 8 * (size_t)b.cells;
+    hipLaunchKernelGGL(gs_run_batch_agg_kernel, dim3(b.n_chains * blocks_per_chain), dim3(256), lds,
+                       s, a, b);
+    return hipGetLastError();
+}
+
+hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, int grid, size_t lds,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(gs_run_batch_sweep_kernel, dim3(grid), dim3(64), lds, s, a, b);
+    return hipGetLastError();
+}
+
+hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, gs_run_batch_sweep_kernel, 64,
+                                                        lds);
+}

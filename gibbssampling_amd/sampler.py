@@ -134,6 +134,35 @@ class MotifSampler:
         return _motif_indices(pos, pwms)
 
     @staticmethod
+    def runSweepsBatched(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,
+                         sweeps: int, seeds, motifMems=None, init_mode: int = 0,
+                         first_sweep: int = 0, device: int = 0) -> list[list[MotifIndex]]:
+        """One independent chain of `sweeps` chained sweeps per seed, all in one
+        Context.motif_run_batch call: entry r is runSweeps(..., motifMems[r], sweeps,
+        seeds[r], first_sweep).  Without motifMems chain r starts from getPWMOfRandomStarts
+        of seeds[r] (init_mode as in doMotifSampling).  A chain that raised raises here.
+        Faster than the loop up to about 2 000 sequences a chain, slower beyond
+        (DESIGN.md §9.13)."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        pos = None
+        if motifMems is not None:
+            if len(motifMems) != len(seeds):
+                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+            if any(len(m) != len(sources) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "a motifMem and sources differ in length")
+            pos = np.array([_single_positions(m) for m in motifMems],
+                           np.int32).reshape(len(seeds), len(sources))
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, status = ctx.motif_run_batch(motifLength, pseudoCount, cutOff, sweeps, seeds,
+                                                pos, init_mode, first_sweep)
+        for r, st in enumerate(status):
+            if st != _native.GS_OK:
+                raise _native._ERRORS.get(int(st), _native.DeviceError)(
+                    int(st), f"chain {r} of the batch failed")
+        return [_motif_indices(pos[r], pwms[r]) for r in range(len(seeds))]
+
+    @staticmethod
     def findBestMotifIndicesWithStartPositions(motifAmount: int, motifLength: int,
                                                pseudoCount: float, cutOff: float, alphabet,
                                                sources, motifMem: Sequence[MotifIndex],

@@ -212,6 +212,35 @@ int gs_multi_batch_last_ms(const gs_ctx *ctx, double out[3]);
  * greedy round. */
 int gs_multi_batch_last_info(const gs_ctx *ctx, int32_t out[4]);
 
+/* R independent chains of n_sweeps synchronous sweeps each (motifAmount = 1) in one call:
+ * chain r is exactly gs_motif_run(ctx, W, pc, cut_off, n_sweeps, seeds[r], first_sweep,
+ * row r, ...) from its start.  init_mode -1: chain r starts from the caller's row
+ * pos_inout[r] (-1 = Positions []); 0 / 1: from the positions of gs_random_starts(ctx, W, pc,
+ * seeds[r], init_mode, ...), pos_inout is output only and sweep 0 is the sweep of
+ * doMotifSampling.  The uniform of sequence n in sweep t is gs_uniform(seeds[r],
+ * gs_stream_sweep(first_sweep + t), global n), or u[r][t][n] with u non-null (as
+ * gs_motif_sweep); a second call with init_mode -1 and first_sweep + n_sweeps continues the
+ * chains.  One sweep of all chains is one launch over the (chain, target) pairs, the launches
+ * back to back with one synchronisation at the end.  PWMS are those of the last sweep;
+ * n_sweeps == 0 leaves the positions as they are (init_mode 0 / 1: the starts) and does not
+ * write pwms_out; n_chains == 0 does nothing.  Returns the status of the lowest-index failing
+ * chain (gs_error_index: its sequence), GS_OK if none: a chain that raises (.fs:752, .fs:117)
+ * keeps its status in status_out[r], its later sweeps are skipped and its rows unspecified;
+ * the other chains finish.  GS_E_ARG before any launch: a bad W or init_mode, n_sweeps < 0,
+ * first_sweep < 0, a null seeds or output, a start outside [-1, L - W] (init_mode -1).
+ * GS_E_UNSUPPORTED: sharded sequences or a communicator, a fixed PCV or PPM, chain slabs
+ * beyond 4 GiB, sequences too long for the list path's LDS carve.  The context holds no
+ * snapshot afterwards and its error words are clear. */
+int gs_motif_run_batch(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+                       int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains,
+                       int64_t first_sweep, int32_t init_mode,
+                       const double *u,      /* nullable: [n_chains][n_sweeps][n_local] */
+                       int32_t *pos_inout,   /* [n_chains][n_local], -1 = Positions []   */
+                       double *pwms_out,     /* [n_chains][n_local]                      */
+                       int32_t *status_out   /* [n_chains], nullable                     */);
+/* Device times of the last gs_motif_run_batch, ms: starts (and first aggregates), sweeps. */
+int gs_run_batch_last_ms(const gs_ctx *ctx, double out[2]);
+
 /* Global aggregates of a snapshot (parity hook): C[a*W+j] = number of motif
  * segments with alphabet[a] at column j (the PFM of .fs:955-962 over ALL
  * sequences), T[a] = sum over sequences with a motif of the alphabet[a] count
@@ -382,6 +411,8 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * its picks by the exact sequential replay), graph_mode, site_coop, coop_rate, motif_coop,
  * site_dt16, site_exit_chunk, site_exit_ratio, greedy_exit_chunk,
  * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots, multi_batch_fill,
+ * run_batch_clear (gs_motif_run_batch: 0 a memset of the next aggregate rows before each
+ * sweep, 1 a third row cleared in-kernel), run_batch_blocks (its workgroups per CU),
  * greedy_switch, site_switch.  GS_E_ARG for an unknown name or a value out of
  * range.  Set before gs_set_sequences (launch geometry is fixed there). */
 int gs_set_tuning(gs_ctx *ctx, const char *name, double value);
