@@ -1,9 +1,9 @@
 // gs_api.cpp — C ABI (include/gibbs_hip.h) over the gfx950 kernels.
 //
-// Entry points only: argument validation with the reference's error behaviour and
-// the calls into the engine (gs_engine.cpp).  The HBM layout (encoded symbols, 16-byte
-// aligned per sequence), the device snapshot state and the RCCL all-reduces live
-// there.
+// Entry points only: the tuning table, argument validation with the reference's error
+// behaviour and the calls into the engine (gs_engine.cpp) and the batch drivers
+// (gs_batch.cpp).  The HBM layout (encoded symbols, 16-byte aligned per sequence), the
+// device snapshot state and the RCCL all-reduces live in the engine.
 #include "gs_ctx.h"
 
 using namespace gs_host;
@@ -68,1090 +68,20 @@ const char *kVersion = "gibbs_hip 0.1.0 (gfx950)";
 
 }  // namespace
 
-// The all-background takeover (gs_engine.cpp bg_ready) is dropped by every call
-// that changes what the next sweep computes: the sampler's parameters (fixed PCV,
-// scan mode, communicator) or its positions outside set_snapshot (which drops it
-// itself).  Called only once a call's arguments are validated, so that a rejected
-// call on one rank leaves every rank's state alike.
 static void exchange_unmap(gs_ctx *c);
 
-static void takeover_reset(gs_ctx *c) {
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
-}
-
-// ---- gs_motif_sampling_batch: R chains, one greedy launch ----
-
-// getPWMOfRandomStarts on the stream: the draws' partial counts (mode 0, into the caller's
-// d_cpart of n_global * A * W int32), then the Jacobi pass over the snapshot just set
-// (d_agg[cur_agg]) -> d_pwms, d_pos[1].  No synchronisation.
-static int starts_enqueue(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, int32_t *d_cpart) {
-    const int A = c->A, AW = A * W;
-    if (mode == 0) {
-        HIP_TRY(c, hipMemsetAsync(d_cpart, 0, (size_t)c->n_global * AW * 4, c->stream));
-        PartialArgs p{};
-        p.seq = c->d_seq;
-        p.doff = c->d_doff;
-        p.len = c->d_len;
-        p.n_local = c->n_local;
-        p.global_offset = c->global_offset;
-        p.n_global = c->n_global;
-        p.A = A;
-        p.W = W;
-        p.seed = seed;
-        p.cpart = d_cpart;
-        if (c->n_local > 0) {
-            int grid = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_global, c->n_cu * 8));
-            HIP_TRY(c, gs_starts_partial_launch(p, grid, c->stream));
-        }
-        if (c->comm)
-            RCCL_TRY(c, ncclAllReduce(d_cpart, d_cpart, (size_t)c->n_global * AW, ncclInt32,
-                                      ncclSum, c->comm, c->stream));
-    }
-    return starts_pass(c, mode, W, pc, seed, nullptr, d_cpart, c->d_agg[c->cur_agg], c->d_pwms,
-                       c->d_pos[1], c->use_ppm ? c->d_ppm_fixed : nullptr);
-}
-
-static const char *device_error_message(int code) {  // (as check_device_error)
-    return code == 2   ? "roulette wheel ran past the last category (.fs:752)"
-           : code == 3 ? "background count sum overflows int32 (.fs:117)"
-                       : "device error";
-}
-
-// The state buffers for W, kept when they are already there: alloc_state keys on
-// have_state, which is false between a batch's chains and after gs_random_starts, and
-// would free and reallocate buffers that enqueued work still names.
-static int ensure_state(gs_ctx *c, int32_t W) {
-    if (c->d_pos[0] && c->W == W) return GS_OK;
-    return alloc_state(c, W);
-}
-
-// The device-resident route to a snapshot (set_snapshot without its host side, single
-// device, no communicator): positions already on the device (d_src, valid by
-// construction: nothing is checked on the host, and they are never all []) go to
-// d_pos[0] on the stream, their aggregates to d_agg[0].  reset_err = false keeps a sticky
-// device error of the kernels that produced them.
-static int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool reset_err) {
+// What the four batched entry points check alike once their own arguments are in range
+// (messages: "<name>: <text>"): the device, W, all sequences on one device with no
+// communicator (why_one_device), no fixed PCV / PPM (twins_text).
+static int batch_entry_checks(gs_ctx *c, const char *name, int32_t W, const char *why_one_device,
+                              const char *twins_text) {
     int rc;
+    if ((rc = check_dev(c))) return rc;
     if ((rc = validate_W(c, W))) return rc;
-    if ((rc = ensure_state(c, W))) return rc;
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
-    if (!c->d_bg_note) HIP_TRY(c, hipMalloc(&c->d_bg_note, 4));
-    HIP_TRY(c, hipMemsetAsync(c->d_bg_note, 0, 4, c->stream));
-    if (d_src != c->d_pos[0] && c->n_local > 0)
-        HIP_TRY(c, hipMemcpyAsync(c->d_pos[0], d_src, (size_t)c->n_local * 4,
-                                  hipMemcpyDeviceToDevice, c->stream));
-    c->cur_pos = 0;
-    for (auto &b : c->d_agg)
-        HIP_TRY(c, hipMemsetAsync(b, 0, (size_t)kRepl * c->stride * 8, c->stream));
-    if (reset_err) {
-        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
-    }
-    if (c->n_local > 0)
-        if ((rc = launch_sweep(c, 1, 0.0, 0.0, nullptr, 0, 0, -1, 0, -1))) return rc;
-    c->cur_agg = 0;
-    c->rep_valid = true;
-    c->vec_valid = false;
-    c->dna_agree = true;
-    c->bg_agree = true;
-    HIP_TRY(c, hipMemsetAsync(c->d_gen_done, 0, kDoneBytes, c->stream));
-    c->ftab_agg = -1;
-    if (c->dna_ok) {
-        c->cur_aggv = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_rep, 0, (size_t)kRepl * c->stride * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_dna_done, 0, kDoneBytes, c->stream));
-        if (use_dna(c) && (rc = need_vec(c))) return rc;
-    }
-    c->have_state = true;
-    return GS_OK;
-}
-
-// The greedy arguments that do not name a chain's buffers, with the LDS carve of
-// greedy_run (gs_engine.cpp): the workgroup part, the visit ring of 2 * waves slots, one
-// slice per wavefront: the (PWM, PCV) table and the PCV (site = 0, the motif sampler), or
-// the D table, the others' background and the composition (site = 1, the site sampler).
-static int greedy_carve(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes,
-                        GreedyArgs &a, int &waves_out, int64_t &lds_out) {
-    const int A = c->A, E = c->E, W = c->W, WM = gs_sweep_wm(W);
-    int64_t o = 0;
-    auto take = [&](int64_t b) {
-        int64_t q = o;
-        o = align16(o + b);
-        return (int32_t)q;
-    };
-    a.o_C = take(4 * (int64_t)A * W);
-    a.o_T = take(8 * (int64_t)A);
-    a.o_ppmG = take(8 * (int64_t)A * W);
-    a.o_ppmM = take(8 * (int64_t)A * W);
-    a.o_ctl = take(4 * 64);
-    const int64_t fixed = o;
-    a.ring_seq_bytes = (int32_t)(align16(c->Lmax) + align16(WM) + 32);
-    int64_t wb = 0;
-    if (site) {
-        a.w_dt = 0;
-        // D_k[b] <= (k + 1) W <= Lmax W: two bytes an entry when that fits
-        a.dt16 = (int64_t)c->Lmax * W < 65536 && c->tune.site_dt16 ? 1 : 0;
-        wb = align16((a.dt16 ? 2 : 4) * (int64_t)c->Lmax * A);
-        a.w_bg = (int32_t)wb;
-        wb += 8 * 64;
-        a.w_comp = (int32_t)wb;
-        wb += 4 * 64;
-    } else {
-        a.w_tab = 0;
-        wb = align16(16 * (int64_t)E * tab_stride(WM));
-        a.w_pcv = (int32_t)wb;
-        wb += 8 * 64;
-    }
-    a.wave_bytes = (int32_t)wb;
-    a.site = site;
-    const int64_t per_wave = wb + 2 * (a.ring_seq_bytes + 4 * 3 + 8 + 4 * 64) + 64 + 32;
-    int waves = c->tune.greedy_waves;
-    while (waves > 1 && fixed + per_wave * waves > c->max_lds) --waves;
-    if ((int64_t)waves > c->n_local) waves = (int)std::max<int64_t>(1, c->n_local);
-    while (waves & (waves - 1)) waves &= waves - 1;  // a power of two (ring indexing)
-    const int R = 2 * waves;
-    a.o_ring = take((int64_t)R * a.ring_seq_bytes);
-    a.o_rt = take(4 * (int64_t)R);
-    a.o_rL = take(4 * (int64_t)R);
-    a.o_rp = take(4 * (int64_t)R);
-    a.o_rpw = take(8 * (int64_t)R);
-    a.o_rcomp = take(4 * 64 * (int64_t)R);
-    a.o_red = take(8 * 4 * (int64_t)waves);
-    a.o_wave = take((int64_t)waves * a.wave_bytes);
-    a.site_coop = site && c->tune.site_coop ? 1 : 0;
-    a.motif_coop = site ? 0 : c->tune.motif_coop;
-    a.coop_rate = site ? c->tune.coop_rate : 0.0f;
-    if (o > c->max_lds)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "longest sequence exceeds the greedy kernel's LDS budget (" +
-                        std::to_string(o) + " > " + std::to_string(c->max_lds) + " B)");
-    a.seq = c->d_seq;
-    a.doff = c->d_doff;
-    a.len = c->d_len;
-    a.comp = c->d_comp;
-    a.n = c->n_local;
-    a.A = A;
-    a.W = W;
-    a.E = E;
-    a.cells = c->cells;
-    a.stride = c->stride;
-    a.pc = pc;
-    a.cutoff = cutoff;
-    a.thr_lo = cutoff_threshold(cutoff);
-    a.apc = (double)A * pc;
-    a.den = (double)(c->n_global - 1) + a.apc;
-    a.max_passes = max_passes;
-    waves_out = waves;
-    lds_out = o;
-    return GS_OK;
-}
-
-namespace {
-// Device slabs of one batch call, freed on scope exit.
-struct BatchBufs {
-    int32_t *pos = nullptr, *passes = nullptr, *err = nullptr, *starts = nullptr, *cpart = nullptr;
-    double *pwms = nullptr;
-    int64_t *agg = nullptr;
-    unsigned long long *erri = nullptr;
-    // the site batch's shifted passes: start vectors, stage pass counts, pass control
-    int32_t *shifted = nullptr, *stage_passes = nullptr, *ctl = nullptr;
-    ~BatchBufs() {
-        dfree(shifted);
-        dfree(stage_passes);
-        dfree(ctl);
-        dfree(pos);
-        dfree(passes);
-        dfree(err);
-        dfree(starts);
-        dfree(cpart);
-        dfree(pwms);
-        dfree(agg);
-        dfree(erri);
-    }
-};
-}  // namespace
-
-// R independent doMotifSampling runs (.fs:1034-1038, motifAmount = 1).  Stage 1, chain
-// after chain on the context's single-chain state and stream, no host wait in between:
-// starts (seed r) -> snapshot of them -> sweep 0 of seed r -> device copies of positions,
-// PWMS, replica aggregates and the error words into slab r.  Stage 2: one launch of
-// gs_greedy_batch_kernel, workgroup r on slab r, every pass in-kernel.  One
-// synchronisation, then the slabs come down.  The caller validated the arguments.
-static int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds, int32_t R,
-                int32_t mode, int32_t max_passes, int32_t *pos_out, double *pwms_out,
-                int32_t *passes_out, int32_t *status_out) {
-    int rc;
-    const int64_t n = c->n_local;
-    if (n == 0) {
-        for (int32_t r = 0; r < R; ++r) {
-            if (passes_out) passes_out[r] = 0;
-            if (status_out) status_out[r] = GS_OK;
-        }
-        return GS_OK;
-    }
-    if ((rc = ensure_state(c, W))) return rc;
-    GreedyArgs a{};
-    int waves = 0;
-    int64_t lds = 0;
-    if ((rc = greedy_carve(c, 0, pc, cutoff, max_passes, a, waves, lds))) return rc;
-    const int64_t agg_elems = (int64_t)kRepl * c->stride;
-    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
-    const int64_t bytes = (int64_t)R * (n * (4 + 8 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 16) +
-                          cpart_bytes;
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_batch: the chains' slabs take " + std::to_string(bytes) +
-                        " B, more than the " + std::to_string(kBatchBytesMax) +
-                        " B a batch may hold: split the seeds over several calls");
-    BatchBufs b;
-    HIP_TRY(c, hipMalloc(&b.pos, (size_t)(R * n) * 4));
-    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)(R * n) * 8));
-    HIP_TRY(c, hipMalloc(&b.agg, (size_t)(R * agg_elems) * 8));
-    HIP_TRY(c, hipMalloc(&b.passes, (size_t)R * 4));
-    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 4));
-    HIP_TRY(c, hipMalloc(&b.erri, (size_t)R * 8));
-    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
-    if (mode == 0) {
-        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
-    } else {
-        HIP_TRY(c, hipMalloc(&b.starts, (size_t)(R * n) * 4));
-        hs.resize((size_t)(R * n));
-        for (int32_t r = 0; r < R; ++r)
-            for (int64_t i = 0; i < n; ++i)
-                hs[(size_t)(r * n + i)] =
-                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
-                                c->h_len[i] - W + 1);
-        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
-                                  c->stream));
-    }
-    hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
-    auto recycle = [&]() {
-        c->ev_pool.push_back(e0);
-        c->ev_pool.push_back(e1);
-        c->ev_pool.push_back(e2);
-    };
-    rc = [&]() -> int {
-        int rc2;
-        HIP_TRY(c, hipEventRecord(e0, c->stream));
-        for (int32_t r = 0; r < R; ++r) {
-            // the start vector the aggregate pass reads: the shared draws (mode 1), or any
-            // valid one (mode 0 takes only the composition totals from it)
-            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
-                return rc2;
-            // a target that raises (.fs:117) writes no start: every entry stays a valid one
-            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
-            // its error word stays set: the sweep skips, the chain's slab carries it
-            if ((rc2 = set_snapshot_dev(c, W, c->d_pos[1], false))) return rc2;
-            if (use_dna(c)) {  // (as gs_run_sweeps: the device sweep counter at sweep 0)
-                if ((rc2 = need_vec(c))) return rc2;
-                HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, 0ull, c->d_done_ctr, c->stream));
-            }
-            if ((rc2 = one_sweep(c, pc, cutoff, nullptr, seeds[r], stream_sweep(0), true)))
-                return rc2;
-            if ((rc2 = need_rep(c))) return rc2;
-            HIP_TRY(c, hipMemcpyAsync(b.pos + r * n, c->d_pos[c->cur_pos], (size_t)n * 4,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.pwms + r * n, c->d_pwms, (size_t)n * 8,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.agg + r * agg_elems, c->d_agg[c->cur_agg],
-                                      (size_t)agg_elems * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.err + r, c->d_err_code, 4, hipMemcpyDeviceToDevice,
-                                      c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.erri + r, c->d_err_index, 8, hipMemcpyDeviceToDevice,
-                                      c->stream));
-        }
-        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
-        HIP_TRY(c, hipEventRecord(e1, c->stream));
-        a.agg = b.agg;
-        a.pos = b.pos;
-        a.pwms = b.pwms;
-        a.passes_out = b.passes;
-        a.err_code = b.err;
-        a.err_index = b.erri;
-        a.exit_chunk = 0;
-        a.exit_out = nullptr;
-        HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
-        HIP_TRY(c, hipEventRecord(e2, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }();
-    // the context's single-chain buffers were the chains' scratch: no snapshot is left
-    c->have_state = false;
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
-    c->ftab_agg = -1;
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
-        recycle();
-        return rc;
-    }
-    c->last_greedy_waves = waves;
-    float ms1 = 0.0f, ms2 = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms1, e0, e1));
-    HIP_TRY(c, hipEventElapsedTime(&ms2, e1, e2));
-    recycle();
-    c->batch_ms[0] = (double)ms1;
-    c->batch_ms[1] = (double)ms2;
-    std::vector<int32_t> herr((size_t)R), hpass((size_t)R);
-    std::vector<unsigned long long> hidx((size_t)R);
-    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(pwms_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
-    int first = -1;
-    for (int32_t r = 0; r < R; ++r) {
-        if (passes_out) passes_out[r] = hpass[(size_t)r];
-        if (status_out) status_out[r] = herr[(size_t)r];
-        if (herr[(size_t)r] != 0 && first < 0) first = r;
-    }
-    if (first >= 0)
-        return fail(c, herr[(size_t)first],
-                    std::string(device_error_message(herr[(size_t)first])) + " (chain " +
-                        std::to_string(first) + ")",
-                    (int64_t)hidx[(size_t)first]);
-    return GS_OK;
-}
-
-// R independent doSiteSampling runs (.fs:697-701), DESIGN.md §9.11.  Stage 1, chain after
-// chain on the context's single-chain state and stream, no host wait in between: starts
-// (seed r) -> snapshot of them -> device copies of positions, scores, replica aggregates
-// and the error words into slab r.  Stage 2: getBestPWMSsWithStartPositions of every
-// chain as one launch of the star site engine, workgroup r on slab r, every pass
-// in-kernel.  Stage 3: the shifted passes (-1 to completion, then +1), every running
-// chain in the same launches, one synchronisation per pass for all chains.  The caller
-// validated the arguments.
-static int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
-                      int32_t max_passes, int32_t *pos_out, double *score_out,
-                      int32_t *passes_out, int32_t *status_out) {
-    int rc;
-    const int64_t n = c->n_local;
-    if (n == 0) {
-        for (int32_t r = 0; r < R; ++r) {
-            if (passes_out) passes_out[3 * r] = passes_out[3 * r + 1] = passes_out[3 * r + 2] = 0;
-            if (status_out) status_out[r] = GS_OK;
-        }
-        return GS_OK;
-    }
-    if ((rc = ensure_state(c, W))) return rc;
-    GreedyArgs a{};
-    int waves = 0;
-    int64_t lds = 0;
-    if ((rc = greedy_carve(c, 1, pc, 0.0, max_passes, a, waves, lds))) return rc;
-    const int64_t agg_elems = (int64_t)kRepl * c->stride;
-    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
-    // per chain: positions, scores, shifted starts (and the shared draws), aggregates,
-    // Gauss–Seidel passes, error words, stage passes [3], pass control [3]
-    const int64_t bytes =
-        (int64_t)R * (n * (4 + 8 + 4 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 4 + 4 + 8 + 12 + 12) +
-        cpart_bytes;
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_site_sampling_batch: the chains' slabs take " + std::to_string(bytes) +
-                        " B, more than the " + std::to_string(kBatchBytesMax) +
-                        " B a batch may hold: split the seeds over several calls");
-    BatchBufs b;
-    HIP_TRY(c, hipMalloc(&b.pos, (size_t)(R * n) * 4));
-    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)(R * n) * 8));
-    HIP_TRY(c, hipMalloc(&b.shifted, (size_t)(R * n) * 4));
-    HIP_TRY(c, hipMalloc(&b.agg, (size_t)(R * agg_elems) * 8));
-    HIP_TRY(c, hipMalloc(&b.passes, (size_t)R * 4));
-    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 4));
-    HIP_TRY(c, hipMalloc(&b.erri, (size_t)R * 8));
-    HIP_TRY(c, hipMalloc(&b.stage_passes, (size_t)R * 12));
-    HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * 12));
-    int32_t *d_run = b.ctl, *d_moved = b.ctl + R, *d_left = b.ctl + 2 * (int64_t)R;
-    // the shifted scans' arguments: the chains' slabs, the D table in LDS
-    StartsArgs sa{};
-    int64_t slds = 0;
-    if ((rc = starts_pass(c, 2, W, pc, 0, b.shifted, nullptr, b.agg, b.pwms, b.pos, nullptr, &sa,
-                          &slds)))
-        return rc;
-    if (sa.dt_global)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_site_sampling_batch: the scan's D table of the longest sequence does "
-                    "not fit in LDS (loop gs_site_sampling)");
-    sa.err_code = b.err;
-    sa.err_index = b.erri;
-    const int scan_blocks =
-        (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)c->n_cu * 8 + R - 1) / R));
-    const int agg_blocks = (int)std::max<int64_t>(
-        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
-    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
-    if (mode == 0) {
-        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
-    } else {
-        HIP_TRY(c, hipMalloc(&b.starts, (size_t)(R * n) * 4));
-        hs.resize((size_t)(R * n));
-        for (int32_t r = 0; r < R; ++r)
-            for (int64_t i = 0; i < n; ++i)
-                hs[(size_t)(r * n + i)] =
-                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
-                                c->h_len[i] - W + 1);
-        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
-                                  c->stream));
-    }
-    hipEvent_t ev[4] = {get_event(c), get_event(c), get_event(c), get_event(c)};
-    auto recycle = [&]() {
-        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
-    };
-    std::vector<int32_t> left((size_t)R);
-    rc = [&]() -> int {
-        int rc2;
-        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-        for (int32_t r = 0; r < R; ++r) {
-            // (as motif_batch) the start vector the aggregate pass reads
-            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
-                return rc2;
-            // a target that raises (.fs:117) writes no start: every entry stays a valid one
-            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
-            // the acc of the refinements (site_upload): the starts, their aggregates
-            if ((rc2 = set_snapshot_dev(c, W, c->d_pos[1], false))) return rc2;
-            HIP_TRY(c, hipMemcpyAsync(b.pos + r * n, c->d_pos[0], (size_t)n * 4,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.pwms + r * n, c->d_pwms, (size_t)n * 8,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.agg + r * agg_elems, c->d_agg[c->cur_agg],
-                                      (size_t)agg_elems * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.err + r, c->d_err_code, 4, hipMemcpyDeviceToDevice,
-                                      c->stream));
-            HIP_TRY(c, hipMemcpyAsync(b.erri + r, c->d_err_index, 8, hipMemcpyDeviceToDevice,
-                                      c->stream));
-        }
-        // the context's own error words end clear, whatever the last chain's were
-        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(b.stage_passes, 0, (size_t)R * 12, c->stream));
-        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-        a.agg = b.agg;
-        a.pos = b.pos;
-        a.pwms = b.pwms;
-        a.passes_out = b.passes;
-        a.err_code = b.err;
-        a.err_index = b.erri;
-        a.exit_chunk = 0;
-        a.exit_out = nullptr;
-        HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
-        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-        const int32_t dirs[2] = {-1, 1};
-        for (int st = 0; st < 2; ++st) {
-            HIP_TRY(c, gs_site_batch_ctl_launch(R, 0, 1 + st, max_passes, d_run, d_moved, b.err,
-                                                b.stage_passes, d_left, c->stream));
-            for (int32_t pass = 1; pass <= max_passes; ++pass) {
-                HIP_TRY(c, hipMemsetAsync(b.agg, 0, (size_t)(R * agg_elems) * 8, c->stream));
-                HIP_TRY(c, gs_site_batch_pass_launch(sa, (size_t)slds, R, dirs[st], c->E, c->d_comp,
-                                                     d_run, d_moved, b.shifted, agg_blocks,
-                                                     scan_blocks, c->stream));
-                HIP_TRY(c, gs_site_batch_ctl_launch(R, pass, 1 + st, max_passes, d_run, d_moved,
-                                                    b.err, b.stage_passes, d_left, c->stream));
-                HIP_TRY(c, hipMemcpyAsync(left.data(), d_left, (size_t)R * 4, hipMemcpyDeviceToHost,
-                                          c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (std::all_of(left.begin(), left.end(), [](int32_t v) { return v == 0; })) break;
-            }
-        }
-        HIP_TRY(c, hipEventRecord(ev[3], c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }();
-    // the context's single-chain buffers were the chains' scratch: no snapshot is left
-    c->have_state = false;
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
-    c->ftab_agg = -1;
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
-        recycle();
-        return rc;
-    }
-    c->last_greedy_waves = waves;
-    for (int i = 0; i < 3; ++i) {
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-        c->site_batch_ms[i] = (double)ms;
-    }
-    recycle();
-    std::vector<int32_t> herr((size_t)R), hpass((size_t)R), hstage((size_t)R * 3);
-    std::vector<unsigned long long> hidx((size_t)R);
-    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hstage.data(), b.stage_passes, (size_t)R * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(score_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
-    int first = -1;
-    for (int32_t r = 0; r < R; ++r) {
-        if (passes_out) {
-            passes_out[3 * r] = hpass[(size_t)r];
-            passes_out[3 * r + 1] = hstage[(size_t)r * 3 + 1];
-            passes_out[3 * r + 2] = hstage[(size_t)r * 3 + 2];
-        }
-        if (status_out) status_out[r] = herr[(size_t)r];
-        if (herr[(size_t)r] != 0 && first < 0) first = r;
-    }
-    if (first >= 0)
-        return fail(c, herr[(size_t)first],
-                    std::string(device_error_message(herr[(size_t)first])) + " (chain " +
-                        std::to_string(first) + ")",
-                    (int64_t)hidx[(size_t)first]);
-    return GS_OK;
-}
-
-namespace {
-// Device slabs of one list-path batch call (row r = chain r), freed on scope exit.
-struct MultiBatchBufs {
-    int32_t *cnt[3] = {nullptr, nullptr, nullptr};  // starts as lists, sweep output, live
-    int32_t *pos[3] = {nullptr, nullptr, nullptr};
-    double *pwms[2] = {nullptr, nullptr};           // sweep output, live
-    int64_t *agg[2] = {nullptr, nullptr};           // of the starts, live
-    unsigned long long *err = nullptr;
-    uint64_t *seeds = nullptr;
-    SpecCtl *ctl = nullptr;
-    SpecRes *res = nullptr;
-    int32_t *ovf = nullptr, *pairs = nullptr, *chains = nullptr, *starts = nullptr, *cpart = nullptr;
-    ~MultiBatchBufs() {
-        for (auto &q : cnt) dfree(q);
-        for (auto &q : pos) dfree(q);
-        for (auto &q : pwms) dfree(q);
-        for (auto &q : agg) dfree(q);
-        dfree(err);
-        dfree(seeds);
-        dfree(ctl);
-        dfree(res);
-        dfree(ovf);
-        dfree(pairs);
-        dfree(chains);
-        dfree(starts);
-        dfree(cpart);
-    }
-};
-
-// Speculative slots per chain of the list batch's greedy: the GPU is
-// filled by chains first, so the width falls with R from multi_batch_fill (2) scoring
-// workgroups per CU in all, about what is resident at once; never more than the single
-// chain's width, and the arenas stay under kArenaBudget.
-int32_t multi_batch_slots(const gs_ctx *c, int64_t chains, int64_t slot_bytes) {
-    int64_t s = std::min<int64_t>(c->n_local, c->tune.multi_spec_slots);
-    s = std::min<int64_t>(s, ((int64_t)c->tune.multi_batch_fill * c->n_cu + chains - 1) / chains);
-    s = std::min<int64_t>(s, kArenaBudget / (chains * slot_bytes));
-    return (int32_t)std::max<int64_t>(1, s);
-}
-}  // namespace
-
-// R independent doMotifSampling runs with Positions lists (.fs:1034-1038, any
-// motifAmount), DESIGN.md §9.12.  Stage 1, chain after chain on the context's
-// single-chain state and stream, no host wait in between: starts (seed r) as the lists
-// of slab r.  Stage 2: the aggregates of every chain's starts and sweep 0 over the
-// (chain, target) pairs, one host wait per arena round for all chains.  Stage 3: the
-// greedy passes, speculative steps of two launches for all chains, one host wait per
-// kSpecBatch steps; chains whose arena overflowed start again from the kept sweep output
-// with a larger one.  One download.  The caller validated the arguments.
-static int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff,
-                       const uint64_t *seeds, int32_t R, int32_t mode, int32_t max_passes,
-                       int32_t cap, int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
-                       int32_t *passes_out, int32_t *status_out) {
-    int rc;
-    const int64_t n = c->n_local;
-    for (int i = 0; i < 3; ++i) c->multi_batch_ms[i] = 0.0;
-    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = 0;
-    if (n == 0) {
-        for (int32_t r = 0; r < R; ++r) {
-            if (passes_out) passes_out[r] = 0;
-            if (status_out) status_out[r] = GS_OK;
-        }
-        return GS_OK;
-    }
-    MultiArgs a{};
-    const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, true);
-    if ((rc = multi_lds_check(c, lds))) return rc;
-    if ((rc = ensure_state(c, W))) return rc;
-    const int32_t cells = c->A * W + c->A;
-    const int64_t sweep_arena = std::max<int64_t>(2048, 4 * (int64_t)a.kmax);
-    const int64_t greedy_arena = std::max<int64_t>(4096, 8 * (int64_t)a.kmax);
-    auto slot_bytes = [&](int64_t arena) { return (2 * (int64_t)a.kmax + 3 * arena) * 8; };
-    const int64_t sweep_grid0 = std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>((int64_t)R * n, (int64_t)c->n_cu * 8),
-                             kArenaBudget / slot_bytes(sweep_arena)));
-    if ((int64_t)R * slot_bytes(greedy_arena) > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_multi_batch: one arena per chain takes more than a batch "
-                    "may hold: split the seeds over several calls");
-    const int32_t slots0 = multi_batch_slots(c, R, slot_bytes(greedy_arena));
-    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
-    // per chain: three list slabs, two PWMS slabs, two aggregate rows, error word, seed,
-    // control block, chain index, speculation results; per pair: overflow and rescoring
-    // lists (and the shared draws); the first rounds' arenas
-    const int64_t bytes =
-        (int64_t)R * (n * (3 * (4 + 4 * (int64_t)cap) + 16 + 8 + (mode == 1 ? 4 : 0)) +
-                      (int64_t)cells * 16 + 8 + 8 + (int64_t)sizeof(SpecCtl) + 4 +
-                      (int64_t)slots0 * (int64_t)sizeof(SpecRes)) +
-        cpart_bytes +
-        std::max(sweep_grid0 * slot_bytes(sweep_arena), (int64_t)R * slots0 * slot_bytes(greedy_arena));
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_multi_batch: the chains' slabs take " + std::to_string(bytes) +
-                        " B, more than the " + std::to_string(kBatchBytesMax) +
-                        " B a batch may hold: split the seeds over several calls");
-    MultiBatchBufs b;
-    const int64_t rows = (int64_t)R * n;
-    for (auto &q : b.cnt) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 4));
-    for (auto &q : b.pos) HIP_TRY(c, hipMalloc(&q, (size_t)(rows * cap) * 4));
-    for (auto &q : b.pwms) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 8));
-    for (auto &q : b.agg) HIP_TRY(c, hipMalloc(&q, (size_t)R * cells * 8));
-    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 8));
-    HIP_TRY(c, hipMalloc(&b.seeds, (size_t)R * 8));
-    HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * sizeof(SpecCtl)));
-    HIP_TRY(c, hipMalloc(&b.res, (size_t)R * slots0 * sizeof(SpecRes)));
-    HIP_TRY(c, hipMalloc(&b.ovf, (size_t)(rows + 1) * 4));
-    HIP_TRY(c, hipMalloc(&b.pairs, (size_t)rows * 4));
-    HIP_TRY(c, hipMalloc(&b.chains, (size_t)R * 4));
-    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
-    if (mode == 0) {
-        HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
-    } else {
-        HIP_TRY(c, hipMalloc(&b.starts, (size_t)rows * 4));
-        hs.resize((size_t)rows);
-        for (int32_t r = 0; r < R; ++r)
-            for (int64_t i = 0; i < n; ++i)
-                hs[(size_t)(r * n + i)] =
-                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
-                                c->h_len[i] - W + 1);
-        HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
-                                  c->stream));
-    }
-    std::vector<int32_t> live((size_t)R);  // the chains of a greedy round
-    for (int32_t r = 0; r < R; ++r) live[(size_t)r] = r;
-    HIP_TRY(c, hipMemcpyAsync(b.seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(b.chains, live.data(), (size_t)R * 4, hipMemcpyHostToDevice,
-                              c->stream));
-    MultiBatchArgs ba{};
-    ba.n_chains = R;
-    ba.slots = slots0;
-    ba.cells = cells;
-    ba.chains = b.chains;
-    ba.seeds = b.seeds;
-    ba.err = b.err;
-    ba.ctl = b.ctl;
-    ba.res = b.res;
-    ba.ovf_count = b.ovf;
-    ba.ovf_list = b.ovf + 1;
-    a.u = nullptr;
-    a.stream = stream_sweep(0);
-    a.max_passes = max_passes;
-    a.targets = nullptr;
-    a.n_targets = 0;
-    const int agg_blocks = (int)std::max<int64_t>(
-        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
-    std::vector<SpecCtl> hctl((size_t)R);
-    std::vector<unsigned long long> herr((size_t)R);
-    int32_t info[4] = {0, 0, 0, slots0};
-    // chains whose categories pass kArenaMax: their word takes kMultiErrUnsupported
-    auto give_up = [&](const std::vector<int32_t> &chains) -> int {
-        for (int32_t r : chains) {
-            const unsigned long long w = ((unsigned long long)c->global_offset << 4) |
-                                         (unsigned long long)kMultiErrUnsupported;
-            HIP_TRY(c, hipMemcpyAsync(b.err + r, &w, 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-        return GS_OK;
-    };
-    hipEvent_t ev[4] = {get_event(c), get_event(c), get_event(c), get_event(c)};
-    auto recycle = [&]() {
-        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
-    };
-    rc = [&]() -> int {
-        int rc2;
-        // ---- stage 1: every chain's starts, as lists ----
-        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-        for (int32_t r = 0; r < R; ++r) {
-            // (as motif_batch) the start vector the aggregate pass reads
-            if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
-                return rc2;
-            // a target that raises (.fs:117) writes no start: every entry stays a valid one
-            HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
-            if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
-            HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, cap, b.cnt[0] + r * n,
-                                                   b.pos[0] + r * n * cap, c->d_err_code,
-                                                   c->d_err_index, b.err + r, b.ctl + r,
-                                                   c->stream));
-        }
-        // the context's own error words end clear, whatever the last chain's were
-        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
-        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-        // ---- stage 2: aggregates of the starts, sweep 0 of every chain ----
-        a.cnt_in = b.cnt[0];
-        a.pos_in = b.pos[0];
-        a.cnt_out = b.cnt[1];
-        a.pos_out = b.pos[1];
-        a.pwms_out = b.pwms[0];
-        a.agg = b.agg[0];
-        a.agg_rw = b.agg[1];
-        HIP_TRY(c, hipMemsetAsync(b.agg[0], 0, (size_t)R * cells * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(b.pos[1], 0xff, (size_t)(rows * cap) * 4, c->stream));
-        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[0], agg_blocks, c->stream));
-        ba.pairs = nullptr;
-        ba.n_pairs = rows;
-        for (int64_t arena = sweep_arena;;) {
-            int64_t grid = std::min<int64_t>(ba.n_pairs, (int64_t)c->n_cu * 8);
-            grid = std::max<int64_t>(1, std::min<int64_t>(grid, kArenaBudget / slot_bytes(arena)));
-            if ((rc2 = multi_scratch(c, a, grid, arena))) return rc2;
-            HIP_TRY(c, hipMemsetAsync(b.ovf, 0, 4, c->stream));
-            HIP_TRY(c, gs_multi_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
-            int32_t novf = 0;
-            HIP_TRY(c, hipMemcpyAsync(&novf, b.ovf, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (novf == 0) break;
-            if (arena * 16 > kArenaMax) {
-                std::vector<int32_t> pairs((size_t)novf), chains;
-                HIP_TRY(c, hipMemcpy(pairs.data(), b.ovf + 1, (size_t)novf * 4,
-                                     hipMemcpyDeviceToHost));
-                for (int32_t p : pairs) chains.push_back((int32_t)(p / n));
-                std::sort(chains.begin(), chains.end());
-                chains.erase(std::unique(chains.begin(), chains.end()), chains.end());
-                if ((rc2 = give_up(chains))) return rc2;
-                break;
-            }
-            arena *= 16;
-            ++info[0];
-            HIP_TRY(c, hipMemcpyAsync(b.pairs, b.ovf + 1, (size_t)novf * 4,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            ba.pairs = b.pairs;
-            ba.n_pairs = novf;
-        }
-        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-        // ---- stage 3: greedy passes from the sweep's lists (kept for restarts) ----
-        HIP_TRY(c, hipMemcpyAsync(b.cnt[2], b.cnt[1], (size_t)rows * 4, hipMemcpyDeviceToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemcpyAsync(b.pos[2], b.pos[1], (size_t)(rows * cap) * 4,
-                                  hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(b.pwms[1], b.pwms[0], (size_t)rows * 8, hipMemcpyDeviceToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemsetAsync(b.agg[1], 0, (size_t)R * cells * 8, c->stream));
-        HIP_TRY(c, gs_multi_batch_ctl_launch(ba, R, c->stream));
-        a.cnt_in = a.cnt_out = b.cnt[2];
-        a.pos_in = a.pos_out = b.pos[2];
-        a.pwms_out = b.pwms[1];
-        a.agg = b.agg[1];
-        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[1], agg_blocks, c->stream));
-        const int64_t step_limit = ((int64_t)n + 1) * max_passes + kSpecBatch;
-        std::vector<int32_t> next;
-        for (int64_t arena = greedy_arena;; arena *= 16) {
-            // the chains of this arena size, as many at a time as the arena budget holds
-            const int64_t group = std::max<int64_t>(1, kArenaBudget / slot_bytes(arena));
-            next.clear();
-            for (size_t g0 = 0; g0 < live.size(); g0 += (size_t)group) {
-                const int32_t ng = (int32_t)std::min<size_t>((size_t)group, live.size() - g0);
-                ba.n_chains = ng;
-                ba.slots = std::min(slots0, multi_batch_slots(c, ng, slot_bytes(arena)));
-                if (arena != greedy_arena || ng != R) {
-                    HIP_TRY(c, hipMemcpyAsync(b.chains, live.data() + g0, (size_t)ng * 4,
-                                              hipMemcpyHostToDevice, c->stream));
-                    if (arena != greedy_arena) {
-                        HIP_TRY(c, gs_multi_batch_restart_launch(ba, (int32_t)n, cap, b.cnt[1],
-                                                                 b.pos[1], b.pwms[0], b.cnt[2],
-                                                                 b.pos[2], b.pwms[1], b.agg[1],
-                                                                 c->stream));
-                        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b.agg[1], agg_blocks,
-                                                             c->stream));
-                    }
-                }
-                if ((rc2 = multi_scratch(c, a, (int64_t)ng * ba.slots, arena))) return rc2;
-                bool running = true;
-                for (int64_t steps = 0; running && steps <= step_limit; steps += kSpecBatch) {
-                    HIP_TRY(c, gs_multi_batch_spec_launch(a, ba, c->tune.multi_greedy_threads,
-                                                          (size_t)lds, kSpecBatch, c->stream));
-                    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b.ctl, (size_t)R * sizeof(SpecCtl),
-                                              hipMemcpyDeviceToHost, c->stream));
-                    HIP_TRY(c, hipStreamSynchronize(c->stream));
-                    running = false;
-                    for (int32_t i = 0; i < ng; ++i)
-                        running |= !hctl[(size_t)live[g0 + (size_t)i]].done;
-                }
-                if (running) return fail(c, GS_E_HIP, "list-path greedy made no progress");
-                HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost));
-                for (int32_t i = 0; i < ng; ++i) {
-                    const int32_t r = live[g0 + (size_t)i];
-                    if (herr[(size_t)r] != ~0ull && (int)(herr[(size_t)r] & 15ull) == kMultiErrArena)
-                        next.push_back(r);
-                }
-            }
-            if (next.empty()) break;
-            if (arena * 16 > kArenaMax) {
-                if ((rc2 = give_up(next))) return rc2;
-                break;
-            }
-            ++info[1];
-            info[2] += (int32_t)next.size();
-            live = next;
-        }
-        HIP_TRY(c, hipEventRecord(ev[3], c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }();
-    // the context's single-chain buffers were the chains' scratch: no snapshot is left
-    c->have_state = false;
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
-    c->ftab_agg = -1;
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
-        recycle();
-        return rc;
-    }
-    for (int i = 0; i < 3; ++i) {
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-        c->multi_batch_ms[i] = (double)ms;
-    }
-    recycle();
-    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = info[i];
-    // ---- stage 4: one download ----
-    HIP_TRY(c, hipMemcpyAsync(cnt_out, b.cnt[2], (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(pos_out, b.pos[2], (size_t)(rows * cap) * 4, hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipMemcpyAsync(pwms_out, b.pwms[1], (size_t)rows * 8, hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b.ctl, (size_t)R * sizeof(SpecCtl), hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipMemcpyAsync(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int first = -1, first_status = GS_OK;
-    for (int32_t r = 0; r < R; ++r) {
-        const unsigned long long e = herr[(size_t)r];
-        const int st = (int)(e & 15ull);
-        const int status = e == ~0ull                    ? GS_OK
-                           : st == 2                     ? GS_E_ROULETTE_OVERRUN
-                           : st == 3                     ? GS_E_OVERFLOW
-                           : st == kMultiErrUnsupported ? GS_E_UNSUPPORTED
-                                                         : GS_E_HIP;
-        if (passes_out) passes_out[r] = hctl[(size_t)r].pass;
-        if (status_out) status_out[r] = status;
-        if (status != GS_OK && first < 0) {
-            first = r;
-            first_status = status;
-        }
-    }
-    if (first >= 0)
-        return fail(c, first_status,
-                    std::string(first_status == GS_E_UNSUPPORTED
-                                    ? "a sequence has more than 2^28 motif combinations "
-                                      "(.fs:727-742)"
-                                    : device_error_message(first_status)) +
-                        " (chain " + std::to_string(first) + ")",
-                    (int64_t)(herr[(size_t)first] >> 4));
-    return GS_OK;
-}
-
-namespace {
-// Device slabs of one chain batch (row r = chain r), freed on scope exit.
-struct RunBatchBufs {
-    int32_t *pos[2] = {nullptr, nullptr};
-    double *pwms = nullptr, *u = nullptr;
-    int64_t *agg[3] = {nullptr, nullptr, nullptr};  // rows, then the chains' skip words
-    unsigned long long *err = nullptr;
-    uint64_t *seeds = nullptr;
-    SpecCtl *ctl = nullptr;
-    int32_t *cnt = nullptr, *starts = nullptr, *cpart = nullptr;
-    ~RunBatchBufs() {
-        for (auto &q : pos) dfree(q);
-        for (auto &q : agg) dfree(q);
-        dfree(pwms);
-        dfree(u);
-        dfree(err);
-        dfree(seeds);
-        dfree(ctl);
-        dfree(cnt);
-        dfree(starts);
-        dfree(cpart);
-    }
-};
-}  // namespace
-
-// R independent chains of T synchronous sweeps (motifAmount = 1), DESIGN.md §9.13.  Stage
-// 1: the chains' starts, uploaded rows (mode -1) or, chain after chain on the context's
-// single-chain state and stream as in multi_batch, those of getPWMOfRandomStarts; then the
-// aggregates of every chain's starts.  Stage 2: T launches of gs_run_batch_sweep_kernel
-// over the (chain, target) pairs back to back, positions double-buffered, the aggregate
-// rows rotating over three buffers (the next one zeroed by a memset before the sweep that
-// fills it, or by the sweep before: tune.run_batch_clear).  One synchronisation, one
-// download.  The caller validated the arguments.
-static int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T,
-                     const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode,
-                     const double *u, int32_t *pos_inout, double *pwms_out, int32_t *status_out) {
-    int rc;
-    const int64_t n = c->n_local;
-    c->run_batch_ms[0] = c->run_batch_ms[1] = 0.0;
-    if (status_out)
-        for (int32_t r = 0; r < R; ++r) status_out[r] = GS_OK;
-    if (n == 0) return GS_OK;
-    MultiArgs a{};
-    const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
-    if ((rc = multi_lds_check(c, lds))) return rc;
-    const int32_t cells = c->A * W + c->A;
-    const int64_t rows = (int64_t)R * n, agg_elems = (int64_t)R * cells + R;
-    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
-    const int64_t u_elems = u ? rows * T : 0;
-    int blocks = 0;
-    HIP_TRY(c, gs_run_batch_occupancy(&blocks, (size_t)lds));
-    blocks = std::max(1, std::min(blocks, c->tune.run_batch_blocks));
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)c->n_cu * blocks));
-    // per chain: two position rows, a PWMS row, three aggregate rows and skip words, error
-    // word, seed, control block (and the shared draws); the explicit uniforms; the window
-    // scores of a workgroup when they do not fit in LDS
-    const int64_t bytes = (int64_t)R * (n * (8 + 8 + (mode == 1 ? 4 : 0)) + 3 * 8 * ((int64_t)cells + 1) +
-                                        8 + 8 + (int64_t)sizeof(SpecCtl)) +
-                          n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax;
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_run_batch: the chains' slabs take " + std::to_string(bytes) +
-                        " B, more than the " + std::to_string(kBatchBytesMax) +
-                        " B a batch may hold: split the seeds over several calls");
-    if (mode >= 0 && (rc = ensure_state(c, W))) return rc;
-    if ((rc = multi_scratch(c, a, grid, 0))) return rc;
-    RunBatchBufs b;
-    for (auto &q : b.pos) HIP_TRY(c, hipMalloc(&q, (size_t)rows * 4));
-    for (auto &q : b.agg) HIP_TRY(c, hipMalloc(&q, (size_t)agg_elems * 8));
-    HIP_TRY(c, hipMalloc(&b.pwms, (size_t)rows * 8));
-    HIP_TRY(c, hipMalloc(&b.err, (size_t)R * 8));
-    HIP_TRY(c, hipMalloc(&b.seeds, (size_t)R * 8));
-    if (u_elems > 0) {
-        HIP_TRY(c, hipMalloc(&b.u, (size_t)u_elems * 8));
-        HIP_TRY(c, hipMemcpyAsync(b.u, u, (size_t)u_elems * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(c, hipMemcpyAsync(b.seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
-    for (auto &q : b.agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
-    std::vector<int32_t> hs;  // mode 1: every chain's shared draws, one upload
-    RunBatchArgs ba{};
-    ba.n_chains = R;
-    ba.cells = cells;
-    ba.seeds = b.seeds;
-    ba.err = b.err;
-    ba.n_pairs = rows;
-    ba.u_stride = (int64_t)T * n;
-    const bool clear_in_kernel = c->tune.run_batch_clear == 1;
-    const int agg_blocks = (int)std::max<int64_t>(
-        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
-    hipEvent_t ev[3] = {get_event(c), get_event(c), get_event(c)};
-    rc = [&]() -> int {
-        int rc2;
-        // ---- stage 1: every chain's starts and their aggregates ----
-        HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-        if (mode < 0) {
-            HIP_TRY(c, hipMemcpyAsync(b.pos[0], pos_inout, (size_t)rows * 4, hipMemcpyHostToDevice,
-                                      c->stream));
-            HIP_TRY(c, hipMemsetAsync(b.err, 0xff, (size_t)R * 8, c->stream));
-        } else {
-            HIP_TRY(c, hipMalloc(&b.cnt, (size_t)n * 4));
-            HIP_TRY(c, hipMalloc(&b.ctl, (size_t)R * sizeof(SpecCtl)));
-            if (mode == 0) {
-                HIP_TRY(c, hipMalloc(&b.cpart, (size_t)std::max<int64_t>(cpart_bytes, 4)));
-            } else {
-                HIP_TRY(c, hipMalloc(&b.starts, (size_t)rows * 4));
-                hs.resize((size_t)rows);
-                for (int32_t r = 0; r < R; ++r)
-                    for (int64_t i = 0; i < n; ++i)
-                        hs[(size_t)(r * n + i)] =
-                            uniform_int(seeds[r], stream_init_shared(),
-                                        (uint64_t)(c->global_offset + i), c->h_len[i] - W + 1);
-                HIP_TRY(c, hipMemcpyAsync(b.starts, hs.data(), hs.size() * 4, hipMemcpyHostToDevice,
-                                          c->stream));
-            }
-            for (int32_t r = 0; r < R; ++r) {
-                // (as multi_batch) the start vector the aggregate pass reads
-                if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, (size_t)n * 4, c->stream));
-                if ((rc2 = set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : b.starts + r * n, true)))
-                    return rc2;
-                // a target that raises (.fs:117) writes no start: every entry stays a valid one
-                HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, (size_t)n * 4, c->stream));
-                if ((rc2 = starts_enqueue(c, mode, W, pc, seeds[r], b.cpart))) return rc2;
-                // lists of capacity 1 are the position rows; a chain that raised keeps its word
-                HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, 1, b.cnt,
-                                                       b.pos[0] + r * n, c->d_err_code,
-                                                       c->d_err_index, b.err + r, b.ctl + r,
-                                                       c->stream));
-            }
-            // the context's own error words end clear, whatever the last chain's were
-            HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
-        }
-        ba.pos_in = b.pos[0];
-        ba.agg_out = b.agg[0];
-        HIP_TRY(c, gs_run_batch_agg_launch(a, ba, agg_blocks, c->stream));
-        HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-        // ---- stage 2: T sweeps of every chain, no host wait in between ----
-        for (int32_t t = 0; t < T; ++t) {
-            const int cur = t % 3, nxt = (t + 1) % 3, aft = (t + 2) % 3;
-            // buffer nxt is zero from the start (t < 2), from sweep t - 1, or from here
-            if (!clear_in_kernel && t >= 2)
-                HIP_TRY(c, hipMemsetAsync(b.agg[nxt], 0, (size_t)agg_elems * 8, c->stream));
-            ba.pos_in = b.pos[t & 1];
-            ba.pos_out = b.pos[(t + 1) & 1];
-            ba.pwms_out = t == T - 1 ? b.pwms : nullptr;
-            ba.agg_in = b.agg[cur];
-            ba.agg_out = b.agg[nxt];
-            ba.agg_clear = clear_in_kernel && t >= 1 ? b.agg[aft] : nullptr;
-            ba.u = b.u ? b.u + (int64_t)t * n : nullptr;
-            a.stream = stream_sweep((uint64_t)(first_sweep + t));
-            HIP_TRY(c, gs_run_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
-        }
-        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }();
-    if (mode >= 0) {
-        // the context's single-chain buffers were the chains' scratch: no snapshot is left
-        c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-        c->note_pending = false;
-        c->ftab_agg = -1;
-    }
-    c->have_state = false;
-    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing in flight on the slabs when they go
-    else
-        for (int i = 0; i < 2; ++i) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
-                c->run_batch_ms[i] = (double)ms;
-        }
-    for (hipEvent_t e : ev) c->ev_pool.push_back(e);
-    if (rc) return rc;
-    // ---- stage 3: one download ----
-    std::vector<unsigned long long> herr((size_t)R);
-    if (T > 0 || mode >= 0)
-        HIP_TRY(c, hipMemcpyAsync(pos_inout, b.pos[T & 1], (size_t)rows * 4, hipMemcpyDeviceToHost,
-                                  c->stream));
-    if (T > 0)
-        HIP_TRY(c, hipMemcpyAsync(pwms_out, b.pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
-                                  c->stream));
-    HIP_TRY(c, hipMemcpyAsync(herr.data(), b.err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int first = -1, first_status = GS_OK;
-    for (int32_t r = 0; r < R; ++r) {
-        const unsigned long long e = herr[(size_t)r];
-        const int st = (int)(e & 15ull);
-        const int status = e == ~0ull ? GS_OK
-                           : st == 2  ? GS_E_ROULETTE_OVERRUN
-                           : st == 3  ? GS_E_OVERFLOW
-                                      : GS_E_HIP;
-        if (status_out) status_out[r] = status;
-        if (status != GS_OK && first < 0) {
-            first = r;
-            first_status = status;
-        }
-    }
-    if (first >= 0)
-        return fail(c, first_status,
-                    std::string(device_error_message((int)(herr[(size_t)first] & 15ull))) +
-                        " (chain " + std::to_string(first) + ")",
-                    (int64_t)(herr[(size_t)first] >> 4));
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED, std::string(name) + ": " + why_one_device);
+    if (c->use_pcv || c->use_ppm)
+        return fail(c, GS_E_UNSUPPORTED, std::string(name) + ": " + twins_text);
     return GS_OK;
 }
 
@@ -1749,16 +679,13 @@ int gs_motif_sampling_batch(gs_ctx *c, int32_t W, double pc, double cutoff, cons
     if (!seeds || (c->n_local > 0 && (!pos_out || !pwms_out))) return GS_E_ARG;
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_batch: every chain walks all targets in order "
-                    "(.fs:885-929): it needs all sequences on one device and no communicator");
-    if (c->use_pcv || c->use_ppm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_batch: the ByPCV / OfPPM twins are not batched (clear "
-                    "the fixed PCV / PPM, or loop gs_motif_sampling)");
+    if ((rc = batch_entry_checks(
+             c, "gs_motif_sampling_batch", W,
+             "every chain walks all targets in order (.fs:885-929): it needs all sequences on "
+             "one device and no communicator",
+             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
+             "gs_motif_sampling)")))
+        return rc;
     takeover_reset(c);
     return motif_batch(c, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, pos_out,
                        pwms_out, passes_out, status_out);
@@ -2004,17 +931,13 @@ int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seed
     if (!seeds || (c->n_local > 0 && (!pos_out || !score_out))) return GS_E_ARG;
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_site_sampling_batch: getBestPWMSsWithStartPositions walks every target "
-                    "in order (.fs:554-585): it needs all sequences on one device and no "
-                    "communicator");
-    if (c->use_pcv || c->use_ppm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_site_sampling_batch: the WithBPV / OfPPM twins are not batched (clear "
-                    "the fixed PCV / PPM, or loop gs_site_sampling)");
+    if ((rc = batch_entry_checks(
+             c, "gs_site_sampling_batch", W,
+             "getBestPWMSsWithStartPositions walks every target in order (.fs:554-585): it "
+             "needs all sequences on one device and no communicator",
+             "the WithBPV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
+             "gs_site_sampling)")))
+        return rc;
     takeover_reset(c);
     return site_batch(c, W, pc, seeds, n_chains, init_mode, max_passes, pos_out, score_out,
                       passes_out, status_out);
@@ -2040,16 +963,13 @@ int gs_motif_sampling_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, do
     if (!seeds || (c->n_local > 0 && (!cnt_out || !pos_out || !pwms_out))) return GS_E_ARG;
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_multi_batch: every chain walks all targets in order "
-                    "(.fs:885-929): it needs all sequences on one device and no communicator");
-    if (c->use_pcv || c->use_ppm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_sampling_multi_batch: the ByPCV / OfPPM twins are not batched "
-                    "(clear the fixed PCV / PPM, or loop gs_motif_sampling_multi)");
+    if ((rc = batch_entry_checks(
+             c, "gs_motif_sampling_multi_batch", W,
+             "every chain walks all targets in order (.fs:885-929): it needs all sequences on "
+             "one device and no communicator",
+             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
+             "gs_motif_sampling_multi)")))
+        return rc;
     takeover_reset(c);
     return multi_batch(c, motif_amount, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, cap,
                        cnt_out, pos_out, pwms_out, passes_out, status_out);
@@ -2076,16 +996,13 @@ int gs_motif_run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_run_batch: a chain's aggregates are summed on one device: it needs "
-                    "all sequences there and no communicator");
-    if (c->use_pcv || c->use_ppm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_motif_run_batch: the ByPCV / OfPPM twins are not batched (clear the "
-                    "fixed PCV / PPM, or loop gs_motif_run)");
+    if ((rc = batch_entry_checks(
+             c, "gs_motif_run_batch", W,
+             "a chain's aggregates are summed on one device: it needs all sequences there and "
+             "no communicator",
+             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
+             "gs_motif_run)")))
+        return rc;
     if (init_mode == -1)
         for (int32_t r = 0; r < n_chains; ++r)
             if ((rc = validate_pos(c, W, pos_inout + (int64_t)r * c->n_local))) return rc;

@@ -1,0 +1,782 @@
+// gs_batch.cpp — the host drivers of the four batched entry points:
+// motif_batch (gs_motif_sampling_batch), site_batch (gs_site_sampling_batch), multi_batch
+// (gs_motif_sampling_multi_batch) and run_batch (gs_motif_run_batch), over one copy of the
+// stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they
+// reuse (set_snapshot_dev, starts_enqueue, greedy_carve, one_sweep) are in gs_engine.cpp.
+#include "gs_ctx.h"
+
+namespace gs_host {
+namespace {
+
+// One device allocation, freed on scope exit.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { dfree(p); }
+    int alloc(gs_ctx *c, int64_t elems) {
+        HIP_TRY(c, hipMalloc(&p, (size_t)elems * sizeof(T)));
+        return GS_OK;
+    }
+    operator T *() const { return p; }
+};
+// (a stage's status, handed on when it is not GS_OK)
+#define GS_TRY(x)                      \
+    do {                               \
+        if (int rc_ = (x)) return rc_; \
+    } while (0)
+
+// The boundaries of a call's N - 1 timed stages: pooled events, recorded on the stream in
+// order, back in the pool on every path.
+template <int N>
+struct StageEvents {
+    gs_ctx *c;
+    hipEvent_t ev[N];
+    int next = 0;
+    explicit StageEvents(gs_ctx *ctx) : c(ctx) {
+        for (hipEvent_t &e : ev) e = get_event(c);
+    }
+    StageEvents(const StageEvents &) = delete;
+    StageEvents &operator=(const StageEvents &) = delete;
+    ~StageEvents() {
+        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
+    }
+    hipError_t mark() { return hipEventRecord(ev[next++], c->stream); }
+    // After the stages (rc: their outcome, which is returned): a failed call synchronises,
+    // so that nothing is in flight on the slabs when they go; a good one (synchronised by
+    // its last stage) leaves the intervals in ms[N - 1], 0.0 where one cannot be read.
+    int finish(int rc, double *ms) {
+        if (rc) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+        for (int i = 0; i + 1 < N; ++i) {
+            float t = 0.0f;
+            ms[i] = hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess ? (double)t : 0.0;
+        }
+        return GS_OK;
+    }
+};
+
+// No target: every chain is done after no pass.
+int no_targets(int32_t R, int32_t *passes_out, int per_chain, int32_t *status_out) {
+    for (int32_t r = 0; r < R; ++r) {
+        for (int k = 0; passes_out && k < per_chain; ++k) passes_out[per_chain * r + k] = 0;
+        if (status_out) status_out[r] = GS_OK;
+    }
+    return GS_OK;
+}
+
+int batch_bytes_refuse(gs_ctx *c, const char *entry, int64_t bytes) {
+    if (bytes <= kBatchBytesMax) return GS_OK;
+    return fail(c, GS_E_UNSUPPORTED,
+                std::string(entry) + ": the chains' slabs take " + std::to_string(bytes) +
+                    " B, more than the " + std::to_string(kBatchBytesMax) +
+                    " B a batch may hold: split the seeds over several calls");
+}
+
+// Workgroups per chain of the batched aggregate passes: 256 targets each, the GPU four
+// deep over all chains.
+int agg_blocks(const gs_ctx *c, int64_t n, int32_t R) {
+    return (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 255) / 256, std::max<int64_t>(1, (int64_t)c->n_cu * 4 / R)));
+}
+
+// Mode 1: every chain's shared draws (row r: seed r), drawn on the host, one upload.  The
+// host copy lives as long as the device one (the upload reads pageable memory).
+struct SharedStarts {
+    DevBuf<int32_t> d;
+    std::vector<int32_t> h;
+    int draw(gs_ctx *c, int32_t W, const uint64_t *seeds, int32_t R) {
+        const int64_t n = c->n_local;
+        GS_TRY(d.alloc(c, R * n));
+        h.resize((size_t)(R * n));
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = 0; i < n; ++i)
+                h[(size_t)(r * n + i)] =
+                    uniform_int(seeds[r], stream_init_shared(), (uint64_t)(c->global_offset + i),
+                                c->h_len[i] - W + 1);
+        HIP_TRY(c, hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
+        return GS_OK;
+    }
+    const int32_t *row(gs_ctx *c, int32_t r) const { return d ? d + (int64_t)r * c->n_local : nullptr; }
+};
+
+// The starts of one chain on the context's single-chain state: the start vector the
+// aggregate pass reads (the shared draws d_starts_row, mode 1, or any valid one: mode 0
+// takes only the composition totals from it) -> snapshot -> getPWMOfRandomStarts into
+// d_pos[1], d_pwms.  The error words are reset first and keep what the chain raises.
+int chain_starts(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed,
+                 const int32_t *d_starts_row, int32_t *d_cpart) {
+    const size_t n = (size_t)c->n_local;
+    if (mode == 0) HIP_TRY(c, hipMemsetAsync(c->d_pos[0], 0, n * 4, c->stream));
+    GS_TRY(set_snapshot_dev(c, W, mode == 0 ? c->d_pos[0] : d_starts_row, true));
+    // a target that raises (.fs:117) writes no start: every entry stays a valid one
+    HIP_TRY(c, hipMemsetAsync(c->d_pos[1], 0, n * 4, c->stream));
+    return starts_enqueue(c, mode, W, pc, seed, d_cpart);
+}
+
+// The context's own error words end clear, whatever the last chain's were.
+int clear_ctx_error_words(gs_ctx *c) {
+    HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+    return GS_OK;
+}
+
+// The context's single-chain buffers were the chains' scratch: no snapshot is left.
+void scratch_used(gs_ctx *c) {
+    c->have_state = false;
+    takeover_reset(c);
+    c->ftab_agg = -1;
+}
+
+// The chains' status from their (code, index) error words: status_out[r], and the call
+// fails with the lowest failing chain's.
+int report_chain_errors(gs_ctx *c, const std::vector<int32_t> &code,
+                        const std::vector<unsigned long long> &index, int32_t *status_out) {
+    int first = -1;
+    for (size_t r = 0; r < code.size(); ++r) {
+        if (status_out) status_out[r] = code[r];
+        if (code[r] != 0 && first < 0) first = (int)r;
+    }
+    if (first < 0) return GS_OK;
+    return fail(c, code[(size_t)first],
+                std::string(device_error_message(code[(size_t)first])) + " (chain " +
+                    std::to_string(first) + ")",
+                (int64_t)index[(size_t)first]);
+}
+
+// The same from packed status words.  unsupported (nullable): the text of a chain given
+// up with kMultiErrUnsupported.
+int report_chain_errors(gs_ctx *c, const std::vector<unsigned long long> &word,
+                        int32_t *status_out, const char *unsupported) {
+    int first = -1, first_status = GS_OK;
+    for (size_t r = 0; r < word.size(); ++r) {
+        const bool given_up =
+            unsupported && word[r] != ~0ull && (int)(word[r] & 15ull) == kMultiErrUnsupported;
+        const int status = given_up ? GS_E_UNSUPPORTED : packed_status(word[r]);
+        if (status_out) status_out[r] = status;
+        if (status != GS_OK && first < 0) {
+            first = (int)r;
+            first_status = status;
+        }
+    }
+    if (first < 0) return GS_OK;
+    return fail(c, first_status,
+                std::string(first_status == GS_E_UNSUPPORTED ? unsupported
+                                                             : device_error_message(first_status)) +
+                    " (chain " + std::to_string(first) + ")",
+                (int64_t)(word[(size_t)first] >> 4));
+}
+
+// The slabs of the star greedy batches (row r = chain r) and what both drivers do with
+// them: the chain just prepared on the context -> slab r; one launch for all chains.
+struct StarSlabs {
+    DevBuf<int32_t> pos, passes, err;
+    DevBuf<double> pwms;
+    DevBuf<int64_t> agg;
+    DevBuf<unsigned long long> erri;
+    int64_t n = 0, agg_elems = 0;
+    int alloc(gs_ctx *c, int32_t R) {
+        n = c->n_local;
+        agg_elems = (int64_t)kRepl * c->stride;
+        GS_TRY(pos.alloc(c, R * n));
+        GS_TRY(pwms.alloc(c, R * n));
+        GS_TRY(agg.alloc(c, R * agg_elems));
+        GS_TRY(passes.alloc(c, R));
+        GS_TRY(err.alloc(c, R));
+        return erri.alloc(c, R);
+    }
+    int take_chain(gs_ctx *c, int32_t r) {
+        HIP_TRY(c, hipMemcpyAsync(pos + r * n, c->d_pos[c->cur_pos], (size_t)n * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(pwms + r * n, c->d_pwms, (size_t)n * 8, hipMemcpyDeviceToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(agg + r * agg_elems, c->d_agg[c->cur_agg], (size_t)agg_elems * 8,
+                                  hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(err + r, c->d_err_code, 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(erri + r, c->d_err_index, 8, hipMemcpyDeviceToDevice, c->stream));
+        return GS_OK;
+    }
+    int launch(gs_ctx *c, GreedyArgs &a, int32_t R, int waves, int64_t lds) {
+        a.agg = agg;
+        a.pos = pos;
+        a.pwms = pwms;
+        a.passes_out = passes;
+        a.err_code = err;
+        a.err_index = erri;
+        a.exit_chunk = 0;
+        a.exit_out = nullptr;
+        HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
+        return GS_OK;
+    }
+};
+
+// Speculative slots per chain of the list batch's greedy: the GPU is
+// filled by chains first, so the width falls with R from multi_batch_fill (2) scoring
+// workgroups per CU in all, about what is resident at once; never more than the single
+// chain's width, and the arenas stay under kArenaBudget.
+int32_t multi_batch_slots(const gs_ctx *c, int64_t chains, int64_t slot_bytes) {
+    int64_t s = std::min<int64_t>(c->n_local, c->tune.multi_spec_slots);
+    s = std::min<int64_t>(s, ((int64_t)c->tune.multi_batch_fill * c->n_cu + chains - 1) / chains);
+    s = std::min<int64_t>(s, kArenaBudget / (chains * slot_bytes));
+    return (int32_t)std::max<int64_t>(1, s);
+}
+
+}  // namespace
+
+// R independent doMotifSampling runs (.fs:1034-1038, motifAmount = 1).  Stage 1, chain
+// after chain on the context's single-chain state and stream, no host wait in between:
+// starts (seed r) -> snapshot of them -> sweep 0 of seed r -> device copies of positions,
+// PWMS, replica aggregates and the error words into slab r.  Stage 2: one launch of
+// gs_greedy_batch_kernel, workgroup r on slab r, every pass in-kernel.  One
+// synchronisation, then the slabs come down.  The caller validated the arguments.
+int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds, int32_t R,
+                int32_t mode, int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                int32_t *passes_out, int32_t *status_out) {
+    const int64_t n = c->n_local;
+    if (n == 0) return no_targets(R, passes_out, 1, status_out);
+    GS_TRY(ensure_state(c, W));
+    GreedyArgs a{};
+    int waves = 0;
+    int64_t lds = 0;
+    GS_TRY(greedy_carve(c, 0, pc, cutoff, max_passes, a, waves, lds));
+    const int64_t agg_elems = (int64_t)kRepl * c->stride;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_motif_sampling_batch",
+        (int64_t)R * (n * (4 + 8 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 16) + cpart_bytes));
+    StarSlabs b;
+    GS_TRY(b.alloc(c, R));
+    DevBuf<int32_t> cpart;
+    SharedStarts starts;
+    if (mode == 0)
+        GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
+    else
+        GS_TRY(starts.draw(c, W, seeds, R));
+    StageEvents<3> ev(c);
+    int rc = [&]() -> int {
+        HIP_TRY(c, ev.mark());
+        for (int32_t r = 0; r < R; ++r) {
+            GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+            // its error word stays set: the sweep skips, the chain's slab carries it
+            GS_TRY(set_snapshot_dev(c, W, c->d_pos[1], false));
+            if (use_dna(c)) {  // (as gs_run_sweeps: the device sweep counter at sweep 0)
+                GS_TRY(need_vec(c));
+                HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, 0ull, c->d_done_ctr, c->stream));
+            }
+            GS_TRY(one_sweep(c, pc, cutoff, nullptr, seeds[r], stream_sweep(0), true));
+            GS_TRY(need_rep(c));
+            GS_TRY(b.take_chain(c, r));
+        }
+        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
+        HIP_TRY(c, ev.mark());
+        GS_TRY(b.launch(c, a, R, waves, lds));
+        HIP_TRY(c, ev.mark());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    scratch_used(c);
+    GS_TRY(ev.finish(rc, c->batch_ms));
+    c->last_greedy_waves = waves;
+    std::vector<int32_t> herr((size_t)R), hpass((size_t)R);
+    std::vector<unsigned long long> hidx((size_t)R);
+    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pwms_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
+    if (passes_out) std::copy(hpass.begin(), hpass.end(), passes_out);
+    return report_chain_errors(c, herr, hidx, status_out);
+}
+
+// R independent doSiteSampling runs (.fs:697-701), DESIGN.md §9.11.  Stage 1, chain after
+// chain on the context's single-chain state and stream, no host wait in between: starts
+// (seed r) -> snapshot of them -> device copies of positions, scores, replica aggregates
+// and the error words into slab r.  Stage 2: getBestPWMSsWithStartPositions of every
+// chain as one launch of the star site engine, workgroup r on slab r, every pass
+// in-kernel.  Stage 3: the shifted passes (-1 to completion, then +1), every running
+// chain in the same launches, one synchronisation per pass for all chains.  The caller
+// validated the arguments.
+int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
+               int32_t max_passes, int32_t *pos_out, double *score_out, int32_t *passes_out,
+               int32_t *status_out) {
+    const int64_t n = c->n_local;
+    if (n == 0) return no_targets(R, passes_out, 3, status_out);
+    GS_TRY(ensure_state(c, W));
+    GreedyArgs a{};
+    int waves = 0;
+    int64_t lds = 0;
+    GS_TRY(greedy_carve(c, 1, pc, 0.0, max_passes, a, waves, lds));
+    const int64_t agg_elems = (int64_t)kRepl * c->stride;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    // per chain: positions, scores, shifted starts (and the shared draws), aggregates,
+    // Gauss–Seidel passes, error words, stage passes [3], pass control [3]
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_site_sampling_batch",
+        (int64_t)R * (n * (4 + 8 + 4 + (mode == 1 ? 4 : 0)) + agg_elems * 8 + 4 + 4 + 8 + 12 + 12) +
+            cpart_bytes));
+    StarSlabs b;
+    GS_TRY(b.alloc(c, R));
+    // the shifted passes: start vectors, stage pass counts [R][3], pass control [3][R]
+    DevBuf<int32_t> shifted, stage_passes, ctl;
+    GS_TRY(shifted.alloc(c, R * n));
+    GS_TRY(stage_passes.alloc(c, (int64_t)R * 3));
+    GS_TRY(ctl.alloc(c, (int64_t)R * 3));
+    int32_t *d_run = ctl, *d_moved = ctl + R, *d_left = ctl + 2 * (int64_t)R;
+    // the shifted scans' arguments: the chains' slabs, the D table in LDS
+    StartsArgs sa{};
+    int64_t slds = 0;
+    GS_TRY(starts_pass(c, 2, W, pc, 0, shifted, nullptr, b.agg, b.pwms, b.pos, nullptr, &sa, &slds));
+    if (sa.dt_global)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_site_sampling_batch: the scan's D table of the longest sequence does "
+                    "not fit in LDS (loop gs_site_sampling)");
+    sa.err_code = b.err;
+    sa.err_index = b.erri;
+    const int scan_blocks =
+        (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)c->n_cu * 8 + R - 1) / R));
+    const int ablocks = agg_blocks(c, n, R);
+    DevBuf<int32_t> cpart;
+    SharedStarts starts;
+    if (mode == 0)
+        GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
+    else
+        GS_TRY(starts.draw(c, W, seeds, R));
+    StageEvents<4> ev(c);
+    std::vector<int32_t> left((size_t)R);
+    int rc = [&]() -> int {
+        HIP_TRY(c, ev.mark());
+        for (int32_t r = 0; r < R; ++r) {
+            GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+            // the acc of the refinements (site_upload): the starts, their aggregates
+            GS_TRY(set_snapshot_dev(c, W, c->d_pos[1], false));
+            GS_TRY(b.take_chain(c, r));
+        }
+        GS_TRY(clear_ctx_error_words(c));
+        HIP_TRY(c, hipMemsetAsync(b.passes, 0, (size_t)R * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(stage_passes, 0, (size_t)R * 12, c->stream));
+        HIP_TRY(c, ev.mark());
+        GS_TRY(b.launch(c, a, R, waves, lds));
+        HIP_TRY(c, ev.mark());
+        const int32_t dirs[2] = {-1, 1};
+        for (int st = 0; st < 2; ++st) {
+            HIP_TRY(c, gs_site_batch_ctl_launch(R, 0, 1 + st, max_passes, d_run, d_moved, b.err,
+                                                stage_passes, d_left, c->stream));
+            for (int32_t pass = 1; pass <= max_passes; ++pass) {
+                HIP_TRY(c, hipMemsetAsync(b.agg, 0, (size_t)(R * agg_elems) * 8, c->stream));
+                HIP_TRY(c, gs_site_batch_pass_launch(sa, (size_t)slds, R, dirs[st], c->E, c->d_comp,
+                                                     d_run, d_moved, shifted, ablocks, scan_blocks,
+                                                     c->stream));
+                HIP_TRY(c, gs_site_batch_ctl_launch(R, pass, 1 + st, max_passes, d_run, d_moved,
+                                                    b.err, stage_passes, d_left, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(left.data(), d_left, (size_t)R * 4, hipMemcpyDeviceToHost,
+                                          c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                if (std::all_of(left.begin(), left.end(), [](int32_t v) { return v == 0; })) break;
+            }
+        }
+        HIP_TRY(c, ev.mark());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    scratch_used(c);
+    GS_TRY(ev.finish(rc, c->site_batch_ms));
+    c->last_greedy_waves = waves;
+    std::vector<int32_t> herr((size_t)R), hpass((size_t)R), hstage((size_t)R * 3);
+    std::vector<unsigned long long> hidx((size_t)R);
+    HIP_TRY(c, hipMemcpy(herr.data(), b.err, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hidx.data(), b.erri, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hpass.data(), b.passes, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hstage.data(), stage_passes, (size_t)R * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pos_out, b.pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(score_out, b.pwms, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
+    for (int32_t r = 0; passes_out && r < R; ++r) {
+        passes_out[3 * r] = hpass[(size_t)r];
+        passes_out[3 * r + 1] = hstage[(size_t)r * 3 + 1];
+        passes_out[3 * r + 2] = hstage[(size_t)r * 3 + 2];
+    }
+    return report_chain_errors(c, herr, hidx, status_out);
+}
+
+// R independent doMotifSampling runs with Positions lists (.fs:1034-1038, any
+// motifAmount), DESIGN.md §9.12.  Stage 1, chain after chain on the context's
+// single-chain state and stream, no host wait in between: starts (seed r) as the lists
+// of slab r.  Stage 2: the aggregates of every chain's starts and sweep 0 over the
+// (chain, target) pairs, one host wait per arena round for all chains.  Stage 3: the
+// greedy passes, speculative steps of two launches for all chains, one host wait per
+// kSpecBatch steps; chains whose arena overflowed start again from the kept sweep output
+// with a larger one.  One download.  The caller validated the arguments.
+int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const uint64_t *seeds,
+                int32_t R, int32_t mode, int32_t max_passes, int32_t cap, int32_t *cnt_out,
+                int32_t *pos_out, double *pwms_out, int32_t *passes_out, int32_t *status_out) {
+    const int64_t n = c->n_local;
+    for (int i = 0; i < 3; ++i) c->multi_batch_ms[i] = 0.0;
+    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = 0;
+    if (n == 0) return no_targets(R, passes_out, 1, status_out);
+    MultiArgs a{};
+    const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, true);
+    GS_TRY(multi_lds_check(c, lds));
+    GS_TRY(ensure_state(c, W));
+    const int32_t cells = c->A * W + c->A;
+    const int64_t sweep_arena = std::max<int64_t>(2048, 4 * (int64_t)a.kmax);
+    const int64_t greedy_arena = std::max<int64_t>(4096, 8 * (int64_t)a.kmax);
+    auto slot_bytes = [&](int64_t arena) { return (2 * (int64_t)a.kmax + 3 * arena) * 8; };
+    const int64_t sweep_grid0 = std::max<int64_t>(
+        1, std::min<int64_t>(std::min<int64_t>((int64_t)R * n, (int64_t)c->n_cu * 8),
+                             kArenaBudget / slot_bytes(sweep_arena)));
+    if ((int64_t)R * slot_bytes(greedy_arena) > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_motif_sampling_multi_batch: one arena per chain takes more than a batch "
+                    "may hold: split the seeds over several calls");
+    const int32_t slots0 = multi_batch_slots(c, R, slot_bytes(greedy_arena));
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    // per chain: three list slabs, two PWMS slabs, two aggregate rows, error word, seed,
+    // control block, chain index, speculation results; per pair: overflow and rescoring
+    // lists (and the shared draws); the first rounds' arenas
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_motif_sampling_multi_batch",
+        (int64_t)R * (n * (3 * (4 + 4 * (int64_t)cap) + 16 + 8 + (mode == 1 ? 4 : 0)) +
+                      (int64_t)cells * 16 + 8 + 8 + (int64_t)sizeof(SpecCtl) + 4 +
+                      (int64_t)slots0 * (int64_t)sizeof(SpecRes)) +
+            cpart_bytes +
+            std::max(sweep_grid0 * slot_bytes(sweep_arena),
+                     (int64_t)R * slots0 * slot_bytes(greedy_arena))));
+    // the slabs (row r = chain r)
+    DevBuf<int32_t> b_cnt[3], b_pos[3];  // starts as lists, sweep output, live
+    DevBuf<double> b_pwms[2];            // sweep output, live
+    DevBuf<int64_t> b_agg[2];            // of the starts, live
+    DevBuf<unsigned long long> b_err;
+    DevBuf<uint64_t> b_seeds;
+    DevBuf<SpecCtl> b_ctl;
+    DevBuf<SpecRes> b_res;
+    DevBuf<int32_t> b_ovf, b_pairs, b_chains, cpart;
+    SharedStarts starts;
+    const int64_t rows = (int64_t)R * n;
+    for (auto &q : b_cnt) GS_TRY(q.alloc(c, rows));
+    for (auto &q : b_pos) GS_TRY(q.alloc(c, rows * cap));
+    for (auto &q : b_pwms) GS_TRY(q.alloc(c, rows));
+    for (auto &q : b_agg) GS_TRY(q.alloc(c, (int64_t)R * cells));
+    GS_TRY(b_err.alloc(c, R));
+    GS_TRY(b_seeds.alloc(c, R));
+    GS_TRY(b_ctl.alloc(c, R));
+    GS_TRY(b_res.alloc(c, (int64_t)R * slots0));
+    GS_TRY(b_ovf.alloc(c, rows + 1));
+    GS_TRY(b_pairs.alloc(c, rows));
+    GS_TRY(b_chains.alloc(c, R));
+    if (mode == 0)
+        GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
+    else
+        GS_TRY(starts.draw(c, W, seeds, R));
+    std::vector<int32_t> live((size_t)R);  // the chains of a greedy round
+    for (int32_t r = 0; r < R; ++r) live[(size_t)r] = r;
+    HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(b_chains, live.data(), (size_t)R * 4, hipMemcpyHostToDevice,
+                              c->stream));
+    MultiBatchArgs ba{};
+    ba.n_chains = R;
+    ba.slots = slots0;
+    ba.cells = cells;
+    ba.chains = b_chains;
+    ba.seeds = b_seeds;
+    ba.err = b_err;
+    ba.ctl = b_ctl;
+    ba.res = b_res;
+    ba.ovf_count = b_ovf;
+    ba.ovf_list = b_ovf + 1;
+    a.u = nullptr;
+    a.stream = stream_sweep(0);
+    a.max_passes = max_passes;
+    a.targets = nullptr;
+    a.n_targets = 0;
+    const int ablocks = agg_blocks(c, n, R);
+    std::vector<SpecCtl> hctl((size_t)R);
+    std::vector<unsigned long long> herr((size_t)R);
+    int32_t info[4] = {0, 0, 0, slots0};
+    // chains whose categories pass kArenaMax: their word takes kMultiErrUnsupported
+    auto give_up = [&](const std::vector<int32_t> &chains) -> int {
+        for (int32_t r : chains) {
+            const unsigned long long w = ((unsigned long long)c->global_offset << 4) |
+                                         (unsigned long long)kMultiErrUnsupported;
+            HIP_TRY(c, hipMemcpyAsync(b_err + r, &w, 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        return GS_OK;
+    };
+    StageEvents<4> ev(c);
+    int rc = [&]() -> int {
+        // ---- stage 1: every chain's starts, as lists ----
+        HIP_TRY(c, ev.mark());
+        for (int32_t r = 0; r < R; ++r) {
+            GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+            HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, cap, b_cnt[0] + r * n,
+                                                   b_pos[0] + r * n * cap, c->d_err_code,
+                                                   c->d_err_index, b_err + r, b_ctl + r,
+                                                   c->stream));
+        }
+        GS_TRY(clear_ctx_error_words(c));
+        HIP_TRY(c, ev.mark());
+        // ---- stage 2: aggregates of the starts, sweep 0 of every chain ----
+        a.cnt_in = b_cnt[0];
+        a.pos_in = b_pos[0];
+        a.cnt_out = b_cnt[1];
+        a.pos_out = b_pos[1];
+        a.pwms_out = b_pwms[0];
+        a.agg = b_agg[0];
+        a.agg_rw = b_agg[1];
+        HIP_TRY(c, hipMemsetAsync(b_agg[0], 0, (size_t)R * cells * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(b_pos[1], 0xff, (size_t)(rows * cap) * 4, c->stream));
+        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b_agg[0], ablocks, c->stream));
+        ba.pairs = nullptr;
+        ba.n_pairs = rows;
+        for (int64_t arena = sweep_arena;;) {
+            int64_t grid = std::min<int64_t>(ba.n_pairs, (int64_t)c->n_cu * 8);
+            grid = std::max<int64_t>(1, std::min<int64_t>(grid, kArenaBudget / slot_bytes(arena)));
+            GS_TRY(multi_scratch(c, a, grid, arena));
+            HIP_TRY(c, hipMemsetAsync(b_ovf, 0, 4, c->stream));
+            HIP_TRY(c, gs_multi_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
+            int32_t novf = 0;
+            HIP_TRY(c, hipMemcpyAsync(&novf, b_ovf, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (novf == 0) break;
+            if (arena * 16 > kArenaMax) {
+                std::vector<int32_t> pairs((size_t)novf), chains;
+                HIP_TRY(c, hipMemcpy(pairs.data(), b_ovf + 1, (size_t)novf * 4,
+                                     hipMemcpyDeviceToHost));
+                for (int32_t p : pairs) chains.push_back((int32_t)(p / n));
+                std::sort(chains.begin(), chains.end());
+                chains.erase(std::unique(chains.begin(), chains.end()), chains.end());
+                GS_TRY(give_up(chains));
+                break;
+            }
+            arena *= 16;
+            ++info[0];
+            HIP_TRY(c, hipMemcpyAsync(b_pairs, b_ovf + 1, (size_t)novf * 4, hipMemcpyDeviceToDevice,
+                                      c->stream));
+            ba.pairs = b_pairs;
+            ba.n_pairs = novf;
+        }
+        HIP_TRY(c, ev.mark());
+        // ---- stage 3: greedy passes from the sweep's lists (kept for restarts) ----
+        HIP_TRY(c, hipMemcpyAsync(b_cnt[2], b_cnt[1], (size_t)rows * 4, hipMemcpyDeviceToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(b_pos[2], b_pos[1], (size_t)(rows * cap) * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(b_pwms[1], b_pwms[0], (size_t)rows * 8, hipMemcpyDeviceToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(b_agg[1], 0, (size_t)R * cells * 8, c->stream));
+        HIP_TRY(c, gs_multi_batch_ctl_launch(ba, R, c->stream));
+        a.cnt_in = a.cnt_out = b_cnt[2];
+        a.pos_in = a.pos_out = b_pos[2];
+        a.pwms_out = b_pwms[1];
+        a.agg = b_agg[1];
+        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b_agg[1], ablocks, c->stream));
+        const int64_t step_limit = ((int64_t)n + 1) * max_passes + kSpecBatch;
+        std::vector<int32_t> next;
+        for (int64_t arena = greedy_arena;; arena *= 16) {
+            // the chains of this arena size, as many at a time as the arena budget holds
+            const int64_t group = std::max<int64_t>(1, kArenaBudget / slot_bytes(arena));
+            next.clear();
+            for (size_t g0 = 0; g0 < live.size(); g0 += (size_t)group) {
+                const int32_t ng = (int32_t)std::min<size_t>((size_t)group, live.size() - g0);
+                ba.n_chains = ng;
+                ba.slots = std::min(slots0, multi_batch_slots(c, ng, slot_bytes(arena)));
+                if (arena != greedy_arena || ng != R) {
+                    HIP_TRY(c, hipMemcpyAsync(b_chains, live.data() + g0, (size_t)ng * 4,
+                                              hipMemcpyHostToDevice, c->stream));
+                    if (arena != greedy_arena) {
+                        HIP_TRY(c, gs_multi_batch_restart_launch(ba, (int32_t)n, cap, b_cnt[1],
+                                                                 b_pos[1], b_pwms[0], b_cnt[2],
+                                                                 b_pos[2], b_pwms[1], b_agg[1],
+                                                                 c->stream));
+                        HIP_TRY(c, gs_multi_batch_agg_launch(a, ba, b_agg[1], ablocks, c->stream));
+                    }
+                }
+                GS_TRY(multi_scratch(c, a, (int64_t)ng * ba.slots, arena));
+                bool running = true;
+                for (int64_t steps = 0; running && steps <= step_limit; steps += kSpecBatch) {
+                    HIP_TRY(c, gs_multi_batch_spec_launch(a, ba, c->tune.multi_greedy_threads,
+                                                          (size_t)lds, kSpecBatch, c->stream));
+                    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b_ctl, (size_t)R * sizeof(SpecCtl),
+                                              hipMemcpyDeviceToHost, c->stream));
+                    HIP_TRY(c, hipStreamSynchronize(c->stream));
+                    running = false;
+                    for (int32_t i = 0; i < ng; ++i)
+                        running |= !hctl[(size_t)live[g0 + (size_t)i]].done;
+                }
+                if (running) return fail(c, GS_E_HIP, "list-path greedy made no progress");
+                HIP_TRY(c, hipMemcpy(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost));
+                for (int32_t i = 0; i < ng; ++i) {
+                    const int32_t r = live[g0 + (size_t)i];
+                    if (herr[(size_t)r] != ~0ull && (int)(herr[(size_t)r] & 15ull) == kMultiErrArena)
+                        next.push_back(r);
+                }
+            }
+            if (next.empty()) break;
+            if (arena * 16 > kArenaMax) {
+                GS_TRY(give_up(next));
+                break;
+            }
+            ++info[1];
+            info[2] += (int32_t)next.size();
+            live = next;
+        }
+        HIP_TRY(c, ev.mark());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    scratch_used(c);
+    GS_TRY(ev.finish(rc, c->multi_batch_ms));
+    for (int i = 0; i < 4; ++i) c->multi_batch_info[i] = info[i];
+    // ---- stage 4: one download ----
+    HIP_TRY(c, hipMemcpyAsync(cnt_out, b_cnt[2], (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pos_out, b_pos[2], (size_t)(rows * cap) * 4, hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms[1], (size_t)rows * 8, hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hctl.data(), b_ctl, (size_t)R * sizeof(SpecCtl), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int32_t r = 0; passes_out && r < R; ++r) passes_out[r] = hctl[(size_t)r].pass;
+    return report_chain_errors(c, herr, status_out,
+                               "a sequence has more than 2^28 motif combinations (.fs:727-742)");
+}
+
+// R independent chains of T synchronous sweeps (motifAmount = 1), DESIGN.md §9.13.  Stage
+// 1: the chains' starts, uploaded rows (mode -1) or, chain after chain on the context's
+// single-chain state and stream as in multi_batch, those of getPWMOfRandomStarts; then the
+// aggregates of every chain's starts.  Stage 2: T launches of gs_run_batch_sweep_kernel
+// over the (chain, target) pairs back to back, positions double-buffered, the aggregate
+// rows rotating over three buffers (the next one zeroed by a memset before the sweep that
+// fills it, or by the sweep before: tune.run_batch_clear).  One synchronisation, one
+// download.  The caller validated the arguments.
+int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
+              int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
+              double *pwms_out, int32_t *status_out) {
+    const int64_t n = c->n_local;
+    c->run_batch_ms[0] = c->run_batch_ms[1] = 0.0;
+    if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
+    if (n == 0) return GS_OK;
+    MultiArgs a{};
+    const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
+    GS_TRY(multi_lds_check(c, lds));
+    const int32_t cells = c->A * W + c->A;
+    const int64_t rows = (int64_t)R * n, agg_elems = (int64_t)R * cells + R;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    const int64_t u_elems = u ? rows * T : 0;
+    int blocks = 0;
+    HIP_TRY(c, gs_run_batch_occupancy(&blocks, (size_t)lds));
+    blocks = std::max(1, std::min(blocks, c->tune.run_batch_blocks));
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)c->n_cu * blocks));
+    // per chain: two position rows, a PWMS row, three aggregate rows and skip words, error
+    // word, seed, control block (and the shared draws); the explicit uniforms; the window
+    // scores of a workgroup when they do not fit in LDS
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_motif_run_batch",
+        (int64_t)R * (n * (8 + 8 + (mode == 1 ? 4 : 0)) + 3 * 8 * ((int64_t)cells + 1) + 8 + 8 +
+                      (int64_t)sizeof(SpecCtl)) +
+            n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax));
+    if (mode >= 0) GS_TRY(ensure_state(c, W));
+    GS_TRY(multi_scratch(c, a, grid, 0));
+    // the slabs (row r = chain r)
+    DevBuf<int32_t> b_pos[2];
+    DevBuf<int64_t> b_agg[3];  // rows, then the chains' skip words
+    DevBuf<double> b_pwms, b_u;
+    DevBuf<unsigned long long> b_err;
+    DevBuf<uint64_t> b_seeds;
+    DevBuf<SpecCtl> b_ctl;
+    DevBuf<int32_t> b_cnt, cpart;
+    SharedStarts starts;
+    for (auto &q : b_pos) GS_TRY(q.alloc(c, rows));
+    for (auto &q : b_agg) GS_TRY(q.alloc(c, agg_elems));
+    GS_TRY(b_pwms.alloc(c, rows));
+    GS_TRY(b_err.alloc(c, R));
+    GS_TRY(b_seeds.alloc(c, R));
+    if (u_elems > 0) {
+        GS_TRY(b_u.alloc(c, u_elems));
+        HIP_TRY(c, hipMemcpyAsync(b_u, u, (size_t)u_elems * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+    for (auto &q : b_agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
+    RunBatchArgs ba{};
+    ba.n_chains = R;
+    ba.cells = cells;
+    ba.seeds = b_seeds;
+    ba.err = b_err;
+    ba.n_pairs = rows;
+    ba.u_stride = (int64_t)T * n;
+    const bool clear_in_kernel = c->tune.run_batch_clear == 1;
+    const int ablocks = agg_blocks(c, n, R);
+    StageEvents<3> ev(c);
+    int rc = [&]() -> int {
+        // ---- stage 1: every chain's starts and their aggregates ----
+        HIP_TRY(c, ev.mark());
+        if (mode < 0) {
+            HIP_TRY(c, hipMemcpyAsync(b_pos[0], pos_inout, (size_t)rows * 4, hipMemcpyHostToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemsetAsync(b_err, 0xff, (size_t)R * 8, c->stream));
+        } else {
+            GS_TRY(b_cnt.alloc(c, n));
+            GS_TRY(b_ctl.alloc(c, R));
+            if (mode == 0)
+                GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
+            else
+                GS_TRY(starts.draw(c, W, seeds, R));
+            for (int32_t r = 0; r < R; ++r) {
+                GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+                // lists of capacity 1 are the position rows; a chain that raised keeps its word
+                HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, 1, b_cnt,
+                                                       b_pos[0] + r * n, c->d_err_code,
+                                                       c->d_err_index, b_err + r, b_ctl + r,
+                                                       c->stream));
+            }
+            GS_TRY(clear_ctx_error_words(c));
+        }
+        ba.pos_in = b_pos[0];
+        ba.agg_out = b_agg[0];
+        HIP_TRY(c, gs_run_batch_agg_launch(a, ba, ablocks, c->stream));
+        HIP_TRY(c, ev.mark());
+        // ---- stage 2: T sweeps of every chain, no host wait in between ----
+        for (int32_t t = 0; t < T; ++t) {
+            const int cur = t % 3, nxt = (t + 1) % 3, aft = (t + 2) % 3;
+            // buffer nxt is zero from the start (t < 2), from sweep t - 1, or from here
+            if (!clear_in_kernel && t >= 2)
+                HIP_TRY(c, hipMemsetAsync(b_agg[nxt], 0, (size_t)agg_elems * 8, c->stream));
+            ba.pos_in = b_pos[t & 1];
+            ba.pos_out = b_pos[(t + 1) & 1];
+            ba.pwms_out = t == T - 1 ? b_pwms.p : nullptr;
+            ba.agg_in = b_agg[cur];
+            ba.agg_out = b_agg[nxt];
+            ba.agg_clear = clear_in_kernel && t >= 1 ? b_agg[aft].p : nullptr;
+            ba.u = b_u ? b_u + (int64_t)t * n : nullptr;
+            a.stream = stream_sweep((uint64_t)(first_sweep + t));
+            HIP_TRY(c, gs_run_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
+        }
+        HIP_TRY(c, ev.mark());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    // uploaded rows never touched the single-chain buffers: only the snapshot goes
+    if (mode >= 0)
+        scratch_used(c);
+    else
+        c->have_state = false;
+    GS_TRY(ev.finish(rc, c->run_batch_ms));
+    // ---- stage 3: one download ----
+    std::vector<unsigned long long> herr((size_t)R);
+    if (T > 0 || mode >= 0)
+        HIP_TRY(c, hipMemcpyAsync(pos_inout, b_pos[T & 1], (size_t)rows * 4, hipMemcpyDeviceToHost,
+                                  c->stream));
+    if (T > 0)
+        HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return report_chain_errors(c, herr, status_out, nullptr);
+}
+
+}  // namespace gs_host

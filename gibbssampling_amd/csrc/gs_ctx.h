@@ -1,5 +1,5 @@
 // gs_ctx.h — host-side state of one context (struct gs_ctx), the engine's internal
-// interface (gs_engine.cpp) and the kernel launchers (*.hip).  Internal: the public
+// interface (gs_engine.cpp, gs_batch.cpp) and the kernel launchers (*.hip).  Internal: the public
 // C ABI is include/gibbs_hip.h, implemented in gs_api.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -403,6 +403,8 @@ double cutoff_threshold(double cutoff);
 double cutoff_threshold_hi(double cutoff);
 int check_dev(gs_ctx *c);
 int alloc_state(gs_ctx *c, int32_t W);
+int ensure_state(gs_ctx *c, int32_t W);
+void takeover_reset(gs_ctx *c);
 int validate_W(gs_ctx *c, int32_t W);
 int validate_pos(gs_ctx *c, int32_t W, const int32_t *pos);
 hipEvent_t get_event(gs_ctx *c);
@@ -428,6 +430,7 @@ int need_vec(gs_ctx *c);
 int allreduce_vec(gs_ctx *c, int idx);
 int launch_dna(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed);
 int set_snapshot(gs_ctx *c, int32_t W, const int32_t *pos);
+int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool reset_err);
 int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed,
               uint64_t stream, bool want_pwms = true);
 bool graphs_wanted(gs_ctx *c);
@@ -437,7 +440,11 @@ int starts_pass(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, const 
                 const int32_t *d_cpart, const int64_t *agg, double *d_score, int32_t *d_pos_out,
                 const double *d_ppm = nullptr, StartsArgs *build_only = nullptr,
                 int64_t *lds_out = nullptr);
+int starts_enqueue(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, int32_t *d_cpart);
+const char *device_error_message(int code);
 int check_device_error(gs_ctx *c);
+int greedy_carve(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes, GreedyArgs &a,
+                 int &waves_out, int64_t &lds_out);
 int greedy_run(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes,
                       int32_t *passes_out, double *kernel_ms_out, int32_t exit_chunk = 0,
                       int32_t exit_ratio = 0, int32_t *exit_info = nullptr);
@@ -452,6 +459,7 @@ int validate_lists(gs_ctx *c, int32_t M, int32_t W, int32_t cap, const int32_t *
 int64_t multi_args(gs_ctx *c, MultiArgs &a, int32_t M, int32_t W, int32_t cap, double pc,
                    double cutoff, bool greedy);
 int multi_scratch(gs_ctx *c, MultiArgs &a, int64_t slots, int64_t arena_cap);
+int packed_status(unsigned long long e);
 int multi_status(gs_ctx *c, unsigned long long *status_out = nullptr);
 int multi_upload(gs_ctx *c, MultiBufs &b, MultiArgs &a, int32_t cap, const int32_t *cnt,
                  const int32_t *pos);
@@ -466,5 +474,18 @@ int multi_greedy_dev(gs_ctx *c, MultiArgs &a, int64_t lds, int32_t cap, int32_t 
 int multi_lds_check(gs_ctx *c, int64_t lds);
 int greedy_hybrid(gs_ctx *c, double pc, double cutoff, int32_t max_passes, int32_t *passes_out,
                   double *kernel_ms_out);
+// gs_batch.cpp: the drivers of the four batched entry points (arguments validated)
+int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds, int32_t R,
+                int32_t mode, int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                int32_t *passes_out, int32_t *status_out);
+int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
+               int32_t max_passes, int32_t *pos_out, double *score_out, int32_t *passes_out,
+               int32_t *status_out);
+int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const uint64_t *seeds,
+                int32_t R, int32_t mode, int32_t max_passes, int32_t cap, int32_t *cnt_out,
+                int32_t *pos_out, double *pwms_out, int32_t *passes_out, int32_t *status_out);
+int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
+              int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
+              double *pwms_out, int32_t *status_out);
 
 }  // namespace gs_host

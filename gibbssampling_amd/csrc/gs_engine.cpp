@@ -38,8 +38,7 @@ void free_state(gs_ctx *c) {
     c->dt_elems = 0;
     c->vec_valid = c->rep_valid = false;
     c->have_state = false;
-    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
-    c->note_pending = false;
+    takeover_reset(c);
     c->W = 0;
 }
 
@@ -185,6 +184,24 @@ int alloc_state(gs_ctx *c, int32_t W) {
     }
     c->W = W;
     return GS_OK;
+}
+
+// The state buffers for W, kept when they are already there: alloc_state keys on
+// have_state, which is false between a batch's chains and after gs_random_starts, and
+// would free and reallocate buffers that enqueued work still names.
+int ensure_state(gs_ctx *c, int32_t W) {
+    if (c->d_pos[0] && c->W == W) return GS_OK;
+    return alloc_state(c, W);
+}
+
+// The all-background takeover (bg_ready) is dropped by every call that changes what the
+// next sweep computes: the sampler's parameters (fixed PCV, scan mode, communicator) or
+// its positions outside set_snapshot (which drops it itself).  Entry points call it only
+// once a call's arguments are validated, so that a rejected call on one rank leaves every
+// rank's state alike.
+void takeover_reset(gs_ctx *c) {
+    c->bg_absorbed = c->bg_zeroed = c->snap_all_none = false;
+    c->note_pending = false;
 }
 
 int validate_W(gs_ctx *c, int32_t W) {
@@ -871,6 +888,51 @@ int set_snapshot(gs_ctx *c, int32_t W, const int32_t *pos) {
     return GS_OK;
 }
 
+// The device-resident route to a snapshot, for the batch drivers (gs_batch.cpp; single
+// device, no communicator): positions already on the device (d_src, valid by
+// construction: nothing is checked on the host, and they are never all []) go to
+// d_pos[0] on the stream, their aggregates to d_agg[0].  reset_err = false keeps a sticky
+// device error of the kernels that produced them.  Kept apart from set_snapshot, from
+// which it differs in: ensure_state for alloc_state (no reallocation under enqueued
+// work), no host positions to validate or upload, snap_all_none always false, no
+// all-reduce and no agreement of the ranks on the sweep kernel, and the error words
+// cleared only on request.
+int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool reset_err) {
+    int rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((rc = ensure_state(c, W))) return rc;
+    takeover_reset(c);
+    if (!c->d_bg_note) HIP_TRY(c, hipMalloc(&c->d_bg_note, 4));
+    HIP_TRY(c, hipMemsetAsync(c->d_bg_note, 0, 4, c->stream));
+    if (d_src != c->d_pos[0] && c->n_local > 0)
+        HIP_TRY(c, hipMemcpyAsync(c->d_pos[0], d_src, (size_t)c->n_local * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+    c->cur_pos = 0;
+    for (auto &b : c->d_agg)
+        HIP_TRY(c, hipMemsetAsync(b, 0, (size_t)kRepl * c->stride * 8, c->stream));
+    if (reset_err) {
+        HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_err_index, 0xff, 8, c->stream));
+    }
+    if (c->n_local > 0)
+        if ((rc = launch_sweep(c, 1, 0.0, 0.0, nullptr, 0, 0, -1, 0, -1))) return rc;
+    c->cur_agg = 0;
+    c->rep_valid = true;
+    c->vec_valid = false;
+    c->dna_agree = true;
+    c->bg_agree = true;
+    HIP_TRY(c, hipMemsetAsync(c->d_gen_done, 0, kDoneBytes, c->stream));
+    c->ftab_agg = -1;
+    if (c->dna_ok) {
+        c->cur_aggv = 0;
+        HIP_TRY(c, hipMemsetAsync(c->d_rep, 0, (size_t)kRepl * c->stride * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_dna_done, 0, kDoneBytes, c->stream));
+        if (use_dna(c) && (rc = need_vec(c))) return rc;
+    }
+    c->have_state = true;
+    return GS_OK;
+}
+
 // want_pwms = false reaches gs_sweep_kernel only: the other kernels always store PWMS
 int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed,
               uint64_t stream, bool want_pwms) {
@@ -1081,6 +1143,44 @@ int starts_pass(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, const 
     return GS_OK;
 }
 
+// getPWMOfRandomStarts on the stream, for the batch drivers: the draws' partial counts
+// (mode 0, into the caller's d_cpart of n_global * A * W int32), then the Jacobi pass over
+// the snapshot just set (d_agg[cur_agg]) -> d_pwms, d_pos[1].  No synchronisation.
+int starts_enqueue(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, int32_t *d_cpart) {
+    const int A = c->A, AW = A * W;
+    if (mode == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_cpart, 0, (size_t)c->n_global * AW * 4, c->stream));
+        PartialArgs p{};
+        p.seq = c->d_seq;
+        p.doff = c->d_doff;
+        p.len = c->d_len;
+        p.n_local = c->n_local;
+        p.global_offset = c->global_offset;
+        p.n_global = c->n_global;
+        p.A = A;
+        p.W = W;
+        p.seed = seed;
+        p.cpart = d_cpart;
+        if (c->n_local > 0) {
+            int grid = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_global, c->n_cu * 8));
+            HIP_TRY(c, gs_starts_partial_launch(p, grid, c->stream));
+        }
+        if (c->comm)
+            RCCL_TRY(c, ncclAllReduce(d_cpart, d_cpart, (size_t)c->n_global * AW, ncclInt32,
+                                      ncclSum, c->comm, c->stream));
+    }
+    return starts_pass(c, mode, W, pc, seed, nullptr, d_cpart, c->d_agg[c->cur_agg], c->d_pwms,
+                       c->d_pos[1], c->use_ppm ? c->d_ppm_fixed : nullptr);
+}
+
+// The device error codes' texts (the code is the GS_E_* status where one exists).
+const char *device_error_message(int code) {
+    return code == 2   ? "roulette wheel ran past the last category (.fs:752)"
+           : code == 3 ? "background count sum overflows int32 (.fs:117)"
+           : code == 5 ? "in-kernel aggregate exchange: a rank did not reach the sweep within 0.5 s"
+                       : "device error";
+}
+
 int check_device_error(gs_ctx *c) {
     int32_t code = 0;
     unsigned long long idx = 0;
@@ -1088,11 +1188,89 @@ int check_device_error(gs_ctx *c) {
     HIP_TRY(c, hipMemcpy(&idx, c->d_err_index, 8, hipMemcpyDeviceToHost));
     if (code == 0) return GS_OK;
     c->have_state = false;  // snapshot is no longer meaningful
-    const char *m = code == 2   ? "roulette wheel ran past the last category (.fs:752)"
-                    : code == 3 ? "background count sum overflows int32 (.fs:117)"
-                    : code == 5 ? "in-kernel aggregate exchange: a rank did not reach the sweep within 0.5 s"
-                                : "device error";
-    return fail(c, code, m, (int64_t)idx);
+    return fail(c, code, device_error_message(code), (int64_t)idx);
+}
+
+// The greedy arguments that do not name a snapshot's buffers, with the LDS carve that
+// gs_greedy.hip reads: the workgroup part, the visit ring of 2 * waves slots, one slice
+// per wavefront: the (PWM, PCV) table and the PCV (site = 0, the motif sampler), or the D
+// table, the others' background and the composition (site = 1, the site sampler).  The
+// one carve of the single chain (greedy_run) and of the batches (gs_batch.cpp).
+int greedy_carve(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes, GreedyArgs &a,
+                 int &waves_out, int64_t &lds_out) {
+    const int A = c->A, E = c->E, W = c->W, WM = gs_sweep_wm(W);
+    // workgroup part, then per wavefront: a tab slice and two ring slots
+    int64_t o = 0;
+    auto take = [&](int64_t b) {
+        int64_t q = o;
+        o = align16(o + b);
+        return (int32_t)q;
+    };
+    a.o_C = take(4 * (int64_t)A * W);
+    a.o_T = take(8 * (int64_t)A);
+    a.o_ppmG = take(8 * (int64_t)A * W);
+    a.o_ppmM = take(8 * (int64_t)A * W);
+    a.o_ctl = take(4 * 64);
+    const int64_t fixed = o;
+    a.ring_seq_bytes = (int32_t)(align16(c->Lmax) + align16(WM) + 32);
+    int64_t wb = 0;
+    if (site) {  // D_k table [K][A], the others' background, the composition
+        a.w_dt = 0;
+        // D_k[b] <= (k + 1) W <= Lmax W: two bytes an entry when that fits
+        a.dt16 = (int64_t)c->Lmax * W < 65536 && c->tune.site_dt16 ? 1 : 0;
+        wb = align16((a.dt16 ? 2 : 4) * (int64_t)c->Lmax * A);
+        a.w_bg = (int32_t)wb;
+        wb += 8 * 64;
+        a.w_comp = (int32_t)wb;
+        wb += 4 * 64;
+    } else {     // (PWM, PCV) table, PCV
+        a.w_tab = 0;
+        wb = align16(16 * (int64_t)E * tab_stride(WM));
+        a.w_pcv = (int32_t)wb;
+        wb += 8 * 64;
+    }
+    a.wave_bytes = (int32_t)wb;
+    a.site = site;
+    const int64_t per_wave = wb + 2 * (a.ring_seq_bytes + 4 * 3 + 8 + 4 * 64) + 64 + 32;
+    int waves = c->tune.greedy_waves;
+    while (waves > 1 && fixed + per_wave * waves > c->max_lds) --waves;
+    if ((int64_t)waves > c->n_local) waves = (int)std::max<int64_t>(1, c->n_local);
+    while (waves & (waves - 1)) waves &= waves - 1;  // a power of two (ring indexing)
+    const int R = 2 * waves;
+    a.o_ring = take((int64_t)R * a.ring_seq_bytes);
+    a.o_rt = take(4 * (int64_t)R);
+    a.o_rL = take(4 * (int64_t)R);
+    a.o_rp = take(4 * (int64_t)R);
+    a.o_rpw = take(8 * (int64_t)R);
+    a.o_rcomp = take(4 * 64 * (int64_t)R);
+    a.o_red = take(8 * 4 * (int64_t)waves);
+    a.o_wave = take((int64_t)waves * a.wave_bytes);
+    a.site_coop = site && c->tune.site_coop ? 1 : 0;
+    a.motif_coop = site ? 0 : c->tune.motif_coop;
+    a.coop_rate = site ? c->tune.coop_rate : 0.0f;  // motif (cfg5): 217 -> 234 ms with it
+    if (o > c->max_lds)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "longest sequence exceeds the greedy kernel's LDS budget (" +
+                        std::to_string(o) + " > " + std::to_string(c->max_lds) + " B)");
+    a.seq = c->d_seq;
+    a.doff = c->d_doff;
+    a.len = c->d_len;
+    a.comp = c->d_comp;
+    a.n = c->n_local;
+    a.A = A;
+    a.W = W;
+    a.E = E;
+    a.cells = c->cells;
+    a.stride = c->stride;
+    a.pc = pc;
+    a.cutoff = cutoff;
+    a.thr_lo = cutoff_threshold(cutoff);
+    a.apc = (double)A * pc;
+    a.den = (double)(c->n_global - 1) + a.apc;
+    a.max_passes = max_passes;
+    waves_out = waves;
+    lds_out = o;
+    return GS_OK;
 }
 
 // The speculative Gauss–Seidel kernel (gs_greedy.hip) on the resident snapshot
@@ -1107,78 +1285,11 @@ int greedy_run(gs_ctx *c, int site, double pc, double cutoff, int32_t max_passes
     float ms = 0.0f;
     if (c->n_local > 0) {
         GreedyArgs a{};
-        const int A = c->A, E = c->E, W = c->W, WM = gs_sweep_wm(W);
-        // workgroup part, then per wavefront: a tab slice and two ring slots
+        int waves = 0;
         int64_t o = 0;
-        auto take = [&](int64_t b) {
-            int64_t q = o;
-            o = align16(o + b);
-            return (int32_t)q;
-        };
-        a.o_C = take(4 * (int64_t)A * W);
-        a.o_T = take(8 * (int64_t)A);
-        a.o_ppmG = take(8 * (int64_t)A * W);
-        a.o_ppmM = take(8 * (int64_t)A * W);
-        a.o_ctl = take(4 * 64);
-        const int64_t fixed = o;
-        a.ring_seq_bytes = (int32_t)(align16(c->Lmax) + align16(WM) + 32);
-        int64_t wb = 0;
-        if (site) {  // D_k table [K][A], the others' background, the composition
-            a.w_dt = 0;
-            // D_k[b] <= (k + 1) W <= Lmax W: two bytes an entry when that fits
-            a.dt16 = (int64_t)c->Lmax * W < 65536 && c->tune.site_dt16 ? 1 : 0;
-            wb = align16((a.dt16 ? 2 : 4) * (int64_t)c->Lmax * A);
-            a.w_bg = (int32_t)wb;
-            wb += 8 * 64;
-            a.w_comp = (int32_t)wb;
-            wb += 4 * 64;
-        } else {     // (PWM, PCV) table, PCV
-            a.w_tab = 0;
-            wb = align16(16 * (int64_t)E * tab_stride(WM));
-            a.w_pcv = (int32_t)wb;
-            wb += 8 * 64;
-        }
-        a.wave_bytes = (int32_t)wb;
-        a.site = site;
+        if ((rc = greedy_carve(c, site, pc, cutoff, max_passes, a, waves, o))) return rc;
         a.pcv_fixed = c->use_pcv ? c->d_pcv_fixed : nullptr;
-        const int64_t per_wave = wb + 2 * (a.ring_seq_bytes + 4 * 3 + 8 + 4 * 64) + 64 + 32;
-        int waves = c->tune.greedy_waves;
-        while (waves > 1 && fixed + per_wave * waves > c->max_lds) --waves;
-        if ((int64_t)waves > c->n_local) waves = (int)std::max<int64_t>(1, c->n_local);
-        while (waves & (waves - 1)) waves &= waves - 1;  // a power of two (ring indexing)
-        const int R = 2 * waves;
-        a.o_ring = take((int64_t)R * a.ring_seq_bytes);
-        a.o_rt = take(4 * (int64_t)R);
-        a.o_rL = take(4 * (int64_t)R);
-        a.o_rp = take(4 * (int64_t)R);
-        a.o_rpw = take(8 * (int64_t)R);
-        a.o_rcomp = take(4 * 64 * (int64_t)R);
-        a.o_red = take(8 * 4 * (int64_t)waves);
-        a.o_wave = take((int64_t)waves * a.wave_bytes);
-        a.site_coop = site && c->tune.site_coop ? 1 : 0;
-        a.motif_coop = site ? 0 : c->tune.motif_coop;
-        a.coop_rate = site ? c->tune.coop_rate : 0.0f;  // motif (cfg5): 217 -> 234 ms with it
-        if (o > c->max_lds)
-            return fail(c, GS_E_UNSUPPORTED,
-                        "longest sequence exceeds the greedy kernel's LDS budget (" +
-                            std::to_string(o) + " > " + std::to_string(c->max_lds) + " B)");
         c->last_greedy_waves = waves;
-        a.seq = c->d_seq;
-        a.doff = c->d_doff;
-        a.len = c->d_len;
-        a.comp = c->d_comp;
-        a.n = c->n_local;
-        a.A = A;
-        a.W = W;
-        a.E = E;
-        a.cells = c->cells;
-        a.stride = c->stride;
-        a.pc = pc;
-        a.cutoff = cutoff;
-        a.thr_lo = cutoff_threshold(cutoff);
-        a.apc = (double)A * pc;
-        a.den = (double)(c->n_global - 1) + a.apc;
-        a.max_passes = max_passes;
         if ((rc = need_rep(c))) return rc;
         c->vec_valid = false;  // the passes rewrite the replicas
         a.agg = c->d_agg[c->cur_agg];
@@ -1502,18 +1613,22 @@ int multi_scratch(gs_ctx *c, MultiArgs &a, int64_t slots, int64_t arena_cap) {
 }
 
 
+// The GS_E_* status of a packed device status word, (global index << 4) | status, of the
+// list path and the chain batches; ~0: none.  (kMultiErrArena and kMultiErrUnsupported are
+// the callers' to handle.)
+int packed_status(unsigned long long e) {
+    if (e == ~0ull) return GS_OK;
+    const int st = (int)(e & 15ull);
+    return st == 2 ? GS_E_ROULETTE_OVERRUN : st == 3 ? GS_E_OVERFLOW : GS_E_HIP;
+}
+
 int multi_status(gs_ctx *c, unsigned long long *status_out) {
     unsigned long long e = ~0ull;
     HIP_TRY(c, hipMemcpy(&e, c->d_merr, 8, hipMemcpyDeviceToHost));
     if (status_out) *status_out = e;
-    if (e == ~0ull) return GS_OK;
-    const int st = (int)(e & 15ull);
-    const int64_t idx = (int64_t)(e >> 4);
-    if (st == kMultiErrArena) return GS_OK;  // handled by the caller
-    const char *m = st == 2   ? "roulette wheel ran past the last category (.fs:752)"
-                    : st == 3 ? "background count sum overflows int32 (.fs:117)"
-                              : "device error";
-    return fail(c, st == 2 ? GS_E_ROULETTE_OVERRUN : st == 3 ? GS_E_OVERFLOW : GS_E_HIP, m, idx);
+    if (e == ~0ull || (int)(e & 15ull) == kMultiErrArena) return GS_OK;  // (arena: the caller's)
+    const int status = packed_status(e);
+    return fail(c, status, device_error_message(status), (int64_t)(e >> 4));
 }
 
 // Upload a list snapshot and build its aggregates (all-reduced over the ranks).

@@ -36,6 +36,7 @@ SHAPES = {"small": (200, 200, 12, 64), "medium": (2_000, 200, 12, 32),
           "cfg2": (10_000, 200, 12, 8)}
 PC, CUTOFF, SEED0 = 1e-4, 1.0, 7
 SOURCES = ["gibbssampling_amd/csrc/gs_greedy.hip", "gibbssampling_amd/csrc/gs_api.cpp",
+           "gibbssampling_amd/csrc/gs_batch.cpp",
            "gibbssampling_amd/csrc/gs_engine.cpp", "gibbssampling_amd/csrc/gs_starts.hip",
            "gibbssampling_amd/csrc/gs_sweep.hip", "gibbssampling_amd/csrc/gs_common.h",
            "gibbssampling_amd/csrc/gs_ctx.h", "gibbssampling_amd/csrc/Makefile"]
@@ -61,19 +62,21 @@ def main():
     ap.add_argument("--init-mode", type=int, default=0)
     ap.add_argument("--loop-lib", default=None,
                     help="library the sequential loop runs through (default: the built one)")
+    ap.add_argument("--batch-lib", default=None,
+                    help="library the batch call runs through (default: the built one)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "batch" / "batch_bench.json"))
     args = ap.parse_args()
     from gibbssampling_amd import Context
 
     rec = {"tool": "tools/batch_bench.py", "source_sha256": source_hash(),
            "pc": PC, "cutoff": CUTOFF, "init_mode": args.init_mode, "reps": args.reps,
-           "loop_lib": args.loop_lib or "built", "shapes": {}}
+           "loop_lib": args.loop_lib or "built", "batch_lib": args.batch_lib or "built", "shapes": {}}
     for name in args.shapes:
         N, L, W, R = SHAPES[name]
         codes, offsets = make_dataset(N, L, W, b"ACGT", seed=5)
         seeds = [SEED0 + r for r in range(R)]
         loop_ctx = Context(0, lib_path=args.loop_lib)
-        batch_ctx = Context(0)
+        batch_ctx = Context(0, lib_path=args.batch_lib)
         for c in (loop_ctx, batch_ctx):
             c.set_sequences(codes, offsets, b"ACGT")
         loop_ctx.motif_sampling(W, PC, CUTOFF, seeds[0], args.init_mode)  # warm-up

@@ -38,6 +38,7 @@ from pmc_traffic import _code_only  # noqa: E402
 SHAPES = {"fsx": (5, 27, 6, 64), "dna200": (200, 200, 12, 64), "dna2000": (2_000, 200, 12, 16)}
 M, PC, CUTOFF, SEED0 = 2, 1e-4, 1.0, 7
 SOURCES = ["gibbssampling_amd/csrc/gs_multi.hip", "gibbssampling_amd/csrc/gs_api.cpp",
+           "gibbssampling_amd/csrc/gs_batch.cpp",
            "gibbssampling_amd/csrc/gs_engine.cpp", "gibbssampling_amd/csrc/gs_starts.hip",
            "gibbssampling_amd/csrc/gs_common.h", "gibbssampling_amd/csrc/gs_ctx.h",
            "gibbssampling_amd/csrc/Makefile"]
@@ -77,6 +78,8 @@ def main():
     ap.add_argument("--loop-lib", required=True,
                     help="the parent commit's build of the library, for the sequential loop")
     ap.add_argument("--fill", type=int, default=None, help="multi_batch_fill of the batch side")
+    ap.add_argument("--batch-lib", default=None,
+                    help="library the batch call runs through (default: the built one)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "batch" / "multi_batch_bench.json"))
     args = ap.parse_args()
     from gibbssampling_amd import Context
@@ -84,13 +87,13 @@ def main():
     rec = {"tool": "tools/multi_batch_bench.py", "source_sha256": source_hash(),
            "motif_amount": M, "pc": PC, "cutoff": CUTOFF, "init_mode": args.init_mode,
            "reps": args.reps, "loop_lib": "parent commit's build", "multi_batch_fill": args.fill,
-           "shapes": {}}
+           "batch_lib": args.batch_lib or "built", "shapes": {}}
     for name in args.shapes:
         N, L, W, R = SHAPES[name]
         codes, offsets, alpha = dataset(name)
         seeds = [SEED0 + r for r in range(R)]
         loop_ctx = Context(0, lib_path=args.loop_lib)
-        batch_ctx = Context(0, tuning=None if args.fill is None else {"multi_batch_fill": args.fill})
+        batch_ctx = Context(0, lib_path=args.batch_lib, tuning=None if args.fill is None else {"multi_batch_fill": args.fill})
         for c in (loop_ctx, batch_ctx):
             c.set_sequences(codes, offsets, alpha)
         loop_ctx.motif_sampling_multi(M, W, PC, CUTOFF, seeds[0], args.init_mode)  # warm-up

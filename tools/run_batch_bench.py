@@ -39,6 +39,7 @@ SHAPES = {"dna200": (200, 200, 12, 64), "dna2000": (2_000, 200, 12, 16),
           "dna10k": (10_000, 200, 12, 8)}
 PC, CUTOFF, SEED0 = 1e-4, 1.0, 7
 SOURCES = ["gibbssampling_amd/csrc/gs_multi.hip", "gibbssampling_amd/csrc/gs_api.cpp",
+           "gibbssampling_amd/csrc/gs_batch.cpp",
            "gibbssampling_amd/csrc/gs_engine.cpp", "gibbssampling_amd/csrc/gs_starts.hip",
            "gibbssampling_amd/csrc/gs_common.h", "gibbssampling_amd/csrc/gs_ctx.h",
            "gibbssampling_amd/csrc/Makefile"]
@@ -71,6 +72,8 @@ def main():
                     help="the parent commit's build of the library, for the sequential loop")
     ap.add_argument("--clear", type=int, default=None, help="run_batch_clear of the batch side")
     ap.add_argument("--blocks", type=int, default=None, help="run_batch_blocks of the batch side")
+    ap.add_argument("--batch-lib", default=None,
+                    help="library the batch call runs through (default: the built one)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "batch" / "run_batch_bench.json"))
     args = ap.parse_args()
     from gibbssampling_amd import Context
@@ -80,13 +83,13 @@ def main():
     rec = {"tool": "tools/run_batch_bench.py", "source_sha256": source_hash(), "pc": PC,
            "cutoff": CUTOFF, "reps": args.reps, "loop_lib": "parent commit's build",
            "starts": "random_starts mode 1 per seed, uploaded (init_mode -1)", "tuning": tuning,
-           "shapes": {}}
+           "batch_lib": args.batch_lib or "built", "shapes": {}}
     for name in args.shapes:
         N, L, W, R = SHAPES[name]
         codes, offsets = make_dataset(N, L, W, b"ACGT", seed=5)
         seeds = [SEED0 + r for r in range(R)]
         loop_ctx = Context(0, lib_path=args.loop_lib)
-        batch_ctx = Context(0, tuning=tuning or None)
+        batch_ctx = Context(0, lib_path=args.batch_lib, tuning=tuning or None)
         for c in (loop_ctx, batch_ctx):
             c.set_sequences(codes, offsets, b"ACGT")
         starts = np.array([loop_ctx.random_starts(W, PC, s, 1)[1] for s in seeds], np.int32)

@@ -40,19 +40,21 @@ def main():
     ap.add_argument("--init-mode", type=int, default=0)
     ap.add_argument("--loop-lib", default=None,
                     help="library the sequential loop runs through (default: the built one)")
+    ap.add_argument("--batch-lib", default=None,
+                    help="library the batch call runs through (default: the built one)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "batch" / "site_batch_bench.json"))
     args = ap.parse_args()
     from gibbssampling_amd import Context
 
     rec = {"tool": "tools/site_batch_bench.py", "source_sha256": source_hash(),
            "pc": PC, "init_mode": args.init_mode, "reps": args.reps,
-           "loop_lib": args.loop_lib or "built", "shapes": {}}
+           "loop_lib": args.loop_lib or "built", "batch_lib": args.batch_lib or "built", "shapes": {}}
     for name in args.shapes:
         N, L, W, R = SHAPES[name]
         codes, offsets = make_dataset(N, L, W, b"ACGT", seed=5)
         seeds = [SEED0 + r for r in range(R)]
         loop_ctx = Context(0, lib_path=args.loop_lib)
-        batch_ctx = Context(0)
+        batch_ctx = Context(0, lib_path=args.batch_lib)
         for c in (loop_ctx, batch_ctx):
             c.set_sequences(codes, offsets, b"ACGT")
         loop_ctx.site_sampling(W, PC, seeds[0], args.init_mode)  # warm-up
