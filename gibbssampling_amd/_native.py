@@ -168,6 +168,8 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_site_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_counts": (C.c_int, [vp, i32, vp, vp, vp]),
         "gs_random_starts": (C.c_int, [vp, i32, f64, u64, i32, vp, vp]),
+        "gs_random_starts_batch": (C.c_int, [vp, i32, f64, vp, i32, i32, vp, vp, vp]),
+        "gs_starts_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_best_pwms": (C.c_int, [vp, i32, f64, i32, vp, vp, P(f64), P(i32)]),
         "gs_uniform": (f64, [u64, u64, u64]),
         "gs_stream_sweep": (u64, [u64]),
@@ -615,6 +617,31 @@ class Context:
         self._check(self.lib.gs_random_starts(self.h, int(W), float(pc), int(seed) & (2**64 - 1),
                                               int(mode), _ptr(score), _ptr(pos)))
         return score, pos
+
+    def random_starts_batch(self, W: int, pc: float, seeds, mode: int = 0):
+        """R independent getPWMOfRandomStarts runs in one call, row r exactly
+        random_starts(W, pc, seeds[r], mode): every chain in the same launches over the
+        (chain, target) pairs -> (score[R, N], pos[R, N], status[R]).  It follows
+        set_fixed_pcv / set_fixed_ppm as random_starts does.  A chain that raises
+        (status[r] != 0, GS_E_OVERFLOW) leaves the other rows valid; errors of the call
+        itself raise."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        score = np.zeros((R, self.n_local), np.float64)
+        pos = np.zeros((R, self.n_local), np.int32)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_random_starts_batch(self.h, int(W), float(pc), _ptr(seeds), R, int(mode),
+                                             _ptr(score), _ptr(pos), _ptr(status))
+        if st != GS_OK and not status.any():
+            self._check(st)
+        return score, pos, status
+
+    def starts_batch_last_ms(self):
+        """Device milliseconds of the last random_starts_batch: (counts or aggregates,
+        scans)."""
+        out = np.zeros(2, np.float64)
+        self._check(self.lib.gs_starts_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
 
     # -- host-staged aggregate exchange
     def best_pwms(self, W: int, pc: float, target: int, fcv49, ppm49):

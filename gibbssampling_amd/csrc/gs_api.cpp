@@ -50,6 +50,7 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(multi_batch_fill, v >= 1 && v <= 4096),
     GS_TUNING_FIELD(run_batch_clear, v == 0 || v == 1),
     GS_TUNING_FIELD(run_batch_blocks, v >= 1 && v <= 32),
+    GS_TUNING_FIELD(batch_starts, v == -1 || v == 0 || v == 1),
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(site_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(ftab_mode, v == 0 || v == 1 || v == 2),
@@ -785,6 +786,33 @@ int gs_random_starts(gs_ctx *c, int32_t W, double pc, uint64_t seed, int32_t mod
         HIP_TRY(c, hipMemcpy(score_out, c->d_pwms, (size_t)c->n_local * 8, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(pos_out, c->d_pos[1], (size_t)c->n_local * 4, hipMemcpyDeviceToHost));
     }
+    return GS_OK;
+}
+
+int gs_random_starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t n_chains,
+                           int32_t mode, double *score_out, int32_t *pos_out,
+                           int32_t *status_out) {
+    if (!c || n_chains < 0 || (mode != 0 && mode != 1)) return GS_E_ARG;
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!score_out || !pos_out))) return GS_E_ARG;
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if (c->use_ppm && c->ppm_W != W)
+        return fail(c, GS_E_ARG, "the fixed PPM was set for another motifLength");
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_random_starts_batch: the chains' counts are summed on one device: it "
+                    "needs all sequences there and no communicator (loop gs_random_starts)");
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    takeover_reset(c);
+    return starts_batch(c, W, pc, seeds, n_chains, mode, score_out, pos_out, status_out);
+}
+
+int gs_starts_batch_last_ms(const gs_ctx *c, double out[2]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->starts_batch_ms[0];
+    out[1] = c->starts_batch_ms[1];
     return GS_OK;
 }
 

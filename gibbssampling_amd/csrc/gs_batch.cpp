@@ -1,8 +1,9 @@
-// gs_batch.cpp — the host drivers of the four batched entry points:
+// gs_batch.cpp — the host drivers of the batched entry points:
 // motif_batch (gs_motif_sampling_batch), site_batch (gs_site_sampling_batch), multi_batch
-// (gs_motif_sampling_multi_batch) and run_batch (gs_motif_run_batch), over one copy of the
-// stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they
-// reuse (set_snapshot_dev, starts_enqueue, greedy_carve, one_sweep) are in gs_engine.cpp.
+// (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch) and starts_batch
+// (gs_random_starts_batch), over one copy of the stages they share.  gs_api.cpp validates
+// the arguments; the single-chain pieces they reuse (set_snapshot_dev, starts_enqueue,
+// starts_pass, greedy_carve, one_sweep) are in gs_engine.cpp.
 #include "gs_ctx.h"
 
 namespace gs_host {
@@ -119,6 +120,159 @@ int chain_starts(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed,
     return starts_enqueue(c, mode, W, pc, seed, d_cpart);
 }
 
+// tune.batch_starts: whether a driver takes its chains' starts from BatchStarts.  Automatic:
+// while a chain has fewer targets than a launch has workgroups (8 a CU); from there on a
+// chain's own launches fill the GPU and the batched starts measured no faster (§9.15).
+bool batched_starts(const gs_ctx *c) {
+    return c->tune.batch_starts == 1 ||
+           (c->tune.batch_starts < 0 && c->n_global < (int64_t)c->n_cu * 8);
+}
+
+// The starts of all chains in a constant number of launches (the drivers under
+// batched_starts, and gs_random_starts_batch): what the loop over
+// chain_starts leaves in d_pos[1] / d_pwms and the context's error words, chain after
+// chain, as row r of the caller's slabs.  prepare() allocates and uploads before the timed
+// stages; enqueue() only enqueues.  Mode 0 runs the chains in groups whose cpart stays under
+// kStartsCpartBudget (a chain's own slab may pass it: then one chain a group), and counts
+// with the chain-indexed kernel while a chain has fewer targets than the launch has
+// workgroups, beyond with the single-chain kernel chain after chain (the chain-indexed one
+// measured 17.4 against 12.5 ms at 10k sequences x 8 chains).
+struct BatchStarts {
+    DevBuf<int64_t> agg;     // mode 1: [R][cells] of the shared draws; mode 0: one row
+    DevBuf<int32_t> cpart;   // mode 0: [group][n_global][A * W]
+    DevBuf<uint64_t> seeds;  // [R]
+    const uint64_t *h_seeds = nullptr;  // the caller's, alive for the call
+    StartsArgs sa{};
+    PartialArgs pa{};
+    int64_t lds = 0, cpart_chain = 0;
+    int32_t R = 0, mode = 0, group = 0, cells = 0;
+    // the device time of the counts / aggregates and of the scans, when asked for
+    std::vector<hipEvent_t> ev;
+    gs_ctx *ctx = nullptr;
+    BatchStarts() = default;
+    BatchStarts(const BatchStarts &) = delete;
+    BatchStarts &operator=(const BatchStarts &) = delete;
+    ~BatchStarts() {
+        if (ctx) release(ctx);
+    }
+
+    int prepare(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds_in, int32_t n_chains,
+                int32_t init_mode) {
+        ctx = c;
+        R = n_chains;
+        mode = init_mode;
+        cells = c->A * W + c->A;
+        // (a fixed PCV / PPM applies as in starts_enqueue; the four drivers refuse both)
+        GS_TRY(starts_pass(c, mode, W, pc, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           c->use_ppm ? c->d_ppm_fixed : nullptr, &sa, &lds));
+        cpart_chain = mode == 0 ? c->n_global * c->A * W : 0;
+        group = mode == 0 ? (int32_t)std::max<int64_t>(
+                                1, std::min<int64_t>(R, kStartsCpartBudget / std::max<int64_t>(
+                                                            1, cpart_chain * 4)))
+                          : R;
+        GS_TRY(agg.alloc(c, (int64_t)(mode == 1 ? R : 1) * cells));
+        if (mode == 0) GS_TRY(cpart.alloc(c, std::max<int64_t>(1, group * cpart_chain)));
+        GS_TRY(seeds.alloc(c, R));
+        h_seeds = seeds_in;
+        HIP_TRY(c, hipMemcpyAsync(seeds, h_seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+        pa.seq = c->d_seq;
+        pa.doff = c->d_doff;
+        pa.len = c->d_len;
+        pa.n_local = c->n_local;
+        pa.global_offset = c->global_offset;
+        pa.n_global = c->n_global;
+        pa.A = c->A;
+        pa.W = W;
+        pa.cpart = cpart;
+        sa.agg = agg;
+        sa.cpart = cpart;
+        return GS_OK;
+    }
+
+    // Chain r's scores, starts and (code, index) error words -> row r of the slabs.
+    // timed: events around every group's two stages (read by elapsed()).
+    int enqueue(gs_ctx *c, double *score, int32_t *pos, int32_t *err_code,
+                unsigned long long *err_index, bool timed = false) {
+        const int64_t n = c->n_local;
+        // a target that raises (.fs:117) writes no start: every entry stays a valid one
+        HIP_TRY(c, hipMemsetAsync(pos, 0, (size_t)(R * n) * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(err_code, 0, (size_t)R * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(err_index, 0xff, (size_t)R * 8, c->stream));
+        auto mark = [&]() -> hipError_t {
+            if (!timed) return hipSuccess;
+            ev.push_back(get_event(c));
+            return hipEventRecord(ev.back(), c->stream);
+        };
+        HIP_TRY(c, mark());
+        // mode 1: the aggregates of every chain's shared draws; mode 0: the composition
+        // totals, the same for every chain, from one row of any valid start vector
+        StartsBatchArgs b{};
+        b.seeds = seeds;
+        b.n_chains = mode == 1 ? R : 1;
+        b.blocks = agg_blocks(c, n, b.n_chains);
+        b.src = mode;
+        b.E = c->E;
+        b.comp = c->d_comp;
+        b.agg_out = agg;
+        b.agg_out_chain = cells;
+        HIP_TRY(c, hipMemsetAsync(agg, 0, (size_t)b.n_chains * cells * 8, c->stream));
+        HIP_TRY(c, gs_starts_batch_agg_launch(sa, b, c->stream));
+        b.agg_chain = mode == 1 ? cells : 0;
+        b.cpart_chain = cpart_chain;
+        // the scans' workgroups: the D table's slots when it lies in HBM (starts_pass)
+        const int64_t wg_max =
+            sa.dt_global ? std::max<int>(c->n_cu * 2, c->tune.multi_spec_slots) : (int64_t)c->n_cu * 8;
+        for (int32_t g0 = 0; g0 < R; g0 += group) {
+            const int32_t ng = std::min(group, R - g0);
+            if (g0 > 0) HIP_TRY(c, mark());
+            b.seeds = seeds + g0;
+            b.n_chains = ng;
+            b.n_pairs = (int64_t)ng * n;
+            if (mode == 0 && c->n_global < (int64_t)c->n_cu * 8) {
+                const int64_t items = (int64_t)ng * c->n_global;
+                HIP_TRY(c, gs_starts_batch_partial_launch(
+                               pa, b, (int)std::min<int64_t>(items, (int64_t)c->n_cu * 8), c->stream));
+            } else if (mode == 0) {
+                // a chain's targets fill the launch's workgroups by themselves: the
+                // single-chain count kernel, chain after chain, each into its slab
+                for (int32_t r = 0; r < ng; ++r) {
+                    PartialArgs p1 = pa;
+                    p1.seed = h_seeds[g0 + r];
+                    p1.cpart = cpart + r * cpart_chain;
+                    HIP_TRY(c, gs_starts_partial_launch(p1, c->n_cu * 8, c->stream));
+                }
+            }
+            HIP_TRY(c, mark());
+            StartsArgs a = sa;
+            a.score_out = score + g0 * n;
+            a.pos_out = pos + g0 * n;
+            a.err_code = err_code + g0;
+            a.err_index = err_index + g0;
+            if (mode == 1) a.agg = agg + (int64_t)g0 * cells;
+            HIP_TRY(c, gs_starts_batch_launch(a, b, (int)std::min<int64_t>(b.n_pairs, wg_max),
+                                              (size_t)lds, c->stream));
+            HIP_TRY(c, mark());
+        }
+        return GS_OK;
+    }
+
+    // After the synchronisation: ms[0] the counts / aggregates, ms[1] the scans, summed
+    // over the groups; the events go back to the pool.
+    void elapsed(gs_ctx *c, double ms[2]) {
+        ms[0] = ms[1] = 0.0;
+        for (size_t i = 0; i + 2 < ev.size(); i += 3)
+            for (int k = 0; k < 2; ++k) {
+                float t = 0.0f;
+                if (hipEventElapsedTime(&t, ev[i + k], ev[i + k + 1]) == hipSuccess) ms[k] += t;
+            }
+        release(c);
+    }
+    void release(gs_ctx *c) {
+        for (hipEvent_t e : ev) c->ev_pool.push_back(e);
+        ev.clear();
+    }
+};
+
 // The context's own error words end clear, whatever the last chain's were.
 int clear_ctx_error_words(gs_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(c->d_err_code, 0, 4, c->stream));
@@ -230,8 +384,9 @@ int32_t multi_batch_slots(const gs_ctx *c, int64_t chains, int64_t slot_bytes) {
 
 // R independent doMotifSampling runs (.fs:1034-1038, motifAmount = 1).  Stage 1, chain
 // after chain on the context's single-chain state and stream, no host wait in between:
-// starts (seed r) -> snapshot of them -> sweep 0 of seed r -> device copies of positions,
-// PWMS, replica aggregates and the error words into slab r.  Stage 2: one launch of
+// starts (seed r; under batched_starts all chains' first, into the slabs) -> snapshot of
+// them -> sweep 0 of seed r -> device copies of positions, PWMS, replica aggregates and the
+// error words into slab r.  Stage 2: one launch of
 // gs_greedy_batch_kernel, workgroup r on slab r, every pass in-kernel.  One
 // synchronisation, then the slabs come down.  The caller validated the arguments.
 int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds, int32_t R,
@@ -253,17 +408,30 @@ int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *
     GS_TRY(b.alloc(c, R));
     DevBuf<int32_t> cpart;
     SharedStarts starts;
-    if (mode == 0)
+    BatchStarts bs;
+    const bool batched = batched_starts(c);
+    if (batched)
+        GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+    else if (mode == 0)
         GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
     else
         GS_TRY(starts.draw(c, W, seeds, R));
     StageEvents<3> ev(c);
     int rc = [&]() -> int {
         HIP_TRY(c, ev.mark());
+        // batched: row r of the slabs holds chain r's starts until take_chain replaces it
+        if (batched) GS_TRY(bs.enqueue(c, b.pwms, b.pos, b.err, b.erri));
         for (int32_t r = 0; r < R; ++r) {
-            GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+            if (batched) {
+                HIP_TRY(c, hipMemcpyAsync(c->d_err_code, b.err + r, 4, hipMemcpyDeviceToDevice,
+                                          c->stream));
+                HIP_TRY(c, hipMemcpyAsync(c->d_err_index, b.erri + r, 8, hipMemcpyDeviceToDevice,
+                                          c->stream));
+            } else {
+                GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+            }
             // its error word stays set: the sweep skips, the chain's slab carries it
-            GS_TRY(set_snapshot_dev(c, W, c->d_pos[1], false));
+            GS_TRY(set_snapshot_dev(c, W, batched ? b.pos + r * n : c->d_pos[1], false));
             if (use_dna(c)) {  // (as gs_run_sweeps: the device sweep counter at sweep 0)
                 GS_TRY(need_vec(c));
                 HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, 0ull, c->d_done_ctr, c->stream));
@@ -296,7 +464,8 @@ int motif_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *
 // R independent doSiteSampling runs (.fs:697-701), DESIGN.md §9.11.  Stage 1, chain after
 // chain on the context's single-chain state and stream, no host wait in between: starts
 // (seed r) -> snapshot of them -> device copies of positions, scores, replica aggregates
-// and the error words into slab r.  Stage 2: getBestPWMSsWithStartPositions of every
+// and the error words into slab r; under batched_starts the launches of BatchStarts write
+// the slabs in place and one more aggregate launch fills the chains' replica 0.  Stage 2: getBestPWMSsWithStartPositions of every
 // chain as one launch of the star site engine, workgroup r on slab r, every pass
 // in-kernel.  Stage 3: the shifted passes (-1 to completion, then +1), every running
 // chain in the same launches, one synchronisation per pass for all chains.  The caller
@@ -342,7 +511,11 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
     const int ablocks = agg_blocks(c, n, R);
     DevBuf<int32_t> cpart;
     SharedStarts starts;
-    if (mode == 0)
+    BatchStarts bs;
+    const bool batched = batched_starts(c);
+    if (batched)
+        GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+    else if (mode == 0)
         GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
     else
         GS_TRY(starts.draw(c, W, seeds, R));
@@ -350,7 +523,23 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
     std::vector<int32_t> left((size_t)R);
     int rc = [&]() -> int {
         HIP_TRY(c, ev.mark());
-        for (int32_t r = 0; r < R; ++r) {
+        if (batched) {
+            // the acc of the refinements in place: the starts and their error words, then
+            // the starts' aggregates into replica 0 of every chain's slab
+            GS_TRY(bs.enqueue(c, b.pwms, b.pos, b.err, b.erri));
+            HIP_TRY(c, hipMemsetAsync(b.agg, 0, (size_t)(R * agg_elems) * 8, c->stream));
+            StartsBatchArgs ab{};
+            ab.n_chains = R;
+            ab.blocks = ablocks;
+            ab.src = 2;
+            ab.E = c->E;
+            ab.comp = c->d_comp;
+            ab.pos = b.pos;
+            ab.agg_out = b.agg;
+            ab.agg_out_chain = agg_elems;
+            HIP_TRY(c, gs_starts_batch_agg_launch(bs.sa, ab, c->stream));
+        }
+        for (int32_t r = 0; !batched && r < R; ++r) {
             GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
             // the acc of the refinements (site_upload): the starts, their aggregates
             GS_TRY(set_snapshot_dev(c, W, c->d_pos[1], false));
@@ -404,8 +593,9 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
 
 // R independent doMotifSampling runs with Positions lists (.fs:1034-1038, any
 // motifAmount), DESIGN.md §9.12.  Stage 1, chain after chain on the context's
-// single-chain state and stream, no host wait in between: starts (seed r) as the lists
-// of slab r.  Stage 2: the aggregates of every chain's starts and sweep 0 over the
+// single-chain state and stream, no host wait in between (or, under batched_starts, all
+// chains in the launches of BatchStarts and one list conversion): starts (seed r) as the
+// lists of slab r.  Stage 2: the aggregates of every chain's starts and sweep 0 over the
 // (chain, target) pairs, one host wait per arena round for all chains.  Stage 3: the
 // greedy passes, speculative steps of two launches for all chains, one host wait per
 // kSpecBatch steps; chains whose arena overflowed start again from the kept sweep output
@@ -467,7 +657,15 @@ int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const
     GS_TRY(b_ovf.alloc(c, rows + 1));
     GS_TRY(b_pairs.alloc(c, rows));
     GS_TRY(b_chains.alloc(c, R));
-    if (mode == 0)
+    BatchStarts bs;
+    DevBuf<int32_t> s_err;             // batched starts: the chains' (code, index) words
+    DevBuf<unsigned long long> s_erri;
+    const bool batched = batched_starts(c);
+    if (batched) {
+        GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+        GS_TRY(s_err.alloc(c, R));
+        GS_TRY(s_erri.alloc(c, R));
+    } else if (mode == 0)
         GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
     else
         GS_TRY(starts.draw(c, W, seeds, R));
@@ -510,7 +708,13 @@ int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const
     int rc = [&]() -> int {
         // ---- stage 1: every chain's starts, as lists ----
         HIP_TRY(c, ev.mark());
-        for (int32_t r = 0; r < R; ++r) {
+        if (batched) {
+            // (the sweep's output slabs are free until stage 2: scores and starts go there)
+            GS_TRY(bs.enqueue(c, b_pwms[0], b_cnt[1], s_err, s_erri));
+            HIP_TRY(c, gs_starts_batch_lists_launch(b_cnt[1], rows, cap, b_cnt[0], b_pos[0], R, s_err,
+                                                    s_erri, b_err, b_ctl, c->stream));
+        }
+        for (int32_t r = 0; !batched && r < R; ++r) {
             GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
             HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, cap, b_cnt[0] + r * n,
                                                    b_pos[0] + r * n * cap, c->d_err_code,
@@ -648,7 +852,8 @@ int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const
 
 // R independent chains of T synchronous sweeps (motifAmount = 1), DESIGN.md §9.13.  Stage
 // 1: the chains' starts, uploaded rows (mode -1) or, chain after chain on the context's
-// single-chain state and stream as in multi_batch, those of getPWMOfRandomStarts; then the
+// single-chain state and stream as in multi_batch (or all at once, batched_starts: the
+// starts' position slab is the chains'), those of getPWMOfRandomStarts; then the
 // aggregates of every chain's starts.  Stage 2: T launches of gs_run_batch_sweep_kernel
 // over the (chain, target) pairs back to back, positions double-buffered, the aggregate
 // rows rotating over three buffers (the next one zeroed by a memset before the sweep that
@@ -691,6 +896,9 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     DevBuf<SpecCtl> b_ctl;
     DevBuf<int32_t> b_cnt, cpart;
     SharedStarts starts;
+    BatchStarts bs;
+    DevBuf<int32_t> s_err;  // batched starts: the chains' (code, index) words
+    DevBuf<unsigned long long> s_erri;
     for (auto &q : b_pos) GS_TRY(q.alloc(c, rows));
     for (auto &q : b_agg) GS_TRY(q.alloc(c, agg_elems));
     GS_TRY(b_pwms.alloc(c, rows));
@@ -722,11 +930,21 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         } else {
             GS_TRY(b_cnt.alloc(c, n));
             GS_TRY(b_ctl.alloc(c, R));
-            if (mode == 0)
+            const bool batched = batched_starts(c);
+            if (batched) {
+                // lists of capacity 1: the starts' position slab is the chains' (the PWMS
+                // slab, free until the last sweep, takes the scores)
+                GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+                GS_TRY(s_err.alloc(c, R));
+                GS_TRY(s_erri.alloc(c, R));
+                GS_TRY(bs.enqueue(c, b_pwms, b_pos[0], s_err, s_erri));
+                HIP_TRY(c, gs_starts_batch_lists_launch(b_pos[0], rows, 1, nullptr, nullptr, R,
+                                                        s_err, s_erri, b_err, b_ctl, c->stream));
+            } else if (mode == 0)
                 GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
             else
                 GS_TRY(starts.draw(c, W, seeds, R));
-            for (int32_t r = 0; r < R; ++r) {
+            for (int32_t r = 0; !batched && r < R; ++r) {
                 GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
                 // lists of capacity 1 are the position rows; a chain that raised keeps its word
                 HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, 1, b_cnt,
@@ -777,6 +995,51 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return report_chain_errors(c, herr, status_out, nullptr);
+}
+
+// R independent getPWMOfRandomStarts runs (.fs:589-611), DESIGN.md §9.15: the launches of
+// BatchStarts on slabs of the call's own, one synchronisation, one download.  The fixed
+// PCV / PPM apply as in gs_random_starts.  The caller validated the arguments.
+int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
+                 double *score_out, int32_t *pos_out, int32_t *status_out) {
+    const int64_t n = c->n_local;
+    c->starts_batch_ms[0] = c->starts_batch_ms[1] = 0.0;
+    if (n == 0) return no_targets(R, nullptr, 0, status_out);
+    GS_TRY(ensure_state(c, W));
+    const int64_t cells = (int64_t)c->A * W + c->A;
+    // per chain: scores, starts, error words, seed (and the aggregate row); one group's cpart
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_random_starts_batch",
+        (int64_t)R * (n * (8 + 4) + 4 + 8 + 8 + (mode == 1 ? cells * 8 : 0)) +
+            (mode == 0 ? c->n_global * c->A * W * 4 : 0)));
+    DevBuf<double> score;
+    DevBuf<int32_t> pos, err;
+    DevBuf<unsigned long long> erri;
+    BatchStarts bs;
+    GS_TRY(score.alloc(c, R * n));
+    GS_TRY(pos.alloc(c, R * n));
+    GS_TRY(err.alloc(c, R));
+    GS_TRY(erri.alloc(c, R));
+    GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+    int rc = [&]() -> int {
+        GS_TRY(bs.enqueue(c, score, pos, err, erri, true));
+        GS_TRY(clear_ctx_error_words(c));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    scratch_used(c);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    bs.elapsed(c, c->starts_batch_ms);
+    std::vector<int32_t> herr((size_t)R);
+    std::vector<unsigned long long> hidx((size_t)R);
+    HIP_TRY(c, hipMemcpy(herr.data(), err, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hidx.data(), erri, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(score_out, score, (size_t)(R * n) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pos_out, pos, (size_t)(R * n) * 4, hipMemcpyDeviceToHost));
+    return report_chain_errors(c, herr, hidx, status_out);
 }
 
 }  // namespace gs_host

@@ -53,6 +53,7 @@ struct gs_tuning {
     int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
     int32_t run_batch_clear = 1;  // chain batch: the next aggregate rows zeroed by a memset before each sweep (0) or a third row cleared in-kernel (1: 1 - 3 % faster at 200 and 2 000 sequences)
     int32_t run_batch_blocks = 32;  // chain batch: cap on the one-wavefront workgroups per CU of its sweep launches (8 / 16 / 32, i.e. what fits: 18.1 / 12.6 / 11.3 ms for 64 chains x 200 sweeps x 200 sequences)
+    int32_t batch_starts = -1;  // batch drivers: the chains' starts chain after chain on the single-chain state (0), all chains in the launches of gs_random_starts_batch (1), or -1: the latter while a chain has fewer targets than a launch has workgroups (8 a CU), the size range where it measured faster; the results do not depend on it
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
     int32_t ftab_mode = 0;  // four-symbol sweep's workgroup tables: 0 built by every workgroup, 1 by a table kernel before the sweep, 2 handed over by the previous sweep's last workgroup (one GPU; else 1); 1 and 2 need the -DGS_FTAB build
     int32_t site_switch = 4;  // the same for the site sampler (cfg2: 4 / 16 / 2 -> 231 / 245 / 252 ms)
@@ -182,6 +183,32 @@ hipError_t gs_run_batch_agg_launch(const MultiArgs &a, const RunBatchArgs &b, in
 hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, int grid, size_t lds,
                                      hipStream_t s);
 hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds);
+// What gs_random_starts_batch adds to StartsArgs / PartialArgs (a second by-value kernel
+// argument, gs_starts.hip): the chains of one launch side by side, chain
+// r on row r of the score / position slabs and error words that the StartsArgs names.
+struct StartsBatchArgs {
+    const uint64_t *seeds;   // [n_chains]
+    int32_t n_chains;
+    int32_t blocks;          // aggregate pass: workgroups per chain
+    int32_t src;             // aggregate pass: starts all 0 (0), the shared draws (1), rows of pos (2)
+    int32_t E;
+    const int32_t *comp;     // [n_local][E+1] static symbol histograms
+    const int32_t *pos;      // aggregate pass, src 2: [n_chains][n_local]
+    int64_t *agg_out;        // aggregate pass: C then T of chain r at r * agg_out_chain, zeroed before
+    int64_t agg_out_chain;
+    int64_t agg_chain;       // scan: int64 between the chains' rows of StartsArgs::agg (0: one shared row)
+    int64_t cpart_chain;     // mode 0: int32 between the chains' slabs of cpart
+    int64_t n_pairs;         // scan: n_chains * n_local
+};
+hipError_t gs_starts_batch_agg_launch(const StartsArgs &a, const StartsBatchArgs &b, hipStream_t s);
+hipError_t gs_starts_batch_partial_launch(const PartialArgs &a, const StartsBatchArgs &b, int grid,
+                                          hipStream_t s);
+hipError_t gs_starts_batch_launch(const StartsArgs &a, const StartsBatchArgs &b, int grid,
+                                  size_t lds_bytes, hipStream_t s);
+hipError_t gs_starts_batch_lists_launch(const int32_t *pos, int64_t rows, int32_t cap, int32_t *cnt,
+                                        int32_t *lst, int32_t n_chains, const int32_t *err_code,
+                                        const unsigned long long *err_index,
+                                        unsigned long long *err, SpecCtl *ctl, hipStream_t s);
 hipError_t gs_single_lists_launch(const int32_t *pos, int32_t n, int32_t *cnt, int32_t *lst,
                                   int to_lists, hipStream_t s);
 hipError_t gs_count_diff_launch(const int32_t *a, const int32_t *b, int32_t n, int32_t *out,
@@ -296,6 +323,7 @@ struct gs_ctx {
     double site_batch_ms[3] = {0.0, 0.0, 0.0};  // the last site batch: starts, Gauss–Seidel launch, shifted passes
     double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
     double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
+    double starts_batch_ms[2] = {0.0, 0.0};  // the last gs_random_starts_batch: counts / aggregates, scans
     int32_t multi_batch_info[4] = {0, 0, 0, 0};  // ... sweep arena rounds, greedy restart rounds, chains restarted, slots
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG
@@ -395,6 +423,7 @@ struct MultiBufs {
 constexpr int64_t kArenaBudget = 4ll << 30;     // bytes of category arenas per launch
 constexpr int64_t kArenaMax = 1ll << 28;        // categories per target
 constexpr int64_t kBatchBytesMax = 4ll << 30;   // bytes of chain slabs per batch call
+constexpr int64_t kStartsCpartBudget = 256ll << 20;  // bytes of cpart slabs per group of chains (batched starts, mode 0)
 
 void drop_graphs(gs_ctx *c);
 void free_state(gs_ctx *c);
@@ -487,5 +516,7 @@ int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const
 int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
               int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
               double *pwms_out, int32_t *status_out);
+int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
+                 double *score_out, int32_t *pos_out, int32_t *status_out);
 
 }  // namespace gs_host

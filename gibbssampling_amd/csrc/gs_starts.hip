@@ -13,7 +13,10 @@
 // (0.0, 0): the first maximal window wins.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "gs_common.h"
+#include "gs_ctx.h"
 
 using namespace gs;
 
@@ -647,5 +650,244 @@ hipError_t gs_site_accept_launch(const double *tmp_score, const int32_t *tmp_pos
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(gs_site_accept_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tmp_score,
                        tmp_pos, score, pos, n, moved);
+    return hipGetLastError();
+}
+
+// ---- gs_random_starts_batch: getPWMOfRandomStarts of R chains at once ----
+//
+// Chain r owns row r of the score / position slabs and of the error words, slab r of
+// cpart (mode 0) and row r of the aggregates (mode 1; mode 0 reads one shared row: only
+// the composition totals are taken from it, and they do not depend on the draws).  The
+// (chain, target) pairs are linearised chain-major.
+
+// The start vectors' aggregates, row r of b.agg_out (zeroed before): C[a][j] the segment
+// counts, T[a] composition minus segment counts, summed in LDS, then one 64-bit atomic per
+// non-zero cell.  b.src 0: every start 0 (any valid vector gives mode 0 its totals), 1:
+// chain r's shared draws, 2: row r of b.pos.
+extern "C" __global__ void __launch_bounds__(256)
+gs_starts_batch_agg_kernel(StartsArgs a, StartsBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int64_t r = blockIdx.x / b.blocks;
+    const int j0 = blockIdx.x - (int)r * b.blocks;
+    const int A = a.A, W = a.W, AW = A * W, n = a.n_local, CS = b.E + 1;
+    unsigned long long *sT = (unsigned long long *)lds;  // [A]
+    int32_t *sC = (int32_t *)(lds + 8 * A);               // [A][W]
+    for (int c = threadIdx.x; c < AW; c += 256) sC[c] = 0;
+    for (int c = threadIdx.x; c < A; c += 256) sT[c] = 0ull;
+    __syncthreads();
+    const uint64_t seed = b.src == 1 ? b.seeds[r] : 0;
+    for (int64_t i = (int64_t)j0 * 256 + threadIdx.x; i < n; i += (int64_t)b.blocks * 256) {
+        int q = 0;
+        if (b.src == 1)
+            q = uniform_int(seed, stream_init_shared(), (uint64_t)(a.global_offset + i),
+                            a.len[i] - W + 1);
+        if (b.src == 2) q = b.pos[r * n + i];
+        const uint8_t *s = a.seq + a.doff[i] + q;
+        for (int j = 0; j < W; ++j) {
+            const int e = s[j];
+            if (e < A) {
+                atomicAdd(&sC[e * W + j], 1);
+                atomicAdd(&sT[e], ~0ull);
+            }
+        }
+        for (int x = 0; x < A; ++x)
+            atomicAdd(&sT[x], (unsigned long long)(long long)b.comp[i * CS + x]);
+    }
+    __syncthreads();
+    unsigned long long *g = (unsigned long long *)(b.agg_out + r * b.agg_out_chain);
+    for (int c = threadIdx.x; c < AW; c += 256)
+        if (sC[c]) atomicAdd(&g[c], (unsigned long long)(long long)sC[c]);
+    for (int c = threadIdx.x; c < A; c += 256)
+        if (sT[c]) atomicAdd(&g[AW + c], sT[c]);
+}
+
+// gs_starts_partial_kernel over the (chain, target) items of b.n_chains chains: the draws
+// of chain r's seed, into slab r of a.cpart (every cell is written: no memset before).
+extern "C" __global__ void __launch_bounds__(64)
+gs_starts_batch_partial_kernel(PartialArgs a, StartsBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    int32_t *cnt = (int32_t *)lds;
+    const int lane = threadIdx.x;
+    const int AW = a.A * a.W;
+    const int64_t items = (int64_t)b.n_chains * a.n_global;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int64_t r = it / a.n_global, t = it - r * a.n_global;
+        const uint64_t seed = b.seeds[r];
+        for (int c = lane; c < AW; c += 64) cnt[c] = 0;
+        __syncthreads();
+        const uint64_t st = stream_init((uint64_t)t);
+        for (int m = lane; m < a.n_local; m += 64) {
+            const int64_t mg = a.global_offset + m;
+            if (mg == t) continue;
+            const int L = a.len[m];
+            const int q = uniform_int(seed, st, (uint64_t)mg, L - a.W + 1);
+            const uint8_t *s = a.seq + a.doff[m] + q;
+            for (int j = 0; j < a.W; ++j) {
+                const int e = s[j];
+                if (e < a.A) atomicAdd(&cnt[e * a.W + j], 1);
+            }
+        }
+        __syncthreads();
+        int32_t *out = a.cpart + r * b.cpart_chain + t * AW;
+        for (int c = lane; c < AW; c += 64) out[c] = cnt[c];
+        __syncthreads();
+    }
+}
+
+// gs_starts_kernel's mode 0 / 1 body over the pairs of b.n_chains chains: workgroup w
+// takes the contiguous pairs [w * per, (w + 1) * per), so that it rebuilds the chain's
+// prologue (C, composition totals) only where its chain changes, in mode 0 (one shared
+// row) once.  a's score / position / error pointers name row 0; a.seed is not read.
+template <bool GD>
+__global__ void __launch_bounds__(64) gs_starts_batch_kernel(StartsArgs a, StartsBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int lane = threadIdx.x;
+    const int A = a.A, W = a.W, AW = A * W;
+    double *ppm = (double *)(lds + a.o_ppm);            // [A][W]
+    int32_t *Dt = GD ? a.dt_global + (int64_t)blockIdx.x * a.dt_stride
+                     : (int32_t *)(lds + a.o_Dt);       // [Lmax+1][A]
+    int32_t *cg = (int32_t *)(lds + a.o_cg);            // [A*W] + [A*W] scratch
+    int64_t *compall = (int64_t *)(lds + a.o_compall);  // [A]
+    int64_t *bg0 = (int64_t *)(lds + a.o_bg);           // [A]
+    int32_t *comp = (int32_t *)(lds + a.o_comp);        // [128]
+    uint8_t *sseq = (uint8_t *)(lds + a.o_seq);
+
+    const int64_t per = (b.n_pairs + gridDim.x - 1) / gridDim.x;
+    const int64_t p0 = (int64_t)blockIdx.x * per;
+    const int64_t p1 = p0 + per < b.n_pairs ? p0 + per : b.n_pairs;
+    int64_t cur = -1;
+    for (int64_t p = p0; p < p1; ++p) {
+        const int64_t ch = p / a.n_local;
+        const int n = (int)(p - ch * a.n_local);
+        if (ch != cur) {
+            if (cur < 0 || b.agg_chain != 0) {
+                const int64_t *agg = a.agg + ch * b.agg_chain;
+                for (int c = lane; c < AW + A; c += 64) {
+                    const int64_t s = agg[c];
+                    if (c < AW)
+                        cg[c] = (int32_t)s;
+                    else
+                        compall[c - AW] = s;  // Σ (composition - segment) over the start vector
+                }
+                __syncthreads();
+                // composition totals: the background cells plus the segments' counts
+                if (lane < A) {
+                    int64_t s = 0;
+                    for (int j = 0; j < W; ++j) s += cg[lane * W + j];
+                    compall[lane] += s;
+                }
+                __syncthreads();
+            }
+            cur = ch;
+        }
+        const uint64_t seed = b.seeds[ch];
+        const int L = a.len[n];
+        const int K = L - W + 1;
+        const int64_t gidx = a.global_offset + n;
+        stage_sequence(a.seq + a.doff[n], L, sseq, comp, lane);
+
+        // ---- others' count matrix and background (.fs:599-609) ----
+        int r = 0;
+        if (a.mode == 1) r = uniform_int(seed, stream_init_shared(), (uint64_t)gidx, K);
+        const int32_t *cpart = a.cpart + ch * b.cpart_chain + gidx * AW;
+        for (int c = lane; c < AW; c += 64) {
+            const int x = c / W, j = c - x * W;
+            int32_t v;
+            if (a.mode != 0)
+                v = cg[c] - (sseq[r + j] == x ? 1 : 0);
+            else
+                v = cpart[c];
+            // normalizePPM (.fs:257-260), or the caller's PPM (.fs:644-662)
+            ppm[c] = a.ppm_fixed ? a.ppm_fixed[c] : ((double)v + a.pc) / a.den;
+            cg[AW + c] = v;
+        }
+        __syncthreads();
+        int64_t bsum = 0;
+        if (lane < A) {
+            int64_t s = 0;
+            for (int j = 0; j < W; ++j) s += cg[AW + lane * W + j];
+            // Σ_{m≠n} (comp_m − comp(seg_m))[a] = (Σ_all comp − comp_n)[a] − Σ_j C_{−n}[a][j]
+            const int64_t v = compall[lane] - comp[lane] - s;
+            bg0[lane] = v;
+            bsum = v;
+        }
+        bsum = wave_sum_i64(bsum);
+        __syncthreads();
+        double best;
+        int bestk;
+        bool overflow;
+        best_pwms_scan(sseq, L, W, A, ppm, bg0, bsum, comp, Dt, a.pc, a.apc, a.pcv_fixed, lane,
+                       best, bestk, overflow);
+        if (overflow) {  // (.fs:117): chain ch's error words; its position row keeps 0
+            if (lane == 0) {
+                atomicCAS(a.err_code + ch, 0, 3);
+                atomicMin(a.err_index + ch, (unsigned long long)gidx);
+            }
+            continue;
+        }
+        if (lane == 0) {
+            a.pos_out[ch * a.n_local + n] = bestk;
+            a.score_out[ch * a.n_local + n] = log(best) / kLn2;
+        }
+    }
+}
+
+// The chains' starts (rows of pos) as the list slabs of the list and chain batches:
+// cnt = 1, lst[0] = start, the rest -1 (cnt / lst null: the position slab is the list
+// slab, capacity 1).  The two error words of chain r's starts become its packed word; a
+// chain that raised there (.fs:117) is done for every later kernel.
+extern "C" __global__ void __launch_bounds__(256)
+gs_starts_batch_lists_kernel(const int32_t *pos, int64_t rows, int32_t cap, int32_t *cnt,
+                             int32_t *lst, int32_t n_chains, const int32_t *err_code,
+                             const unsigned long long *err_index, unsigned long long *err,
+                             SpecCtl *ctl) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (lst)
+        for (int64_t i = tid; i < rows; i += step) {
+            cnt[i] = 1;
+            lst[i * cap] = pos[i];
+            for (int j = 1; j < cap; ++j) lst[i * cap + j] = -1;
+        }
+    for (int64_t r = tid; r < n_chains; r += step) {
+        const int code = err_code[r];
+        err[r] = code ? (err_index[r] << 4) | (unsigned long long)(code & 15) : ~0ull;
+        if (ctl) ctl[r] = SpecCtl{0, 0, 0, code != 0};
+    }
+}
+
+hipError_t gs_starts_batch_agg_launch(const StartsArgs &a, const StartsBatchArgs &b,
+                                      hipStream_t s) {
+    if (b.n_chains <= 0 || a.n_local <= 0) return hipSuccess;
+    if (b.blocks < 1 || (int64_t)b.n_chains * b.blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gs_starts_batch_agg_kernel, dim3(b.n_chains * b.blocks), dim3(256),
+                       (size_t)a.A * (8 + 4 * a.W), s, a, b);
+    return hipGetLastError();
+}
+hipError_t gs_starts_batch_partial_launch(const PartialArgs &a, const StartsBatchArgs &b, int grid,
+                                          hipStream_t s) {
+    if (b.n_chains <= 0 || a.n_local <= 0 || grid < 1) return hipSuccess;
+    hipLaunchKernelGGL(gs_starts_batch_partial_kernel, dim3(grid), dim3(64),
+                       (size_t)a.A * a.W * sizeof(int32_t), s, a, b);
+    return hipGetLastError();
+}
+// grid: at most the slots of a.dt_global when the D table is in HBM.
+hipError_t gs_starts_batch_launch(const StartsArgs &a, const StartsBatchArgs &b, int grid,
+                                  size_t lds_bytes, hipStream_t s) {
+    if (b.n_pairs <= 0 || grid < 1) return hipSuccess;
+    if (a.dt_global)
+        hipLaunchKernelGGL(gs_starts_batch_kernel<true>, dim3(grid), dim3(64), lds_bytes, s, a, b);
+    else
+        hipLaunchKernelGGL(gs_starts_batch_kernel<false>, dim3(grid), dim3(64), lds_bytes, s, a, b);
+    return hipGetLastError();
+}
+hipError_t gs_starts_batch_lists_launch(const int32_t *pos, int64_t rows, int32_t cap, int32_t *cnt,
+                                        int32_t *lst, int32_t n_chains, const int32_t *err_code,
+                                        const unsigned long long *err_index,
+                                        unsigned long long *err, SpecCtl *ctl, hipStream_t s) {
+    if (n_chains <= 0) return hipSuccess;
+    const int64_t work = lst ? std::max<int64_t>(rows, n_chains) : n_chains;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 4096));
+    hipLaunchKernelGGL(gs_starts_batch_lists_kernel, dim3(grid), dim3(256), 0, s, pos, rows, cap, cnt,
+                       lst, n_chains, err_code, err_index, err, ctl);
     return hipGetLastError();
 }

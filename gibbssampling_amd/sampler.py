@@ -466,6 +466,21 @@ class SiteSampler:
         return _pairs(score, pos)
 
     @staticmethod
+    def getPWMOfRandomStartsBatched(motifLength: int, pseudoCount: float, alphabet, sources,
+                                    seeds, init_mode: int = 0, device: int = 0):
+        """One getPWMOfRandomStarts per seed, all in one Context.random_starts_batch call:
+        entry r is getPWMOfRandomStarts(..., seeds[r], init_mode).  A chain that raised
+        raises here.  Faster than the loop at every measured size."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        ctx = _bind(alphabet, sources, device)
+        score, pos, status = ctx.random_starts_batch(motifLength, pseudoCount, seeds, init_mode)
+        for r, st in enumerate(status):
+            if st != _native.GS_OK:
+                raise _native._ERRORS.get(int(st), _native.DeviceError)(
+                    int(st), f"chain {r} of the batch failed")
+        return [_pairs(score[r], pos[r]) for r in range(len(seeds))]
+
+    @staticmethod
     def _refine(shift: int, motifLength: int, pseudoCount: float, alphabet, sources,
                 startPositions, max_passes: int, device: int):
         if len(startPositions) != len(sources):

@@ -258,6 +258,25 @@ int gs_counts(gs_ctx *ctx, int32_t W, const int32_t *pos, int64_t *C_out, int64_
 int gs_random_starts(gs_ctx *ctx, int32_t W, double pseudo_count, uint64_t seed, int32_t mode,
                      double *score_out, int32_t *pos_out);
 
+/* R independent getPWMOfRandomStarts runs (.fs:589-611): chain r is exactly
+ * gs_random_starts(ctx, W, pc, seeds[r], mode, row r, row r), every chain in the same
+ * launches over the (chain, target) pairs: the counts (mode 0) or the aggregates of the
+ * shared draws (mode 1), then the scans; one synchronisation.  It follows gs_set_fixed_pcv /
+ * gs_set_fixed_ppm as gs_random_starts does.  n_chains == 0 does nothing.  Returns the status
+ * of the lowest-index failing chain (gs_error_index: its sequence), GS_OK if none: a chain
+ * that raises (.fs:117) keeps its status in status_out[r] and its rows unspecified (its
+ * starts stay valid ones), the other rows are valid.  GS_E_ARG before any launch: a bad W or
+ * mode, a null seeds or output, a fixed PPM of another W.  GS_E_UNSUPPORTED: sharded
+ * sequences or a communicator, chain slabs beyond 4 GiB.  The context holds no snapshot
+ * afterwards and its error words are clear. */
+int gs_random_starts_batch(gs_ctx *ctx, int32_t W, double pseudo_count, const uint64_t *seeds,
+                           int32_t n_chains, int32_t mode,
+                           double *score_out,   /* [n_chains][n_local] */
+                           int32_t *pos_out,    /* [n_chains][n_local] */
+                           int32_t *status_out  /* [n_chains], nullable */);
+/* Device times of the last gs_random_starts_batch, ms: counts / aggregates, scans. */
+int gs_starts_batch_last_ms(const gs_ctx *ctx, double out[2]);
+
 /* SiteSampler.getBestPWMSs (.fs:462-479) of local sequence `target` against the
  * caller's background counts fcv49 (FrequencyCompositeVector, 49 slots by
  * code - 42) and position probability matrix ppm49 (49 slot rows x W, row-major),
@@ -413,6 +432,9 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots, multi_batch_fill,
  * run_batch_clear (gs_motif_run_batch: 0 a memset of the next aggregate rows before each
  * sweep, 1 a third row cleared in-kernel), run_batch_blocks (its workgroups per CU),
+ * batch_starts (the four batched drivers' starts: 0 chain after chain on the single-chain
+ * state, 1 all chains in the launches of gs_random_starts_batch, -1 automatic: 1 while the
+ * sequences are fewer than 8 per compute unit, the size range where it measured faster),
  * greedy_switch, site_switch.  GS_E_ARG for an unknown name or a value out of
  * range.  Set before gs_set_sequences (launch geometry is fixed there). */
 int gs_set_tuning(gs_ctx *ctx, const char *name, double value);
