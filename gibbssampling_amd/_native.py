@@ -48,6 +48,7 @@ TUNING_ALIASES = {
     "GS_GREEDY_WAVES": "greedy_waves", "GS_MULTI_GREEDY_THREADS": "multi_greedy_threads",
     "GS_MULTI_SPEC_SLOTS": "multi_spec_slots", "GS_GREEDY_SWITCH": "greedy_switch",
     "GS_SITE_SWITCH": "site_switch", "GS_MULTI_BATCH_FILL": "multi_batch_fill",
+    "GS_SWEEP_ONE": "sweep_one",
 }
 
 
@@ -181,6 +182,7 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_stats": (C.c_int, [vp, vp, i32]),
         "gs_sweep_kernel_name": (C.c_char_p, [vp]),
         "gs_last_sweep_launch": (C.c_int, [vp, vp]),
+        "gs_last_sweep_one": (C.c_int, [vp]),
         "gs_set_scan_mode": (C.c_int, [vp, i32]),
         "gs_fastmath_check": (C.c_int, [vp, P(f64), P(f64)]),
         "gs_agg_size": (i64, [vp]),
@@ -722,10 +724,14 @@ class Context:
 
     def last_sweep_launch(self) -> dict:
         """The last gs_sweep_kernel launch: its EK (4 = the four-symbol kernel), lanes per
-        sequence, wavefronts per workgroup, workgroups (include/gibbs_hip.h)."""
+        sequence, wavefronts per workgroup, workgroups, and `one`: 1 when it took the
+        four-symbol kernel's one-iteration path (include/gibbs_hip.h)."""
         v = np.zeros(4, np.int32)
         self._check(self.lib.gs_last_sweep_launch(self.h, _ptr(v)))
-        return dict(zip(("ek", "gl", "waves", "grid"), (int(x) for x in v)))
+        out = dict(zip(("ek", "gl", "waves", "grid"), (int(x) for x in v)))
+        # (an older build loaded by path for an A/B run has no such path)
+        out["one"] = int(self.lib.gs_last_sweep_one(self.h)) if hasattr(self.lib, "gs_last_sweep_one") else 0
+        return out
 
     def stats(self) -> dict:
         """Cumulative fallback counters (include/gibbs_hip.h gs_stats)."""

@@ -54,6 +54,7 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(site_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(ftab_mode, v == 0 || v == 1 || v == 2),
+    GS_TUNING_FIELD(sweep_one, v == -1 || v == 0 || v == 1),
 };
 #undef GS_TUNING_FIELD
 const int kTuningFieldCount = (int)(sizeof(kTuningFields) / sizeof(kTuningFields[0]));
@@ -1158,6 +1159,8 @@ int gs_last_sweep_launch(const gs_ctx *c, int32_t *out) {
     for (int i = 0; i < 4; ++i) out[i] = c->last_sweep[i];
     return GS_OK;
 }
+
+int gs_last_sweep_one(const gs_ctx *c) { return c ? c->last_sweep[4] : 0; }
 
 int gs_stats(gs_ctx *c, int64_t *out, int32_t n) {
     if (!c || !out || n < 0) return GS_E_ARG;

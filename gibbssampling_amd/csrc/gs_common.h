@@ -169,6 +169,9 @@ struct SweepArgs {
     // (binary32 log2 PPM', code-major rows of mt_stride(WM) entries), its fixed-point
     // prefix sums of the positions' log2 PCV at w_pfx + gi * pfx_bytes (= lt_bytes)
     int32_t w_pfx, pfx_bytes;
+    // EK = 4: no wavefront of the launch has more than 64 / gl slots, so the kernel's
+    // one-iteration instantiation runs (gs_engine.cpp launch_sweep decides)
+    int32_t one;
 };
 // bytes of one workgroup-table image (ek4_layout o_wave at WM = 32, rounded up)
 constexpr int kFtabBytes = 8192;

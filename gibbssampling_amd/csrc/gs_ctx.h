@@ -56,6 +56,7 @@ struct gs_tuning {
     int32_t batch_starts = -1;  // batch drivers: the chains' starts chain after chain on the single-chain state (0), all chains in the launches of gs_random_starts_batch (1), or -1: the latter while a chain has fewer targets than a launch has workgroups (8 a CU), the size range where it measured faster; the results do not depend on it
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
     int32_t ftab_mode = 0;  // four-symbol sweep's workgroup tables: 0 built by every workgroup, 1 by a table kernel before the sweep, 2 handed over by the previous sweep's last workgroup (one GPU; else 1); 1 and 2 need the -DGS_FTAB build
+    int32_t sweep_one = -1;  // four-symbol sweep's one-iteration path (no wavefront of the launch has more than 64 / lanes-per-sequence sequences): -1 whenever that holds, 0 never (the loop path), 1 required (GS_E_ARG from the sweep where it does not hold); the results do not depend on it
     int32_t site_switch = 4;  // the same for the site sampler (cfg2: 4 / 16 / 2 -> 231 / 245 / 252 ms)
 };
 
@@ -308,7 +309,7 @@ struct gs_ctx {
     // gs_sweep_kernel blocks per CU for the last (W, E, lanes, waves, LDS) asked: a host
     // API call per sweep costs about as much as a short sweep
     int sweep_occ = 0;
-    int32_t last_sweep[4] = {0, 0, 0, 0};  // gs_last_sweep_launch: ek, lanes, waves, grid
+    int32_t last_sweep[5] = {0, 0, 0, 0, 0};  // gs_last_sweep_launch: ek, lanes, waves, grid, one-iteration path
     int dna_occ[3] = {0, 0, 0}, dna_occ_W = 0;  // gs_sweep_dna_kernel by G (1, 2, 4), for W
     int64_t sweep_occ_key[6] = {-1, -1, -1, -1, -1, -1};  // gs_sweep_live_kernel blocks per CU by G (1, 2, 4, 8) x WM, waves (8, 4, 2, 1)
     int32_t max_lds = 0, n_cu = 0;

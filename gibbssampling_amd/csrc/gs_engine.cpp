@@ -344,6 +344,19 @@ int launch_sweep(gs_ctx *c, int mode, double pc, double cutoff, const double *u_
     const int64_t waves_needed = (c->n_local + 64 / gl - 1) / (64 / gl);
     const int64_t blocks_needed = (waves_needed + waves - 1) / waves;
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks_needed, (int64_t)c->n_cu * per_cu));
+    // the four-symbol kernel's one-iteration path (gs_sweep.hip ONE): no wavefront of
+    // this grid has more sequences than its 64 / gl groups score at a time (the kernel
+    // splits n_local evenly over the grid's wavefronts, gs_sweep_launch)
+    const int64_t grid_waves = (int64_t)grid * waves;
+    const bool one_fits = gs_sweep_ek(a) == 4 && (c->n_local + grid_waves - 1) / grid_waves <= 64 / gl;
+    if (c->tune.sweep_one == 1 && mode == 0 && !one_fits)  // (never a launch)
+        return fail(c, GS_E_ARG,
+                    gs_sweep_ek(a) == 4
+                        ? "sweep_one 1: " + std::to_string(c->n_local) + " sequences on " +
+                              std::to_string(grid_waves) + " wavefronts of " + std::to_string(64 / gl) +
+                              " groups need a second iteration (gs_set_tuning)"
+                        : std::string("sweep_one 1: this sweep does not run the four-symbol kernel (gs_set_tuning)"));
+    a.one = one_fits && c->tune.sweep_one != 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timed = c->prof && mode == 0 && (c->prof_sweep_calls++ % c->prof_stride) == 0;
     if (timed) {  // kernel-attached events: the dispatch's own start / stop times
@@ -381,6 +394,7 @@ int launch_sweep(gs_ctx *c, int mode, double pc, double cutoff, const double *u_
     c->last_sweep[1] = gl;
     c->last_sweep[2] = waves;
     c->last_sweep[3] = grid;
+    c->last_sweep[4] = a.one;
     if (timed) c->ev_sweep.emplace_back(e0, e1);
     return GS_OK;
 }

@@ -66,6 +66,16 @@ __device__ __forceinline__ KSweepArgs *kargs() {
     return (KSweepArgs *)p;
 }
 #define KA(f) (kargs()->f)
+// The same inside gs_sweep_kernel: its one-iteration path (ONE) reads the segment
+// pointer as it is.  Straight-line code has no loop to hoist the loads out of (it keeps
+// no SGPR spill without the laundering), and with it the backend fails there ("illegal
+// VGPR to SGPR copy" at the asm).
+template <bool LAUNDER>
+__device__ __forceinline__ KSweepArgs *kargs_k() {
+    if constexpr (LAUNDER) return kargs();
+    return (KSweepArgs *)(uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+}
+#define KAK(f) (kargs_k<!ONE>()->f)
 
 // log2 of a binary64 value as the certified scan's tables take it, out of line: its
 // polynomial constants stay out of the per-sequence loop's registers (the rare
@@ -579,7 +589,13 @@ __device__ __attribute__((noinline)) RxOut rescan_group_h1(KSweepArgs *ka_in, in
 // E is a compile-time constant, a symbol is its pair code's low two bits, and the
 // per-sequence table build runs with static trip counts (every LDS read of a lane
 // issued before the first is consumed).  EK = 0: E from the arguments.
-template <int WM, int H, int GL, int EK>
+// ONE (EK = 4 only): no wavefront of the launch has more than G = 64 / GL slots (the
+// host's dispatch, gs_engine.cpp launch_sweep), so each group scores its one sequence in
+// straight-line code: its lanes load their own slot's descriptor, position and uniform
+// (no 64-slot batch in lane registers, no permutes out of it), nothing is prefetched,
+// and the group's first lane stores the result itself (no res[] round trip through LDS).
+// The per-sequence math is the loop's own body, run once.
+template <int WM, int H, int GL, int EK, bool ONE = false>
 __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int G = 64 / GL;
@@ -591,6 +607,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     const int gi = lane / GL, li = lane & (GL - 1), gbase = lane & ~(GL - 1);
 
     static_assert(EK == 0 || (EK == 4 && H == 2), "EK = 4 is the pair-table DNA path");
+    static_assert(!ONE || EK == 4, "the one-iteration path is the four-symbol kernel's");
     // EK = 4 kernels run for W == WM only (gs_sweep_ek): the motif width is static too
     const int A = EK ? EK : a.A, E = EK ? EK : a.E, W = EK ? WM : a.W, AW = A * W, CS = E + 1,
               E2 = E * E;
@@ -777,7 +794,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         const int nb = wn0 + k;
         const unsigned long long oob = __ballot(v && (unsigned)nb >= (unsigned)a.n_local);
         if (oob && lane == 0)  // audit, gs_stats [13]
-            atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
+            atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
                       (unsigned long long)__popcll(oob));
         if (v) {
             ln = a.len[nb];
@@ -796,7 +813,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         const int nb = n0 + i * wstride;
         const unsigned long long oob = __ballot(i < cnt && (unsigned)nb >= (unsigned)a.n_local);
         if (oob && lane == 0)  // audit, gs_stats [13] (as the first descriptors' below)
-            atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
+            atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
                       (unsigned long long)__popcll(oob));
         if (i < cnt) {
             b_len = a.len[nb];
@@ -821,6 +838,29 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             if (li < CS) cpf = a.comp[(int64_t)(wn0 + cu * G + gi) * CS + li];
         }
         if (tid == 0) *wctr = 2u * (unsigned)kWavesPerBlock;  // (read after the prologue's barrier)
+    } else if constexpr (ONE) {
+        // every lane of group gi loads slot gi's own values (one address a group): the
+        // descriptor first (equal lengths: none), so that the sequence's load waits for
+        // it alone, then the snapshot position and the uniform
+        const bool rd = gi < cnt;
+        const int nb = n0 + gi;
+        const unsigned long long oob = __ballot(rd && li == 0 && (unsigned)nb >= (unsigned)a.n_local);
+        if (oob && lane == 0)  // audit, gs_stats [13] (as the loop path's descriptors')
+            atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
+                      (unsigned long long)__popcll(oob));
+        if (a.seq_stride > 0) {
+            b_len = a.Lmax;
+            b_off = (int64_t)nb * a.seq_stride;
+        } else if (rd) {
+            b_len = a.len[nb];
+            b_off = a.doff[nb];
+        }
+        if (rd) {
+            b_pos = a.pos_in[nb];
+            b_u = a.u_in ? a.u_in[nb] : uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + nb));
+            if (b_len <= 16 * GL && li * 16 < b_len) pf = *(const uint4 *)(gseq + b_off + li * 16);
+            if (li < CS) cpf = a.comp[(int64_t)nb * CS + li];
+        }
     } else {
         int dl = 0;
         int64_t dof = 0;
@@ -844,7 +884,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // read before or past the arrays; the tests require none
             const unsigned long long oob = __ballot(rd && (unsigned)ng >= (unsigned)a.n_local);
             if (oob && lane == 0)
-                atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
+                atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
                           (unsigned long long)__popcll(oob));
             Ln = bperm_i32(dl, gi);
             on = bperm_i64(dof, gi);
@@ -854,7 +894,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             if (li < CS) cpf = a.comp[(int64_t)(n0 + gi * wstride) * CS + li];
         }
     }
-    if constexpr (!kDyn) load_batch(0);
+    if constexpr (!kDyn && !ONE) load_batch(0);
     TLP(tl_w, 2);
 
     // ---- prologue: aggregates of the snapshot (sum of the replicas) ----
@@ -907,7 +947,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     for (int c = lane; c < AW; c += 64) aggC[c] = 0;
     if (lane < A) aggT[lane] = 0;
     if (blockIdx.x == 0) {
-        int64_t *const agg_zero = KA(agg_zero);
+        int64_t *const agg_zero = KAK(agg_zero);
         if (agg_zero)
             for (int i = tid; i < kRepl * a.stride; i += kSweepThreads) agg_zero[i] = 0;
     }
@@ -1012,7 +1052,9 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     const double epsG1 = (double)W * (0x1.0p-24 + lv);        // epsG = epsG0 + epsG1 * tG
     STAMP(0);
 
-    for (int it = 0; kDyn ? cu < nunits : it < nit; ++it) {
+    // (ONE: at most one trip, a branch around the straight-line body for a wavefront
+    // without sequences)
+    for (int it = 0; kDyn ? cu < nunits : ONE ? (it < 1 && cnt > 0) : it < nit; ++it) {
         const int s = kDyn ? cu * G + gi : it * G + gi;  // this group's slot (kDyn: in the workgroup's range)
         const bool act = s < (kDyn ? wcnt : cnt);
         const int bsl = s & 63;
@@ -1025,6 +1067,9 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             n = wn0 + s;
             if (mode == 0 && act)
                 u = a.u_in ? a.u_in[n] : uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + n));
+        } else if constexpr (ONE) {
+            Lr = b_len, pr = b_pos, off = b_off, u = b_u;  // the group's own slot
+            n = n0 + s;
         } else {
             // (every lane permutes: ds_bpermute reads 0 from a lane that is switched off,
             // and the source lanes belong to other groups)
@@ -1078,7 +1123,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 if (n_len <= 16 * GL && lo16 < n_len) pf = *(const uint4 *)(gseq + n_off + lo16);
                 if (lc < CS) cpf = a.comp[(int64_t)(wn0 + kn) * CS + lc];
             }
-        } else {
+        } else if constexpr (!ONE) {
             const int sn = s + G;
             if ((((it + 1) * G) & 63) == 0 && (it + 1) * G < cnt) load_batch((it + 1) * G);
             const int bn = sn & 63;
@@ -1515,7 +1560,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // the factors, the folds and the batch end's log.  The kind = -6 recheck
             // below lives in the fold and goes with it on those sweeps: it cannot fire
             // while the certified bound holds (gs_stats [3] stays 0).
-            const bool pwms_on = KA(pwms_out) != nullptr;
+            const bool pwms_on = KAK(pwms_out) != nullptr;
             if (pwms_on && kind >= 0) {
                 for (int j = li; j < W; j += GL) {
                     const int e = sym(sseq[pk + j]);
@@ -1540,7 +1585,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 if (kind == 0) {
                     pw = Gp;
                 } else if (kind == 1) {
-                    if (S > KA(thr_hi)) {
+                    if (S > KAK(thr_hi)) {
                         pw = S;  // certainly log2 S > cutOff: log2 taken at the batch end
                         pw_log = true;
                     } else {
@@ -1551,9 +1596,9 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             }
             // statistics of undecided groups (one lane per group)
             if (keep && kind < 0 && li == 0) {
-                atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[0], 1ull);
+                atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[0], 1ull);
                 const int why = !fast ? 2 : kind == -6 ? 3 : 3 - kind;
-                atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[why], 1ull);
+                atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[why], 1ull);
             }
             STAMP(6);
             // ---- binary64 rescans, one group at a time on the whole wavefront ----
@@ -1598,7 +1643,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     for (int c = lane; c < E * WS; c += 64)
                         if (c % WS >= W) *(double2 *)(tab + c * 16) = make_double2(1.0, 1.0);
                 wave_sync();
-                const double thr_lo = KA(thr_lo);
+                const double thr_lo = KAK(thr_lo);
                 auto evx = [&](int k, double &g, double &m) {
                     exact_eval<WM, H == 1>(sx, tab, thr_lo, a.cutoff, k, g, m);
                 };
@@ -1628,7 +1673,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     // windows re-evaluated in the reference's order: two summing
                     // passes (backgrounds, then motif scores), two walking passes
                     if (lane == 0) {
-                        atomicAdd(&(KA(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[1], 1ull);
+                        atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[1], 1ull);
                         double sacc = 0.0, acc = 0.0;
                         int rk = -1, rp = -1;
                         for (int pass = 0; pass < 4 && rk < 0; ++pass) {
@@ -1702,11 +1747,22 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 keep = false;
             }
             newp = kind == 0 ? -1 : pk;
+            // (ONE: the output pointers read by the whole wavefront, scalar loads)
+            int32_t *const pos_o = ONE ? KAK(pos_out) : nullptr;
+            double *const pwms_o = ONE ? KAK(pwms_out) : nullptr;
             if (keep && li == 0) {
                 if constexpr (kDyn) {  // stored now (.fs:737's log2 for a motif pick)
-                    KA(pos_out)[n] = newp;
+                    KAK(pos_out)[n] = newp;
                     if (pwms_on)
-                        KA(pwms_out)[n] = pw_log ? log_ool(pw * 1.0) / kLn2 : pw;  // (H = 1: the log out of line)
+                        KAK(pwms_out)[n] = pw_log ? log_ool(pw * 1.0) / kLn2 : pw;  // (H = 1: the log out of line)
+                } else if constexpr (ONE) {  // stored now, the batch end's operations
+                    const double v = pw_log ? log(pw * 1.0) / kLn2 : pw;  // .fs:737
+#ifndef GS_DIAG_NOOUT
+                    pos_o[n] = newp;
+                    if (pwms_o) pwms_o[n] = v;
+#else
+                    asm volatile("" ::"v"(newp), "v"(v), "s"(pos_o), "s"(pwms_o));
+#endif
                 } else {
                     res[bsl] = SweepResult{newp, pw_log ? 1 : 0, pw};
                 }
@@ -1726,18 +1782,18 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             }
             if (li < A) atomicAdd((unsigned long long *)&aggT[li], (unsigned long long)my_comp);
         }
-        wave_sync();
+        if constexpr (!ONE) wave_sync();  // (ONE: the flush's barrier follows)
         STAMP(9);
         // ---- results of a full batch (or the last one): log2, then 64 stores ----
-        if (!kDyn && ((((it + 1) * G) & 63) == 0 || (it + 1) * G >= cnt)) {
+        if (!kDyn && !ONE && ((((it + 1) * G) & 63) == 0 || (it + 1) * G >= cnt)) {
             const int i = ((it * G) & ~63) + lane;
             if (mode == 0 && i < cnt) {
                 const SweepResult r = res[lane];
-                double *const pwo = KA(pwms_out);  // (null: this sweep's PWMS are not wanted)
+                double *const pwo = KAK(pwms_out);  // (null: this sweep's PWMS are not wanted)
                 const double v = r.log ? log(r.pw * 1.0) / kLn2 : r.pw;  // .fs:737 (log: never without PWMS)
                 const int nb = n0 + i * wstride;
 #ifndef GS_DIAG_NOOUT  // (traffic attribution builds only: the results are not stored)
-                KA(pos_out)[nb] = r.pos;
+                KAK(pos_out)[nb] = r.pos;
                 if (pwo) pwo[nb] = v;
 #else
                 asm volatile("" ::"v"(r.pos), "v"(v));
@@ -1756,16 +1812,16 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // the rest of the chain with gs_sweep_bg_kernel once it is.  Evaluated at the end
     // (workgroup 0, dispatched first), on the snapshot tables still in LDS; ppmG is
     // its scratch
-    if (blockIdx.x == 0 && mode == 0 && KA(bg_note)) {
+    if (blockIdx.x == 0 && mode == 0 && KAK(bg_note)) {
         __syncthreads();
-        const bool bg = bg_regime(cg, T, A, W, a.pc, a.den, a.apc, KA(Lmax), KA(cmin), a.cutoff, ppmG, tid);
-        if (tid == 0) *KA(bg_note) = bg ? 1 : 0;
+        const bool bg = bg_regime(cg, T, A, W, a.pc, a.den, a.apc, KAK(Lmax), KAK(cmin), a.cutoff, ppmG, tid);
+        if (tid == 0) *KAK(bg_note) = bg ? 1 : 0;
     }
     // ---- flush: sum the 4 wavefronts' aggregates, one atomic per cell ----
     __syncthreads();
     STAMP(11);
     STAMP_FLUSH(nseq_done);
-    int64_t *dst = KA(agg_out) + (int64_t)(blockIdx.x % kRepl) * a.stride;
+    int64_t *dst = KAK(agg_out) + (int64_t)(blockIdx.x % kRepl) * a.stride;
     for (int c = tid; c < a.cells; c += kSweepThreads) {
         int64_t v = 0;
 #pragma unroll
@@ -1779,7 +1835,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         v = 0;
 #endif
         if (v != 0) {
-            if (KA(done))
+            if (KAK(done))
                 GS_FLUSH_ADD((unsigned long long *)&dst[c], (unsigned long long)v);
             else
                 atomicAdd((unsigned long long *)&dst[c], (unsigned long long)v);
@@ -1793,14 +1849,17 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
 #ifndef GS_FOR_EACH_WM  // (a single WM for quick resource checks: -D'GS_FOR_EACH_WM(X)=X(12)')
 #define GS_FOR_EACH_WM(X) X(4) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) X(48) X(56) X(64)
 #endif
+#ifndef GS_FOR_EACH_EK4_WM  // (the four-symbol kernels' widths; one of them for quick resource checks)
+#define GS_FOR_EACH_EK4_WM(X) X(4) X(8) X(12) X(16) X(20) X(24) X(28) X(32)
+#endif
 #ifdef GS_SWEEP_EK4_UNIT
 // This translation unit (gs_sweep_ek4.hip) instantiates the EK = 4 kernels only, so
 // the two halves compile in parallel.
-template <int WM>
+template <int WM, bool ONE>
 static const void *sweep_ek4_for(int gl) {
-    if (gl == 16) return (const void *)&gs_sweep_kernel<WM, 2, 16, 4>;
-    if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 2, 32, 4>;
-    if (gl == 64) return (const void *)&gs_sweep_kernel<WM, 2, 64, 4>;
+    if (gl == 16) return (const void *)&gs_sweep_kernel<WM, 2, 16, 4, ONE>;
+    if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 2, 32, 4, ONE>;
+    if (gl == 64) return (const void *)&gs_sweep_kernel<WM, 2, 64, 4, ONE>;
     return nullptr;
 }
 // The four-symbol sweep's workgroup tables of the snapshot in `rep` (kRepl replicas,
@@ -1830,19 +1889,20 @@ hipError_t gs_sweep_tables_launch(int W, const int64_t *rep, int32_t stride, dou
     return hipErrorInvalidValue;
 }
 
-// (W <= 32 only: the host never selects the four-symbol kernel above)
-const void *gs_sweep_ek4_ptr(int wm, int gl) {
+// (W <= 32 only: the host never selects the four-symbol kernel above; one: its
+// one-iteration path)
+const void *gs_sweep_ek4_ptr(int wm, int gl, int one) {
     switch (wm) {
 #define GS_CASE(N) \
     case N:        \
-        return sweep_ek4_for<N>(gl);
-        GS_CASE(4) GS_CASE(8) GS_CASE(12) GS_CASE(16) GS_CASE(20) GS_CASE(24) GS_CASE(28) GS_CASE(32)
+        return one ? sweep_ek4_for<N, true>(gl) : sweep_ek4_for<N, false>(gl);
+        GS_FOR_EACH_EK4_WM(GS_CASE)
 #undef GS_CASE
     }
     return nullptr;
 }
 #else
-const void *gs_sweep_ek4_ptr(int wm, int gl);  // gs_sweep_ek4.hip
+const void *gs_sweep_ek4_ptr(int wm, int gl, int one);  // gs_sweep_ek4.hip
 
 // Sets a device counter in stream order (the graph chain's first sweep index).
 __global__ void gs_set_u64_kernel(unsigned long long *p, unsigned long long v, unsigned int *z) {
@@ -1924,9 +1984,9 @@ __global__ void __launch_bounds__(256) gs_fastmath_kernel(unsigned int *out) {
 // Host-side launch helpers (the C-ABI translation unit stays free of kernel code).
 
 template <int WM>
-static const void *sweep_kernel_for(int h, int gl, int ek) {
+static const void *sweep_kernel_for(int h, int gl, int ek, int one) {
     if (h == 2 && ek == 4) {
-        return gs_sweep_ek4_ptr(WM, gl);
+        return gs_sweep_ek4_ptr(WM, gl, one);
     } else if (h == 2) {
         if (gl == 16) return (const void *)&gs_sweep_kernel<WM, 2, 16, 0>;
         if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 2, 32, 0>;
@@ -1946,12 +2006,15 @@ int gs_sweep_wm(int W);
 // every thread one aggregate cell).  The host carve decides (gs_engine.cpp launch_sweep)
 // and lays the LDS out for it (gs_common.h ek4_layout).
 int gs_sweep_ek(const SweepArgs &a) { return a.ek; }  // chosen by the host carve
+// its one-iteration instantiation (chosen by launch_sweep once the grid is known; the
+// occupancy query before that asks for the loop path's)
+static int gs_sweep_one(const SweepArgs &a) { return a.ek == 4 && a.one; }
 
-static const void *sweep_kernel_ptr(int wm, int h, int gl, int ek) {
+static const void *sweep_kernel_ptr(int wm, int h, int gl, int ek, int one) {
     switch (wm) {
 #define GS_CASE(N) \
     case N:        \
-        return sweep_kernel_for<N>(h, gl, ek);
+        return sweep_kernel_for<N>(h, gl, ek, one);
         GS_FOR_EACH_WM(GS_CASE)
 #undef GS_CASE
     }
@@ -1974,7 +2037,7 @@ int gs_sweep_group_lanes(int E, int Lmax) {
 }
 
 hipError_t gs_sweep_occupancy(int *blocks_per_cu, const SweepArgs &a, int waves, size_t lds_bytes) {
-    const void *k = sweep_kernel_ptr(gs_sweep_wm(a.W), scan_group(a.E), a.gl, gs_sweep_ek(a));
+    const void *k = sweep_kernel_ptr(gs_sweep_wm(a.W), scan_group(a.E), a.gl, gs_sweep_ek(a), gs_sweep_one(a));
     if (!k) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, 64 * waves, lds_bytes);
 }
@@ -1983,7 +2046,7 @@ hipError_t gs_sweep_occupancy(int *blocks_per_cu, const SweepArgs &a, int waves,
 // so the measured time is the kernel's, without the event packets around it.
 hipError_t gs_sweep_launch(const SweepArgs &a, int grid, size_t lds_bytes, hipStream_t stream,
                            hipEvent_t start, hipEvent_t stop) {
-    const void *k = sweep_kernel_ptr(gs_sweep_wm(a.W), scan_group(a.E), a.gl, gs_sweep_ek(a));
+    const void *k = sweep_kernel_ptr(gs_sweep_wm(a.W), scan_group(a.E), a.gl, gs_sweep_ek(a), gs_sweep_one(a));
     if (!k) return hipErrorInvalidValue;
     SweepArgs args = a;
     const int nwaves = grid * a.waves;  // the kernel's slot ranges: n_local split evenly

@@ -404,6 +404,9 @@ const char *gs_sweep_kernel_name(const gs_ctx *ctx);
  * wavefronts per workgroup, out[3] workgroups; all 0 before the first (diagnostics,
  * for tests that must know which instantiation ran). */
 int gs_last_sweep_launch(const gs_ctx *ctx, int32_t *out);
+/* 1 when that launch took the four-symbol kernel's one-iteration path (tuning field
+ * sweep_one), else 0. */
+int gs_last_sweep_one(const gs_ctx *ctx);
 
 /* --- scan mode ---------------------------------------------------------- */
 /* GS_SCAN_CERTIFIED (default): windows are scored in the log2 domain in binary32
@@ -435,7 +438,10 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * batch_starts (the four batched drivers' starts: 0 chain after chain on the single-chain
  * state, 1 all chains in the launches of gs_random_starts_batch, -1 automatic: 1 while the
  * sequences are fewer than 8 per compute unit, the size range where it measured faster),
- * greedy_switch, site_switch.  GS_E_ARG for an unknown name or a value out of
+ * greedy_switch, site_switch, sweep_one (the four-symbol sweep kernel's one-iteration
+ * path, taken when no wavefront of the launch has more sequences than it scores at a
+ * time: -1 automatic, 0 never, 1 required -- a sweep where it does not hold then fails
+ * with GS_E_ARG and launches nothing).  GS_E_ARG for an unknown name or a value out of
  * range.  Set before gs_set_sequences (launch geometry is fixed there). */
 int gs_set_tuning(gs_ctx *ctx, const char *name, double value);
 int gs_get_tuning(const gs_ctx *ctx, const char *name, double *value);
