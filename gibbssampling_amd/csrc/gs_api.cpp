@@ -59,6 +59,16 @@ const gs_tuning_field kTuningFields[] = {
 #undef GS_TUNING_FIELD
 const int kTuningFieldCount = (int)(sizeof(kTuningFields) / sizeof(kTuningFields[0]));
 
+// The quad scan's binary32 background sums (gs_common.h): its two limits and the two
+// error terms the kernel adds, as the kernel computes them (tests/test_scan_bgsum_host.py;
+// not part of the C ABI)
+extern "C" void scan_bg32_model(int32_t W, double lmax, double lmin, int32_t R, double *out) {
+    out[0] = (double)gs::kBg32Range;
+    out[1] = (double)gs::kBg32RefMax;
+    out[2] = gs::bg32_sub_err(W, lmax, lmin);
+    out[3] = gs::bg32_acc_err(R);
+}
+
 // Every entry point that can touch the aggregates outside the sweep chain drops the
 // four-symbol sweep's handed-over workgroup tables (the next sweep rebuilds them).
 static inline void drop_ftab(gs_ctx *c) {

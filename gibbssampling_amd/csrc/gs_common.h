@@ -88,6 +88,27 @@ constexpr double kLn2 = 0x1.62e42fefa39efp-1;
 constexpr double kLog2AbsErr = 0x1.0p-22;  // |log2 error| on mantissas in [0.5, 1)
 constexpr double kExp2RelErr = 0x1.0p-22;  // relative error of 2^f, f in [0, 1)
 
+// The pair-table scan's background sums in binary32 (gs_sweep.hip kQuad, DESIGN.md
+// §5.2): a window's weight is taken relative to the sequence's integer reference r =
+// rint(W max_e log2 PCV[e]) as v_exp_f32(lg - r), summed per lane in binary32 and scaled
+// back once by the exact 2^r.  A window with |lg - r| >= kBg32Range (its weight or a
+// lane sum of them could leave binary32's normal range, 2^+-126) and a sequence with
+// |r| >= kBg32RefMax (the scaled sums could leave binary64's) go to the exact rescan.
+constexpr float kBg32Range = 96.0f;
+constexpr float kBg32RefMax = 900.0f;
+// |fl(lg - r) - (lg - r)| <= |lg - r| 2^-24, and |lg - r| <= W (lmax - lmin) + 1 for
+// the largest / smallest finite log2 PCV of the sequence (rint's half, the roundings of
+// W lmax and of lg's tree sum: below a quarter while epsG < 1/64): added to epsG
+GS_HD double bg32_sub_err(int W, double lmax, double lmin) {
+    return ((double)W * (lmax - lmin) + 1.0) * 0x1.0p-24;
+}
+// a binary32 sum of n <= R + 4 non-negative terms, in any order, is within g = (n - 1) u
+// / (1 - (n - 1) u), u = 2^-24, of their exact sum, relative to either (R <= 64: g <=
+// 1.001 (R + 3) u).  With the terms' own bound e = 0.75 epsG + 1.1 kExp2RelErr < 0.012
+// the lane sum is within e (1 + g) + g <= e + 1.02 (R + 3) u of the reference's: the
+// second term is added to eabs_g
+GS_HD double bg32_acc_err(int R) { return 1.02 * (double)(R + 3) * 0x1.0p-24; }
+
 // Scan modes of the sweep kernel.
 constexpr int kScanCertified = 0;  // binary32 log-domain scan + certified decisions
 constexpr int kScanExact = 1;      // binary64 folds for every window (diagnostics)
@@ -314,7 +335,7 @@ constexpr int mt_stride(int wm) { return wm + 1; }      // H = 1 motif terms log
 struct Ek4Layout {
     int o_cg, o_T, o_ppmG, o_ppmM, o_lppmG, o_bmax, o_lT, o_wave;
     int w_aggC, w_aggT, w_tab, w_res, w_misc, w_group;
-    int g_lt, g_gt, g_pcv, g_lpcv, g_cmax, g_seq;
+    int g_lt, g_gt, g_pcv, g_lpcv, g_cmax, g_cell, g_seq;
 };
 constexpr int ek4_a16(int x) { return (x + 15) & ~15; }
 constexpr Ek4Layout ek4_layout(int WM, int GL) {
@@ -336,11 +357,12 @@ constexpr Ek4Layout ek4_layout(int WM, int GL) {
     l.w_misc = o;  o = ek4_a16(o + 32);
     l.w_group = o;
     o = 0;
-    l.g_lt = o;    // (none: the pair table is built directly)
+    l.g_lt = o;    // (none: the pair table is built from the cells below)
     l.g_gt = o;    o = ek4_a16(o + 128 * (WM / 2));  // group-major [WM/2][16 codes]
     l.g_pcv = o;   o = ek4_a16(o + 8 * 4);
     l.g_lpcv = o;  o = ek4_a16(o + 8 * 4);
     l.g_cmax = o;  o = ek4_a16(o + 16 * WM); // the picked window's factors alias it
+    l.g_cell = o;  o = ek4_a16(o + 4 * 4 * WM);  // [4][WM] fixed-point motif terms (uint32)
     // the sequence (Lmax + WM + 96 bytes, + 64: the odd group's is 64 B further), then
     // the scan's copy of its codes x 8 (as long)
     l.g_seq = o;

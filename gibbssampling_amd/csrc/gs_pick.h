@@ -70,6 +70,17 @@ __device__ __forceinline__ int seg_scan_max_i32(int v) {
     return v;
 }
 
+// inclusive running maximum of floats of either sign inside each 16-lane DPP row (a
+// lane without a source keeps its own value: -inf is the identity)
+__device__ __forceinline__ float row_scan_max_f32(float x) {
+    int v = __float_as_int(x);
+    v = __float_as_int(fmaxf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false))));
+    v = __float_as_int(fmaxf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false))));
+    v = __float_as_int(fmaxf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false))));
+    v = __float_as_int(fmaxf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false))));
+    return __int_as_float(v);
+}
+
 // the value of the group's last lane, in every lane of the group (GL = 16, one DPP row a
 // group: DPP row_newbcast:15, control 0x15F on gfx950 -- tools/probe/dpp_newbcast.hip --
 // one VALU a dword and no LDS round trip; a disabled source lane gives 0, as the

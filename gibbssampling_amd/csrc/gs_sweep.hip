@@ -222,14 +222,17 @@ __device__ __forceinline__ QuadCodes<WM> quad_codes(const uint8_t *codes, int k)
     for (int i = 0; i < QuadCodes<WM>::ND; ++i) q.d[i] = *(const uint32_t *)(codes + k + 4 * i);
     return q;
 }
-// windows k + O and k + O + 1 (O = 0 or 2) of the quad
+// windows k + O and k + O + 1 (O = 0 or 2) of the quad.  Their background sums are two
+// plain binary32 trees (the values and order of window_logs'): the high dwords of the
+// table reads are added where they land; packed adds cost a v_mov_b32 a pair to bring
+// the two windows' halves together (20 a quad).
 template <int WM, int O, bool GM>
 __device__ __forceinline__ void window_logs_q(const QuadCodes<WM> &q, const unsigned char *ltab,
-                                              uint32_t &s0, uint32_t &s1, f2 &lg) {
+                                              uint32_t &s0, uint32_t &s1, float &lg0, float &lg1) {
     constexpr int NG = WM / 2;
     constexpr int RS = gt_stride(WM) * 8;
     uint32_t v0[NG], v1[NG];
-    f2 vg[NG];
+    float g0[NG], g1[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const int b0 = O + 2 * g, b1 = O + 1 + 2 * g;
@@ -239,7 +242,8 @@ __device__ __forceinline__ void window_logs_q(const QuadCodes<WM> &q, const unsi
         const uint2 a1 = pair_entry<GM, RS>(ltab, x1, g);
         v0[g] = a0.x;
         v1[g] = a1.x;
-        vg[g] = f2{__uint_as_float(a0.y), __uint_as_float(a1.y)};
+        g0[g] = __uint_as_float(a0.y);
+        g1[g] = __uint_as_float(a1.y);
     }
     s0 = 0u;
     s1 = 0u;
@@ -248,7 +252,8 @@ __device__ __forceinline__ void window_logs_q(const QuadCodes<WM> &q, const unsi
         s0 += v0[g];
         s1 += v1[g];
     }
-    lg = tree_sum<NG>(vg);
+    lg0 = tree_sum<NG>(g0);
+    lg1 = tree_sum<NG>(g1);
 }
 
 // Certified-scan view of one group's sequence (per lane: the lane's group).  A
@@ -608,6 +613,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
 
     static_assert(EK == 0 || (EK == 4 && H == 2), "EK = 4 is the pair-table DNA path");
     static_assert(!ONE || EK == 4, "the one-iteration path is the four-symbol kernel's");
+    // the quad scan (pair tables, 16-lane groups: a lane's windows four at a time) sums the
+    // background weights in binary32 relative to a per-sequence reference (gs_common.h
+    // kBg32Range)
+    constexpr bool kQuad = H == 2 && GL == 16;
     // EK = 4 kernels run for W == WM only (gs_sweep_ek): the motif width is static too
     const int A = EK ? EK : a.A, E = EK ? EK : a.E, W = EK ? WM : a.W, AW = A * W, CS = E + 1,
               E2 = E * E;
@@ -1211,6 +1220,21 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             const float tG = __int_as_float(seg_last_i32<GL>(
                 seg_scan_max_i32<GL>(__float_as_int(li < E && fabsf(lq) < INFINITY ? fabsf(lq) : 0.0f)),
                 lane));
+            // kQuad: the largest and smallest finite log2 PCV of the sequence (binary32,
+            // the table's own values), the integer reference r = rint(W lmax) >= every
+            // window's lg - 1, and the rounding of lg - r (gs_common.h bg32_sub_err)
+            float rG = 0.0f;
+            double epsR = 0.0;
+            if constexpr (kQuad) {
+                const bool fin = li < E && fabsf(lq) < INFINITY;
+                const float lmax = __int_as_float(seg_last_i32<GL>(
+                    __float_as_int(row_scan_max_f32(fin ? lq : -INFINITY)), lane));
+                const float lmin = -__int_as_float(seg_last_i32<GL>(
+                    __float_as_int(row_scan_max_f32(fin ? -lq : -INFINITY)), lane));
+                rG = rintf((float)W * lmax);
+                epsR = bg32_sub_err(W, (double)lmax, (double)lmin);
+                fast = fast && fabsf(rG) < kBg32RefMax;  // (also no finite log at all: NaN / inf)
+            }
             // H = 1: the symbols' log2 PCV in fixed point 2^-sP (int32, after the binary32
             // logs: a window's W of them within 2^30, W tG 2^sP < 2^30), rounded within
             // 2^-(sP+1) each
@@ -1224,7 +1248,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             STAMP(2);
             TLF(tl_w, 2);
             TLP(tl_w, 7);
-            const double epsG = epsG0 + epsG1 * (double)tG + (H == 1 ? (double)W * ldexp(1.0, -sP - 1) : 0.0);
+            double epsG = epsG0 + epsG1 * (double)tG + (H == 1 ? (double)W * ldexp(1.0, -sP - 1) : 0.0);
+            if constexpr (kQuad) epsG = epsG + epsR;
             fast = fast && epsG < 0.015625 && fabs(a.cutoff) < 1000.0;
             // |G~ - G| <= G~ ((2^epsG - 1) + kExp2RelErr)(1 + 3%) for epsG < 1/64
             const double eabs_g = 0.75 * epsG + 1.1 * kExp2RelErr;
@@ -1315,36 +1340,44 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 wave_sync();
                 TLF(tl_w, 3);
                 if constexpr (EK == 4) {
-                    // ---- pair table directly: lane entry (code, g), code = e0 + 4 e1 ----
-                    // gt[code][g] = (t[e0][2g] + t[e1][2g+1] fixed, lq[e0] + lq[e1] binary32),
-                    // columns past the motif (0, 0); t as the generic path's lt below
+                    // ---- the 4 W fixed-point terms t[e][j] once (as the generic path's lt
+                    // below: clamped at the column's floor Fc_j, the own segment's cell
+                    // substituted), to the group's cells; then the pair table from them ----
+                    uint32_t *const cell = (uint32_t *)(gsl + L4.g_cell);  // [4][WM]
                     if (fast) {
+                        constexpr int NC = (4 * WM + GL - 1) / GL;
+#pragma unroll
+                        for (int q = 0; q < NC; ++q) {
+                            const int c = li + q * GL;  // (a quad of lanes shares its column's reads)
+                            if (c < 4 * W) {
+                                const int e = c & 3, j = c >> 2;
+                                uint32_t sv = 0u;
+                                if (!nopass) {
+                                    const double le = lpcv[e];
+                                    const double2 cf = cmax[j];  // (Fc_j, own cell's log2 PPM')
+                                    const bool own = (p >= 0) & (sym(sseq[pp + j]) == e);
+                                    const double t = (own ? cf.y : lppmG[e * W + j]) - le;
+                                    sv = (uint32_t)rint((fmax(t, cf.x) - cf.x) * scale);
+                                }
+                                cell[e * WM + j] = sv;
+                            }
+                        }
+                    }
+                    wave_sync();
+                    // lane entry (code, g), code = e0 + 4 e1 = the lane's index mod 16:
+                    // gt[code][g] = (t[e0][2g] + t[e1][2g+1], lq[e0] + lq[e1] binary32, the
+                    // same for every g)
+                    if (fast) {
+                        const int code = li & 15, e0 = code & 3, e1 = code >> 2;
+                        const uint32_t bg = __float_as_uint((float)lpcv[e0] + (float)lpcv[e1]);
+                        const uint32_t *const c0 = cell + e0 * WM, *const c1 = cell + e1 * WM + 1;
                         constexpr int NE = (16 * NG + GL - 1) / GL;
 #pragma unroll
                         for (int q = 0; q < NE; ++q) {
                             const int idx = li + q * GL;
                             if (idx < 16 * NG) {
-                                const int code = idx & 15, g = idx >> 4;
-                                uint32_t sv[2];
-                                float bgv[2];
-#pragma unroll
-                                for (int h = 0; h < 2; ++h) {
-                                    const int e = h ? code >> 2 : code & 3, j = 2 * g + h;
-                                    sv[h] = 0u;
-                                    bgv[h] = 0.0f;
-                                    if (j < W) {
-                                        const double le = lpcv[e];
-                                        bgv[h] = (float)le;
-                                        if (!nopass) {
-                                            const double2 cf = cmax[j];  // (Fc_j, own cell's log2 PPM')
-                                            const bool own = (p >= 0) & (sym(sseq[pp + j]) == e);
-                                            const double t = (own ? cf.y : lppmG[e * W + j]) - le;
-                                            sv[h] = (uint32_t)rint((fmax(t, cf.x) - cf.x) * scale);
-                                        }
-                                    }
-                                }
-                                *(uint2 *)(gt + g * 128 + code * 8) =
-                                    make_uint2(sv[0] + sv[1], __float_as_uint(bgv[0] + bgv[1]));
+                                const int g = idx >> 4;
+                                *(uint2 *)(gt + g * 128 + code * 8) = make_uint2(c0[2 * g] + c1[2 * g], bg);
                             }
                         }
                     }
@@ -1430,7 +1463,6 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // (16-lane groups of the pair tables: blocks of a multiple of 4 windows, so
             // that a lane's windows go four at a time from 4-aligned codes; the block
             // ends stay within the zero tail, K + 4 GL + WM < L + WM + 76)
-            constexpr bool kQuad = H == 2 && GL == 16;
             const int R = kQuad ? (((K + GL - 1) / GL + 3) & ~3) : (K + GL - 1) / GL;
             const int k_lo = li * R;
             const int Rmax = wave_max_i32(fast ? R : 0);
@@ -1440,13 +1472,16 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // two windows per step: their LDS lookups overlap (the loop is latency-bound)
             if constexpr (kQuad) {
                 // branch-free but for the (rare) windows that pass the cut-off; a window
-                // past the lane's block adds +0.0 (the sums are >= +0.0: exact)
+                // past the lane's block adds +0.0 (the sums are >= +0.0: exact).  A
+                // window's background weight is 2^(lg - r), one v_sub_f32 and one v_exp_f32;
+                // outside (-kBg32Range, kBg32Range) the sequence is flagged for the rescan
+                float sG32 = 0.0f;  // the lane's sum of 2^(lg - r)
                 auto take = [&](int kk, int rr, uint32_t so, float lgo) {
                     const bool ok = rr < R && kk < K;
-                    const bool xo = !(lgo > -1000.0f && lgo < 1000.0f);
-                    const double go = fexp2(lgo);
+                    const float d = lgo - rG;
+                    const bool xo = !(fabsf(d) < kBg32Range);
+                    sG32 = sG32 + (ok ? __builtin_amdgcn_exp2f(d) : 0.0f);
                     const int co = classify(fv, so);
-                    sG = sG + (ok ? go : 0.0);
                     if (ok && co == kPass) {
                         const double fo = (double)so * fv.unit + fv.base;
                         sM = sM + fo;
@@ -1459,15 +1494,17 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     const int k0 = k_lo + r;
                     const QuadCodes<WM> q = quad_codes<WM>(lcodes, k0);
                     uint32_t s0, s1, s2, s3;
-                    f2 l01, l23;
-                    window_logs_q<WM, 0, EK == 4>(q, ltab, s0, s1, l01);
-                    take(k0, r, s0, l01.x);
-                    take(k0 + 1, r + 1, s1, l01.y);
+                    float l0, l1, l2, l3;
+                    window_logs_q<WM, 0, EK == 4>(q, ltab, s0, s1, l0, l1);
+                    take(k0, r, s0, l0);
+                    take(k0 + 1, r + 1, s1, l1);
                     __builtin_amdgcn_sched_barrier(0);  // 12 table reads in flight at a time
-                    window_logs_q<WM, 2, EK == 4>(q, ltab, s2, s3, l23);
-                    take(k0 + 2, r + 2, s2, l23.x);
-                    take(k0 + 3, r + 3, s3, l23.y);
+                    window_logs_q<WM, 2, EK == 4>(q, ltab, s2, s3, l2, l3);
+                    take(k0 + 2, r + 2, s2, l2);
+                    take(k0 + 3, r + 3, s3, l3);
                 }
+                // the lane's sum back at its absolute scale: an exact power of two
+                sG = ldexp((double)sG32, (int)rG);
             } else if constexpr (H == 2) {
                 for (int r = 0; r < Rmax; r += 2) {
                     const int k0 = k_lo + r, k1 = k0 + 1;
@@ -1538,7 +1575,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     uint32_t ls;
                     float lg;
                     window_logs<WM, H, EK == 4>(lcodes, ltab, k, ls, lg);
-                    g = fexp2(lg);
+                    // (kQuad: the value the scan added for window k, at its absolute scale)
+                    if constexpr (kQuad)
+                        g = ldexp((double)__builtin_amdgcn_exp2f(lg - rG), (int)rG);
+                    else
+                        g = fexp2(lg);
                     m = classify(fv, ls) == kPass ? (double)ls * fv.unit + fv.base : -INFINITY;
                 } else {
                     double fs;
@@ -1548,8 +1589,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             };
             // |M~ - M| <= epsS above the band; M~'s own rounding: 2^-52 relative (H = 2,
             // the fixed-point sum), 2^-23 (H = 1, binary32)
-            int kind = certified_pick<GL>(ev, fast, K, R, lane, u, sG, sM, lcat, npass, eabs_g,
-                                          epsS, H == 2 ? 0x1.0p-52 : 0x1.0p-23, pk);
+            // (kQuad: the lane sums' binary32 accumulation on top, gs_common.h bg32_acc_err)
+            int kind = certified_pick<GL>(ev, fast, K, R, lane, u, sG, sM, lcat, npass,
+                                          kQuad ? eabs_g + bg32_acc_err(R) : eabs_g, epsS,
+                                          H == 2 ? 0x1.0p-52 : 0x1.0p-23, pk);
             STAMP(5);
             TLINE(tl_w, 4);
             // ---- the picked window's exact weight ----
@@ -1962,7 +2005,8 @@ __global__ void __launch_bounds__(256) gs_composition_kernel(const uint8_t *seq,
 
 // Measures the binary32 transcendental errors the certified scan budgets for
 // (kLog2AbsErr, kExp2RelErr): flog2 on 2^24 points of [0.5, 1) against the
-// binary64 log, and v_exp_f32 on every multiple of 2^-24 in [0, 1).
+// binary64 log, and v_exp_f32 on every multiple of 2^-24 in [0, 1) and on 2^24 points
+// of [-kBg32Range, 0].
 __global__ void __launch_bounds__(256) gs_fastmath_kernel(unsigned int *out) {
     const int n = 1 << 24;
     float el = 0.0f, ee = 0.0f;
@@ -1972,6 +2016,11 @@ __global__ void __launch_bounds__(256) gs_fastmath_kernel(unsigned int *out) {
         const float x = (float)i * 0x1.0p-24f;
         const double ex = exp2((double)x);
         ee = fmaxf(ee, (float)(fabs((double)__builtin_amdgcn_exp2f(x) - ex) / ex));
+        // and on the arguments of the quad scan's relative weights, 2^24 points of
+        // [-kBg32Range, 0] (no range reduction of ours in front of the instruction there)
+        const float y = -(float)i * (kBg32Range * 0x1.0p-24f);
+        const double ey = exp2((double)y);
+        ee = fmaxf(ee, (float)(fabs((double)__builtin_amdgcn_exp2f(y) - ey) / ey));
     }
     el = wave_max_nonneg_f32(el);
     ee = wave_max_nonneg_f32(ee);
