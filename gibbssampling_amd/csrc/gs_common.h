@@ -109,6 +109,16 @@ GS_HD double bg32_sub_err(int W, double lmax, double lmin) {
 // second term is added to eabs_g
 GS_HD double bg32_acc_err(int R) { return 1.02 * (double)(R + 3) * 0x1.0p-24; }
 
+// Relative error of a background weight g_k taken by incremental binary64 products (the
+// ratio-table walk of gs_bgwalk.h; gs_sweep_live.hip bg_pick's two multiplies a window)
+// k - x0 < K steps after the walk's first window, against the reference's fold: the
+// first window's 4W + 1 roundings (rows: 1 / pcv[0] and the product; the multiplies;
+// pcv[0]^W), per step three (1 / pcv, the table product, the multiply), the
+// reference's own W.
+GS_HD double bg_walk_rel_err(int W, int K) {
+    return (double)(5 * W + 3 * K + 20) * 0x1.0p-53 * (1.0 + 0x1.0p-10);
+}
+
 // Scan modes of the sweep kernel.
 constexpr int kScanCertified = 0;  // binary32 log-domain scan + certified decisions
 constexpr int kScanExact = 1;      // binary64 folds for every window (diagnostics)

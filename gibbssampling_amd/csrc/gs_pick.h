@@ -1,5 +1,8 @@
-// gs_pick.h — segmented wavefront primitives and the certified roulette pick
-// (.fs:746-754), shared by the sweep kernels (gs_sweep.hip, gs_sweep_dna.hip).
+// gs_pick.h — segmented wavefront primitives, the certified roulette pick
+// (.fs:746-754: certified_pick, the sweep kernels' in gs_sweep.hip and
+// gs_sweep_dna.hip) and the exact pick that ends every kernel's binary64 rescan
+// (exact_pick: gs_sweep.hip's H = 1 group rescan and gs_packed.h rescan_packed, the
+// dna, live and long kernels').
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -207,6 +210,94 @@ __device__ int certified_pick(const Eval &ev, bool on, int K, int R, int lane, d
     }
     if (res == 1) res = -4;
     return res >= 10 ? res - 10 : res;
+}
+
+// The exact pick of one sequence by the whole wavefront, the end of every kernel's
+// binary64 rescan: ev(k, g, m) is the reference's fold of window k (.fs:759-777; m =
+// -inf: not a category) over the K windows; lane l sums windows [l R, l R + R), R =
+// ceil(K / 64); the pick is certified against rounding alone (certified_pick<64> with no
+// error terms; not at all when a weight is negative or NaN), else one lane replays the
+// reference's sequential sums (.fs:747-754) and leaves its result in scratch2 (two
+// ints of the wavefront's LDS, free until the caller's next wave_sync).  serial_stat()
+// gives the gs_stats counter of serial replays, called by that one lane only (the
+// callers read their stats pointer from the kernel arguments there, not before).
+// Returns the category kind (0 background, 1 motif, < 0 none: every category missed,
+// .fs:752), the window and its exact weight, uniform over the wavefront.  All 64 lanes
+// must be active.  mark(13) / mark(14): the ends of the lane sums and of the pick, for a
+// caller that stamps its phases (gs_sweep_dna.hip's diagnostic build).
+struct ExactPick {
+    int kind, win;
+    double w;
+};
+struct NoMarks {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+template <class Eval, class Stat, class Marks = NoMarks>
+__device__ __forceinline__ ExactPick exact_pick(const Eval &ev, int K, int lane, double u,
+                                                const Stat &serial_stat, int32_t *scratch2,
+                                                const Marks &mark = Marks()) {
+    const int R = (K + 63) >> 6;
+    const int k_lo = lane * R, k_hi = min(K, k_lo + R);
+    double xG = 0.0, xM = 0.0;
+    bool neg = false;
+    int xcat = 0;
+    for (int k = k_lo; k < k_hi; ++k) {
+        double g, m;
+        ev(k, g, m);
+        xG = xG + g;
+        neg |= !(g >= 0.0);
+        if (m != -INFINITY) {
+            xM = xM + m;
+            neg |= !(m >= 0.0);
+            ++xcat;
+        }
+    }
+    const int xpass = wave_sum_i32(xcat);
+    mark(13);
+    int pkk = -1;
+    const bool ok = __ballot(neg) == 0;
+    int kk = certified_pick<64>(ev, ok, K, R, lane, u, xG, xM, xcat, xpass, 0.0, 0.0, 0.0, pkk);
+    if (kk < 0) {
+        // exact sequential restatement of .fs:747-754 on one lane, the windows
+        // re-evaluated in the reference's order: two summing passes (backgrounds, then
+        // motif scores), two walking passes
+        if (lane == 0) {
+            atomicAdd(serial_stat(), 1ull);
+            double sacc = 0.0, acc = 0.0;
+            int rk = -1, rp = -1;
+            for (int pass = 0; pass < 4 && rk < 0; ++pass) {
+                for (int k = 0; k < K && rk < 0; ++k) {
+                    double g, m;
+                    ev(k, g, m);
+                    const double x = (pass & 1) ? m : g;
+                    if ((pass & 1) && m == -INFINITY) continue;
+                    if (pass < 2) {
+                        sacc = sacc + x;
+                    } else {
+                        const double w = x / sacc;
+                        if (acc <= u && u <= acc + w) {
+                            rk = pass - 2;
+                            rp = k;
+                        }
+                        acc = acc + w;
+                    }
+                }
+            }
+            scratch2[0] = rk;
+            scratch2[1] = rp;
+        }
+        wave_sync();
+        kk = scratch2[0];
+        pkk = scratch2[1];
+    }
+    mark(14);
+    double xw = 0.0;
+    if (kk >= 0) {
+        double g, m;
+        ev(pkk, g, m);
+        xw = kk == 0 ? g : m;
+    }
+    return ExactPick{kk, pkk, xw};
 }
 
 }  // namespace gs

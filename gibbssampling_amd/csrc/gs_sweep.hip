@@ -489,12 +489,8 @@ __device__ __forceinline__ void sweep_epilogue(const SweepArgs &a, unsigned char
 // lane.  Returns the category kind (0 background, 1 motif, < 0 none), the window and
 // its exact weight, uniform over the wavefront.  The kernel arguments through the
 // kernarg segment (ka): the by-value struct is not copied.
-struct RxOut {
-    int kk, pkk;
-    double xw;
-};
 template <int WM>
-__device__ __attribute__((noinline)) RxOut rescan_group_h1(KSweepArgs *ka_in, int gg, int Lx, int px, double ux) {
+__device__ __attribute__((noinline)) ExactPick rescan_group_h1(KSweepArgs *ka_in, int gg, int Lx, int px, double ux) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     // (the segment pointer made wave-uniform: its fields are scalar loads)
     const uint64_t pv = (uint64_t)ka_in;
@@ -527,67 +523,10 @@ __device__ __attribute__((noinline)) RxOut rescan_group_h1(KSweepArgs *ka_in, in
     wave_sync();
     const double thr_lo = ka->thr_lo;
     auto evx = [&](int k, double &g, double &m) { exact_eval<WM, true>(sx, tab, thr_lo, cutoff, k, g, m); };
-    const int Rx = (Kx + 63) >> 6;
-    const int kx_lo = lane * Rx, kx_hi = min(Kx, kx_lo + Rx);
-    double xG = 0.0, xM = 0.0;
-    bool neg = false;
-    int xcat = 0;
-    for (int k = kx_lo; k < kx_hi; ++k) {
-        double g, m;
-        evx(k, g, m);
-        xG = xG + g;
-        neg |= !(g >= 0.0);
-        if (m != -INFINITY) {
-            xM = xM + m;
-            neg |= !(m >= 0.0);
-            ++xcat;
-        }
-    }
-    const int xpass = wave_sum_i32(xcat);
-    int pkk = -1;
-    const bool ok = __ballot(neg) == 0;
-    int kk = certified_pick<64>(evx, ok, Kx, Rx, lane, ux, xG, xM, xcat, xpass, 0.0, 0.0, 0.0, pkk);
-    if (kk < 0) {
-        // exact sequential restatement of .fs:747-754 on one lane, the windows
-        // re-evaluated in the reference's order: two summing passes (backgrounds, then
-        // motif scores), two walking passes
-        if (lane == 0) {
-            atomicAdd(&(ka->fallbacks + (blockIdx.x % kRepl) * kStatStride)[1], 1ull);
-            double sacc = 0.0, acc = 0.0;
-            int rk = -1, rp = -1;
-            for (int pass = 0; pass < 4 && rk < 0; ++pass) {
-                for (int k = 0; k < Kx && rk < 0; ++k) {
-                    double g, m;
-                    evx(k, g, m);
-                    const double x = (pass & 1) ? m : g;
-                    if ((pass & 1) && m == -INFINITY) continue;
-                    if (pass < 2) {
-                        sacc = sacc + x;
-                    } else {
-                        const double w = x / sacc;
-                        if (acc <= ux && ux <= acc + w) {
-                            rk = pass - 2;
-                            rp = k;
-                        }
-                        acc = acc + w;
-                    }
-                }
-            }
-            misc[0] = rk;
-            misc[1] = rp;
-        }
-        wave_sync();
-        kk = misc[0];
-        pkk = misc[1];
-    }
-    double xw = 0.0;
-    if (kk >= 0) {
-        double g, m;
-        evx(pkk, g, m);
-        xw = kk == 0 ? g : m;
-    }
+    const ExactPick r = exact_pick(
+        evx, Kx, lane, ux, [&] { return &(ka->fallbacks + (blockIdx.x % kRepl) * kStatStride)[1]; }, misc);
     wave_sync();  // the shared exact table is rebuilt for the next group
-    return RxOut{kk, pkk, xw};
+    return r;
 }
 
 // EK = 4: the alphabet is exactly four symbols and the data holds no other (DNA):
@@ -1655,11 +1594,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 const int px = __builtin_amdgcn_readlane(p, src);
                 const double ux = lane_read_f64(u, src);
                 if constexpr (H == 1) {
-                    const RxOut r = rescan_group_h1<WM>(kargs(), gg, Lx, px, ux);
+                    const ExactPick r = rescan_group_h1<WM>(kargs(), gg, Lx, px, ux);
                     if (gi == gg) {
-                        kind = r.kk;
-                        pk = r.pkk;
-                        pw = r.xw;
+                        kind = r.kind;
+                        pk = r.win;
+                        pw = r.w;
                         pw_log = false;
                     }
                     continue;
@@ -1690,6 +1629,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 auto evx = [&](int k, double &g, double &m) {
                     exact_eval<WM, H == 1>(sx, tab, thr_lo, a.cutoff, k, g, m);
                 };
+                // gs_pick.h exact_pick, written out: this kernel's own copy.  Calling
+                // exact_pick here (inlined, in five shapes: by value or by reference, its
+                // results returned or through references, the replay in a helper) moved the
+                // register allocation of every H = 2 instantiation and cost WM = 64, GL = 64
+                // two more spilled SGPRs (124 -> 126); the other kernels' rescans call it.
                 const int Rx = (Kx + 63) >> 6;
                 const int kx_lo = lane * Rx, kx_hi = min(Kx, kx_lo + Rx);
                 double xG = 0.0, xM = 0.0;

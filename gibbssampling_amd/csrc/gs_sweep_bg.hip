@@ -26,7 +26,9 @@
 #include <hip/hip_runtime.h>
 
 #include "gs_bgregime.h"
+#include "gs_bgwalk.h"
 #include "gs_common.h"
+#include "gs_packed.h"
 #include "gs_stamps.h"
 #include "gs_wave.h"
 
@@ -42,35 +44,6 @@ constexpr int O_WAVE = 640;  // per wavefront: ratio tables [16 rows][64 lanes] 
 constexpr int kWaveBytes = 16 * 64 * 8;
 constexpr int kSmem = O_WAVE + kBgWaves * kWaveBytes;
 
-__device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, int sh) {
-    return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)sh);
-}
-
-__device__ __forceinline__ void raise_error(const BgArgs &a, int code, int64_t gidx) {
-    atomicCAS(a.err_code, 0, code);
-    atomicMin(a.err_index, (unsigned long long)gidx);
-}
-
-// Pass 1 visitor: the lane's sum and its value at the starts of 8 chunks of Cz
-// windows (whole 16-window blocks).
-struct Sum {
-    double B, pre[8];
-    int ci, nck, Cz;
-    __device__ __forceinline__ void blk(int t) {
-        if (t == nck) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) pre[i] = i == ci ? B : pre[i];
-            ++ci;
-            nck += Cz;
-        }
-    }
-    static constexpr bool kStops = false;  // never ends a walk early
-    __device__ __forceinline__ void blkw(uint32_t, uint32_t) {}
-    __device__ __forceinline__ bool win(int, double g) {
-        B = B + g;
-        return false;
-    }
-};
 // Pass 2 visitor: from the running sum P, the first window whose upper boundary
 // reaches Tb; certified when Ub lies inside [lo + Db, hi - Db].
 struct Find {
@@ -96,32 +69,6 @@ struct Find {
         return hit;
     }
 };
-
-template <bool FULL, class V>
-__device__ __forceinline__ void walk_block(double &g, bool &done, uint32_t nw, uint32_t ow, int b, int nwin,
-                                           int x0, const double *rt, V &v) {
-    double r[16];
-#pragma unroll
-    for (int R = 0; R < 16; ++R) {
-        const uint32_t ci = __builtin_amdgcn_ubfe(nw, 2 * R, 2), co = __builtin_amdgcn_ubfe(ow, 2 * R, 2);
-        r[R] = rt[(ci | (co << 2)) * 64];
-    }
-#pragma unroll
-    for (int R = 0; R < 16; ++R) {
-        if (R > 0 || b > 0) g = g * r[R];
-        if constexpr (V::kStops) {
-            if (!done && (FULL || b + R < nwin)) done = v.win(x0 + b + R, g);
-        } else {
-            if (FULL || b + R < nwin) v.win(x0 + b + R, g);
-        }
-    }
-}
-
-__device__ __forceinline__ uint4 load_words(const uint32_t *p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);  // 4-byte aligned 16-byte load
-    return v;
-}
 
 // Windows [x0, x0 + nwin) of the sequence at seqw, x0 % 16 == 0, W <= 16, by
 // 64-window super-blocks: super-block s reads words 4s - 1 .. 4s + 4 of the range
@@ -156,9 +103,9 @@ __device__ __forceinline__ V walk(const uint32_t *seqw, int x0, int nwin, int W,
                 v.blk(bb);
                 v.blkw(w[k + 1], w[k + 2]);
                 if (bb + 16 <= nwin)
-                    walk_block<true>(g, done, nw, ow, bb, nwin, x0, rt, v);
+                    bg_walk_block<true>(g, done, nw, ow, bb, nwin, x0, rt, v);
                 else
-                    walk_block<false>(g, done, nw, ow, bb, nwin, x0, rt, v);
+                    bg_walk_block<false>(g, done, nw, ow, bb, nwin, x0, rt, v);
             }
         }
         prev = cur.w;
@@ -192,35 +139,12 @@ __device__ __forceinline__ V walk_short(const uint32_t *seqw, int x0, int nwin, 
         const uint32_t nw = funnel(wc, wb, shn), ow = funnel(wb, wa, 30);
         v.blk(b);
         v.blkw(wb, wc);
-        walk_block<false>(g, done, nw, ow, b, nwin, x0, rt, v);
+        bg_walk_block<false>(g, done, nw, ow, b, nwin, x0, rt, v);
         wa = wb;
         wb = wc;
         wc = wd;
     }
     return v;
-}
-
-// The reference's binary64 fold of a window's PCV factors (.fs:123-124), its W
-// symbols at the low bits of wv.
-__device__ __forceinline__ double fold_bits(uint32_t wv, int W, const double (&pcv)[4]) {
-    double g = 1.0;
-    for (int j = 0; j < W; ++j) {
-        const uint32_t e = (wv >> (2 * j)) & 3u;
-        g = g * (e == 0 ? pcv[0] : e == 1 ? pcv[1] : e == 2 ? pcv[2] : pcv[3]);
-    }
-    return g;
-}
-
-// The same for window k of the sequence at seqw.
-__device__ __forceinline__ double fold_window(const uint32_t *seqw, int k, int W, const double (&pcv)[4]) {
-    const uint32_t *q = seqw + (k >> 4);
-    const uint32_t wv = funnel(q[1], q[0], 2 * (k & 15));
-    double g = 1.0;
-    for (int j = 0; j < W; ++j) {
-        const uint32_t e = (wv >> (2 * j)) & 3u;
-        g = g * (e == 0 ? pcv[0] : e == 1 ? pcv[1] : e == 2 ? pcv[2] : pcv[3]);
-    }
-    return g;
 }
 
 }  // namespace
@@ -284,7 +208,7 @@ __device__ __forceinline__ void bg_tiles(const BgArgs &a, unsigned char *lds, ui
         const int64_t tot = sumT + (p >= 0 ? W : L);
         bool keep = act;
         if (act && tot > 2147483647LL) {  // Checked Array.sum (.fs:117)
-            if (lead) raise_error(a, 3, gidx);
+            if (lead) raise_error(a.err_code, a.err_index, 3, gidx);
             keep = false;
         }
         double pcv[4] = {1.0, 1.0, 1.0, 1.0};
@@ -293,22 +217,13 @@ __device__ __forceinline__ void bg_tiles(const BgArgs &a, unsigned char *lds, ui
         for (int e = 0; e < 4; ++e) {
             if (e < A) {
                 int x = cmp[e];
-                if (p >= 0) {
-                    const uint32_t y = ~(gw ^ (0x55555555u * (uint32_t)e));
-                    x = __popc(y & (y >> 1) & 0x55555555u & wmask);
-                }
+                if (p >= 0) x = sym_count(gw, e, wmask);
                 pcv[e] = ((double)(sT[e] + x) + a.pc) / ((double)tot + a.apc);
                 bad |= !(pcv[e] > 0.0) || !(pcv[e] < INFINITY);
             }
         }
         // ratio table and the first window's scale
-        {
-            double inv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) inv[e] = 1.0 / pcv[e];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) rt[c * 64] = pcv[c & 3] * inv[c >> 2];
-        }
+        bg_ratio_table(rt, pcv);
         double pw0 = 1.0;
         for (int j = 0; j < W; ++j) pw0 = pw0 * pcv[0];
         STAMP(1);
@@ -318,7 +233,7 @@ __device__ __forceinline__ void bg_tiles(const BgArgs &a, unsigned char *lds, ui
         const bool walkable = keep && !bad;
         const int nb = walkable ? nwin : 0;
         const int Cz = max(16, ((nb + 127) >> 7) << 4);
-        Sum s1{0.0, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 0, 0, Cz};
+        BgSum s1{0.0, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 0, 0, Cz};
         s1 = walk(seqw, x0, nb, W, pw0, rt, s1);
         STAMP(2);
         // the group's total and this lane's exclusive prefix
@@ -337,21 +252,15 @@ __device__ __forceinline__ void bg_tiles(const BgArgs &a, unsigned char *lds, ui
         const double Bpre = incl - Bl;  // within the bound below (rounding of the scan)
         const double T = G > 1 ? __shfl(incl, gbase + G - 1, 64) : Bl;
         // every weight's relative bound, the scans' roundings, the roulette's own
-        const double rel = (double)(5 * W + 3 * K + 20) * 0x1.0p-53 * (1.0 + 0x1.0p-10);
+        const double rel = bg_walk_rel_err(W, K);
         const double eb = T * rel + T * (double)(4 * G + 64) * 0x1.0p-53;
         const double ncat = (double)(K + 2);
         const bool ok = keep && !badg && T > 4.0 * eb && T < INFINITY && !a.force_replay;
         const double d2 = (8.0 * ncat + 64.0) * 0x1.0p-53 + eb / T * (1.0 + (T + eb) / (T - eb));
         const double Ub = u * T, Db = d2 * T, Tb = Ub - Db;
         const bool mine = ok && Bpre + Bl >= Tb && (part == 0 || Bpre < Tb);
-        int cst = 0;
-        double P = Bpre;
-#pragma unroll
-        for (int i = 1; i < 8; ++i) {
-            const bool in = i * Cz < nb && Bpre + s1.pre[i] < Tb;
-            cst = in ? i : cst;
-            P = in ? Bpre + s1.pre[i] : P;
-        }
+        double P;
+        const int cst = bg_chunk_start(s1.pre, Cz, nb, Bpre, Tb, P);
         STAMP(3);
         Find f2{P, Tb, Ub, Db, -1, false, false, 0u, 0u, 0u};
         const int xs = x0 + cst * Cz;
@@ -415,7 +324,7 @@ __device__ __forceinline__ void bg_tiles(const BgArgs &a, unsigned char *lds, ui
                 if (rk >= 0)
                     a.pwms_out[sq] = rw;
                 else
-                    raise_error(a, 2, gidx);  // every category missed (.fs:752)
+                    raise_error(a.err_code, a.err_index, 2, gidx);  // every category missed (.fs:752)
             }
         }
     }

@@ -34,8 +34,10 @@
 #include <algorithm>
 
 #include "gs_bgregime.h"
+#include "gs_bgwalk.h"
 #include "gs_common.h"
 #include "gs_fold.h"
+#include "gs_packed.h"
 #include "gs_pick.h"
 #include "gs_stamps.h"
 #include "gs_wave.h"
@@ -43,9 +45,6 @@
 using namespace gs;
 
 namespace {
-
-typedef short s2 __attribute__((ext_vector_type(2)));
-
 
 // LDS carve (bytes): workgroup-shared tables, then one 16 KB slice per wavefront
 // (the lanes' fine tables; the exact rescan's staging area afterwards).
@@ -75,43 +74,6 @@ static_assert(F_MISC + 64 <= kDnaFineBytes, "rescan scratch");
 constexpr int kFix = 24;
 constexpr int32_t kOaBad = (int32_t)0x80000000;  // own-cell term out of range
 
-__device__ __forceinline__ uint32_t pk_add(uint32_t x, uint32_t y) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(s2, x) + __builtin_bit_cast(s2, y));
-}
-
-// The window completed by a ring step: low int16 of the register it was born in
-// plus the high int16 of the register born 8 positions later, as a sign-extended
-// int32 (one SDWA add: the sum of two entries of at most 4 x 4095 never wraps).
-__device__ __forceinline__ int half_sum(uint32_t lo_reg, uint32_t hi_reg) {
-    int r;
-    asm("v_add_u16_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_SEXT src0_sel:WORD_0 "
-        "src1_sel:WORD_1"
-        : "=v"(r)
-        : "v"(lo_reg), "v"(hi_reg));
-    return r;
-}
-
-// count of symbol e among the first W symbols of a packed word (wmask: 2W bits)
-__device__ __forceinline__ int sym_count(uint32_t x, int e, uint32_t wmask) {
-    const uint32_t y = ~(x ^ (0x55555555u * (uint32_t)e));
-    return __popc(y & (y >> 1) & 0x55555555u & wmask);
-}
-
-__device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, int sh) {
-    return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)sh);
-}
-
-__device__ __forceinline__ void raise_error(const DnaArgs &a, int code, int64_t gidx) {
-    atomicCAS(a.err_code, 0, code);
-    atomicMin(a.err_index, (unsigned long long)gidx);
-}
-
-__device__ __forceinline__ uint4 load_words(const uint32_t *p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);  // 4-byte aligned 16-byte load
-    return v;
-}
-
 // Ring state of one lane: the registers born at the last 16 positions (mod 16),
 // coarse and fine tables, and the running results.
 struct Ring {
@@ -133,20 +95,6 @@ constexpr int kChunkCk = 8;  // chunk prefixes kept in registers (lanes of <= 51
 struct Pipe {
     uint4 c[PD], f[PD];
 };
-
-// Pair code * 16 of position P of a chunk whose words are ww[1..4], ww[0] the word
-// before and ww[5] the first word of the next chunk (P < 64 + 14: ww[6] only
-// feeds bits that are masked off).
-template <int P>
-__device__ __forceinline__ uint32_t pair16(const uint32_t (&ww)[7]) {
-    constexpr int rr = P & 15, wi = (P >> 4) + 1;
-    uint32_t v;
-    if constexpr (rr >= 2)
-        v = funnel(ww[wi + 1], ww[wi], 2 * rr - 4);
-    else
-        v = funnel(ww[wi], ww[wi - 1], 28 + 2 * rr);
-    return v & 0xF0u;
-}
 
 template <int P>
 __device__ __forceinline__ void fetch(Pipe &pp, const uint32_t (&ww)[7], const unsigned char *coarse,
@@ -335,26 +283,7 @@ __device__ __forceinline__ V bg_walk(const uint32_t *seqw, int x0, int nwin, int
     return v;
 }
 
-// bg_walk visitors (state by value: lambdas capturing locals by reference left
-// them in scratch).  Pass 1: the lane's sum and its value at the starts of 8
-// chunks of Cz windows (whole 16-window blocks).
-struct BgSum {
-    double B, pre[8];
-    int ci, nck, Cz;
-    __device__ __forceinline__ void blk(int t) {
-        if (t == nck) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) pre[i] = i == ci ? B : pre[i];
-            ++ci;
-            nck += Cz;
-        }
-    }
-    static constexpr bool kStops = false;  // never ends a walk early
-    __device__ __forceinline__ bool win(int, double g) {
-        B = B + g;
-        return false;
-    }
-};
+// bg_walk / bg_walk_fast visitors: pass 1 is gs_bgwalk.h BgSum.
 // Pass 2: from running sum P, the first window whose upper boundary reaches Tb;
 // certified when Ub lies inside [lo + Db, hi - Db].
 struct BgFind {
@@ -384,19 +313,12 @@ struct BgFind {
 // pcv[0]^W times the product of its rows (s_j, 0); every next window is
 // g_k = g_{k-1} R[s_{k-1+W}][s_{k-1}], one product and one table read a window
 // instead of an integer log sum and an exp2.  Relative error of each g_k against
-// the reference's fold: bg_fast_rel_err.
+// the reference's fold: gs_common.h bg_walk_rel_err.  The table, the 16-window block
+// and pass 1's visitor are gs_bgwalk.h's, shared with gs_sweep_bg.hip.
 constexpr int kBgRows = 16;
 constexpr int kBgWordsOff = kBgRows * 64 * 8;
 constexpr int kBgQuads = (kDnaFineBytes - kBgWordsOff) / 1024;
 static_assert(kBgQuads >= 4, "staged words");
-
-__device__ __forceinline__ void bg_fast_table(double *rt, const double (&pcv)[4]) {
-    double inv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) inv[e] = 1.0 / pcv[e];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) rt[c * 64] = pcv[c & 3] * inv[c >> 2];
-}
 
 // The staged words of a lane's range, addressed from the walk's first word: word(i)
 // = word i (i >= -1; word -1 is prev0 when the walk starts at the staged range's
@@ -411,29 +333,6 @@ struct WordsLds {
         return *(const uint32_t *)(base + min(k >> 2, kBgQuads - 1) * 1024 + (k & 3) * 4);
     }
 };
-
-// One 16-window block: the 16 table reads are issued before the first product
-// (a product a window waited for its read otherwise); FULL: every window of the
-// block is in the lane's range.
-template <bool FULL, class V>
-__device__ __forceinline__ void bg_fast_block(double &g, bool &done, uint32_t nw, uint32_t ow, int b,
-                                              int nwin, int x0, const double *rt, V &v) {
-    double r[16];
-#pragma unroll
-    for (int R = 0; R < 16; ++R) {
-        const uint32_t ci = __builtin_amdgcn_ubfe(nw, 2 * R, 2), co = __builtin_amdgcn_ubfe(ow, 2 * R, 2);
-        r[R] = rt[(ci | (co << 2)) * 64];
-    }
-#pragma unroll
-    for (int R = 0; R < 16; ++R) {
-        if (R > 0 || b > 0) g = g * r[R];
-        if constexpr (V::kStops) {
-            if (!done && (FULL || b + R < nwin)) done = v.win(x0 + b + R, g);
-        } else {
-            if (FULL || b + R < nwin) v.win(x0 + b + R, g);
-        }
-    }
-}
 
 // One 16-window block a step, W <= 16: block k reads words k - 1, k and k + 1 of
 // the walk (in-symbols of its windows start at x0 + 16k + W - 1, out-symbols at
@@ -458,22 +357,14 @@ __device__ __forceinline__ V bg_walk_fast(const WordsLds &src, int x0, int nwin,
         const uint32_t nw = funnel(wc, wb, shn), ow = funnel(wb, wa, 30);
         v.blk(b);
         if (b + 16 <= nwin)
-            bg_fast_block<true>(g, done, nw, ow, b, nwin, x0, rt, v);
+            bg_walk_block<true>(g, done, nw, ow, b, nwin, x0, rt, v);
         else
-            bg_fast_block<false>(g, done, nw, ow, b, nwin, x0, rt, v);
+            bg_walk_block<false>(g, done, nw, ow, b, nwin, x0, rt, v);
         wa = wb;
         wb = wc;
         wc = wd;
     }
     return v;
-}
-
-// Relative error of bg_walk_fast's g_k (k - x0 < K steps) against the reference's
-// fold: the first window's 4W + 1 roundings (rows: 1 / pcv[0] and the product;
-// the multiplies; pcv[0]^W), per step three (1 / pcv, the table product, the
-// multiply), the reference's own W.
-__device__ __forceinline__ double bg_fast_rel_err(int W, int K) {
-    return (double)(5 * W + 3 * K + 20) * 0x1.0p-53 * (1.0 + 0x1.0p-10);
 }
 
 // Relative error of bg_walk's g_k against the reference's binary64 fold G_k /
@@ -487,162 +378,9 @@ __device__ __forceinline__ double bg_rel_err(int W, int f) {
 }
 
 
-// Exact binary64 rescan of sequence sq (wave-uniform) by the whole wavefront:
-// the reference's folds for every window (.fs:759-777), the pick certified
-// against rounding alone, else one lane replays the reference's sequential sums
-// (.fs:747-754).  Writes pos_out / pwms_out (or raises the overrun error) and
-// adds the new segment to the wavefront's aggregates.
 // Mark of a sequence left to the exact rescan (pos_out, overwritten before the
 // kernel ends).
 constexpr int32_t kFbMark = (int32_t)0x80000000;
-
-template <int WM>
-__device__ __forceinline__ void rescan_seq(const DnaArgs &a, int sq, uint64_t rng_stream,
-                                        unsigned char *wslice, const double2 *sPPM,
-                                        const int64_t *sT, int64_t sumT, int lane,
-                                        int32_t *waggC, int64_t *waggT STAMP_PARAMS) {
-    const int A = a.A, W = a.W;
-    const uint32_t wmask = W >= 16 ? 0xffffffffu : ((1u << (2 * W)) - 1u);
-    const int Lx = a.len[sq], px = a.pos_in[sq];
-    const int64_t wox = a.pkoff[sq];
-    const int64_t gx = a.global_offset + sq;
-    const double ux = a.u_in ? a.u_in[sq] : uniform(a.seed, rng_stream, (uint64_t)gx);
-    uint32_t gwx = 0;
-    if (px >= 0) {
-        const uint32_t *q = a.pk + wox + (px >> 4);
-        gwx = funnel(q[1], q[0], 2 * (px & 15)) & wmask;
-    }
-    uint8_t *sx = wslice + F_SEQ;
-    unsigned char *tab = wslice + F_TAB;
-    double *mpcv = (double *)(wslice + F_MISC);
-    int32_t *mres = (int32_t *)(wslice + F_MISC + 32);
-    // hold-one-out PCV (.fs:945-954), as in the scan
-    if (lane < A) {
-        const int64_t tot = sumT + (px >= 0 ? W : Lx);
-        const int64_t bgc =
-            sT[lane] + (px >= 0 ? sym_count(gwx, lane, wmask) : a.comp[(int64_t)sq * (A + 1) + lane]);
-        mpcv[lane] = ((double)bgc + a.pc) / ((double)tot + a.apc);
-    }
-    // unpack the sequence: one word (16 symbols) per lane step
-    const int nwx = (Lx + 15) >> 4;
-    for (int i = lane; i < nwx; i += 64) {
-        const uint32_t v = a.pk[wox + i];
-        uint32_t d[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) x |= ((v >> (2 * (4 * t + b))) & 3u) << (8 * b);
-            d[t] = x;
-        }
-        *(uint4 *)(sx + 16 * i) = keep_bytes(make_uint4(d[0], d[1], d[2], d[3]), Lx - 16 * i);
-    }
-    for (int i = 16 * nwx + 16 * lane; i < Lx + WM + 96; i += 16 * 64)
-        *(uint4 *)(sx + i) = make_uint4(0, 0, 0, 0);
-    wave_sync();
-    STAMP(11);
-    // (PWM, PCV) [e][tab_stride(WM)], columns past W (1, 1)
-    constexpr int WS = tab_stride(WM);
-    for (int c = lane; c < A * WS; c += 64) {
-        const int e = c / WS, j = c - e * WS;
-        double2 v = make_double2(1.0, 1.0);
-        if (j < W) {
-            const bool own = px >= 0 && (int)((gwx >> (2 * j)) & 3u) == e;
-            const double2 pp = sPPM[j * 4 + e];
-            const double pe = mpcv[e];
-            v = make_double2((own ? pp.y : pp.x) / pe, pe);
-        }
-        *(double2 *)(tab + (e * WS + j) * 16) = v;
-    }
-    wave_sync();
-    STAMP(12);
-    auto evx = [&](int k, double &gg, double &mm) {
-        exact_eval<WM>(sx, tab, a.thr_lo, a.cutoff, k, gg, mm);
-    };
-    const int Kx = Lx - W + 1;
-    const int Rx = (Kx + 63) >> 6;
-    const int kx_lo = lane * Rx, kx_hi = min(Kx, kx_lo + Rx);
-    double xG = 0.0, xM = 0.0;
-    bool neg = false;
-    int xcat = 0;
-    for (int k = kx_lo; k < kx_hi; ++k) {
-        double gg, mm;
-        evx(k, gg, mm);
-        xG = xG + gg;
-        neg |= !(gg >= 0.0);
-        if (mm != -INFINITY) {
-            xM = xM + mm;
-            neg |= !(mm >= 0.0);
-            ++xcat;
-        }
-    }
-    const int xpass = wave_sum_i32(xcat);
-    STAMP(13);
-    int pkk = -1;
-    const bool okx = __ballot(neg) == 0;
-    int kk = certified_pick<64>(evx, okx, Kx, Rx, lane, ux, xG, xM, xcat, xpass, 0.0, 0.0, 0.0, pkk);
-    if (kk < 0) {
-        // the reference's sequential sums (.fs:747-754) on one lane
-        if (lane == 0) {
-            atomicAdd(&GS_STAT(a)[1], 1ull);
-            double sacc = 0.0, acc = 0.0;
-            int rk = -1, rp = -1;
-            for (int pass = 0; pass < 4 && rk < 0; ++pass) {
-                for (int k = 0; k < Kx && rk < 0; ++k) {
-                    double gg, mm;
-                    evx(k, gg, mm);
-                    const double x = (pass & 1) ? mm : gg;
-                    if ((pass & 1) && mm == -INFINITY) continue;
-                    if (pass < 2) {
-                        sacc = sacc + x;
-                    } else {
-                        const double wgt = x / sacc;
-                        if (acc <= ux && ux <= acc + wgt) {
-                            rk = pass - 2;
-                            rp = k;
-                        }
-                        acc = acc + wgt;
-                    }
-                }
-            }
-            mres[0] = rk;
-            mres[1] = rp;
-        }
-        wave_sync();
-        kk = mres[0];
-        pkk = mres[1];
-    }
-    STAMP(14);
-    double xw = 0.0;
-    if (kk >= 0) {
-        double gg, mm;
-        evx(pkk, gg, mm);
-        xw = kk == 0 ? gg : mm;
-    }
-    if (kk < 0) {
-        if (lane == 0) {
-            raise_error(a, 2, gx);  // every category missed (.fs:752)
-            a.pos_out[sq] = -1;
-        }
-    } else {
-        const int newp = kk == 0 ? -1 : pkk;
-        if (lane == 0) {
-            a.pos_out[sq] = newp;
-            a.pwms_out[sq] = xw;
-        }
-        if (newp >= 0) {
-            // the new segment into the wavefront's aggregates
-            const int e = lane < W ? sx[newp + lane] : 0;
-            if (lane < W) atomicAdd(&waggC[e * W + lane], 1);
-            if (lane < A) {
-                int sc = 0;
-                for (int j = 0; j < W; ++j) sc += sx[newp + j] == lane ? 1 : 0;
-                waggT[lane] += (int64_t)(a.comp[(int64_t)sq * (A + 1) + lane] - sc);
-            }
-        }
-    }
-    wave_sync();  // the staging area is rewritten for the next sequence
-}
 
 }  // namespace
 
@@ -831,7 +569,7 @@ __global__ void __launch_bounds__(64 * kDnaWaves) gs_sweep_dna_kernel(DnaArgs a)
             // ---- hold-one-out background; E == A: no other symbols ----
             const int64_t tot = sumT + (p >= 0 ? W : L);
             if (act && tot > 2147483647LL) {  // Checked Array.sum (.fs:117)
-                if (lead) raise_error(a, 3, gidx);
+                if (lead) raise_error(a.err_code, a.err_index, 3, gidx);
                 keep = false;
             }
             const double sbg = (double)tot + a.apc;
@@ -1069,7 +807,7 @@ __global__ void __launch_bounds__(64 * kDnaWaves) gs_sweep_dna_kernel(DnaArgs a)
                             (__attribute__((address_space(3))) void *)(wslice + kBgWordsOff + 1024 * i), 16,
                             0, 0);
                     if (x0 > 0) wl.prev0 = src[-1];
-                    bg_fast_table(rt, pcv);
+                    bg_ratio_table(rt, pcv);
                     for (int j = 0; j < W; ++j) pw0 = pw0 * pcv[0];
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
@@ -1115,7 +853,7 @@ __global__ void __launch_bounds__(64 * kDnaWaves) gs_sweep_dna_kernel(DnaArgs a)
                 const double T = Br + Mr;
                 // every weight's error: the backgrounds' relative bound, the motifs' eps,
                 // the scale's rounding
-                const double rel = fast ? bg_fast_rel_err(W, K) : bg_rel_err(W, fw);
+                const double rel = fast ? bg_walk_rel_err(W, K) : bg_rel_err(W, fw);
                 const double eb = Br * rel + (double)npass * eps + T * 0x1.0p-50;
                 const bool ok2 = bgl && !bgbadg && T > 4.0 * eb && T < INFINITY;
                 const double d2 = (8.0 * ncat + 64.0) * 0x1.0p-53 + eb / T * (1.0 + (T + eb) / (T - eb));
@@ -1130,14 +868,8 @@ __global__ void __launch_bounds__(64 * kDnaWaves) gs_sweep_dna_kernel(DnaArgs a)
                 // the last chunk that starts below it
                 const double Ub = Ur / scale, Db = Dr / scale, Tb = Ub - Db;
                 const bool mine_bg = ok2 && !ok && Bpre + Bl >= Tb && (part == 0 || Bpre < Tb);
-                int cst = 0;
-                double P = Bpre;
-#pragma unroll
-                for (int i = 1; i < 8; ++i) {
-                    const bool in = i * Cz < nb && Bpre + bs.pre[i] < Tb;
-                    cst = in ? i : cst;
-                    P = in ? Bpre + bs.pre[i] : P;
-                }
+                double P;
+                const int cst = bg_chunk_start(bs.pre, Cz, nb, Bpre, Tb, P);
                 BgFind bf{P, Tb, Ub, Db, -1, false, false};
                 if (fast) {
                     wl.w0 = cst * Cz / 16;
@@ -1394,8 +1126,10 @@ __global__ void __launch_bounds__(64 * kDnaWaves) gs_sweep_dna_kernel(DnaArgs a)
             while (todo) {
                 const int src = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
-                rescan_seq<WM>(a, __builtin_amdgcn_readlane(seq, src), rng_stream, wslice, sPPM, sT,
-                               sumT, lane, waggC, waggT STAMP_ARGS);
+                // (gs_packed.h, inlined here; its phases are stamp slots 11..14)
+                rescan_packed<WM>(a, __builtin_amdgcn_readlane(seq, src), rng_stream, wslice, F_SEQ,
+                                  F_TAB, F_MISC, sPPM, sT, sumT, lane, waggC, waggT,
+                                  [&](int i) { STAMP(i); });
             }
         }
     }

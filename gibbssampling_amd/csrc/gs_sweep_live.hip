@@ -31,7 +31,7 @@
 //     binary64 fold of PPM'/PCV, then log2 (.fs:283-292, .fs:737);
 //  5. whatever the bound cannot settle (a pick near a CDF boundary or among the
 //     backgrounds, a target without a passing window) is rescanned exactly in
-//     binary64 by the whole wavefront right after its tile (rescan_target); the last
+//     binary64 by the whole wavefront right after its tile (rescan_packed); the last
 //     workgroup (a done counter) reduces the aggregate replicas into one vector and
 //     adds the rank's symbol totals (compsum) to T.
 //
@@ -43,6 +43,7 @@
 #include "gs_bgregime.h"
 #include "gs_common.h"
 #include "gs_fold.h"
+#include "gs_packed.h"
 #include "gs_pick.h"
 #include "gs_stamps.h"
 #include "gs_wave.h"
@@ -62,8 +63,6 @@ __device__ __forceinline__ KDnaArgs *kargs_dna() {
 #define KD(f) (kargs_dna()->f)
 
 namespace {
-
-typedef short s2 __attribute__((ext_vector_type(2)));
 
 // Timing experiments only (make variant VFLAGS=-DGS_EXP=n, never the shipped
 // library): phases skipped, bit 1 refine, 2 pick and fold, 4 aggregates, 8 scan,
@@ -92,10 +91,6 @@ constexpr int O_WAVE = (O_RT + 8 * RT_G * 4 + 255) & ~255;  // 256-aligned: lane
 static_assert(O_RT % 16 == 0 && O_WAVE % 256 == 0, "carve");
 
 constexpr int32_t kEntryMax = 4095;  // |filter entry| (units 2^-cs): 8 of them fit an int16
-
-__device__ __forceinline__ uint32_t pk_add(uint32_t x, uint32_t y) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(s2, x) + __builtin_bit_cast(s2, y));
-}
 
 // Quad DPP permute (quad_perm control CTRL) of an int; every lane has a source.
 template <int CTRL>
@@ -128,38 +123,6 @@ __device__ __forceinline__ int64_t grp_bcast_i64(int64_t x, int q) {
     return (int64_t)(((uint64_t)(uint32_t)h2 << 32) | (uint32_t)l2);
 }
 
-// The window completed by a ring step: the low int16 of the register it was born in
-// plus the high int16 of the register born 8 positions later, sign-extended.
-__device__ __forceinline__ int half_sum(uint32_t lo_reg, uint32_t hi_reg) {
-    int r;
-    asm("v_add_u16_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_SEXT src0_sel:WORD_0 "
-        "src1_sel:WORD_1"
-        : "=v"(r)
-        : "v"(lo_reg), "v"(hi_reg));
-    return r;
-}
-
-// count of symbol e among the first W symbols of a packed word (wmask: 2W bits)
-__device__ __forceinline__ int sym_count(uint32_t x, int e, uint32_t wmask) {
-    const uint32_t y = ~(x ^ (0x55555555u * (uint32_t)e));
-    return __popc(y & (y >> 1) & 0x55555555u & wmask);
-}
-
-__device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, int sh) {
-    return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)sh);
-}
-
-__device__ __forceinline__ void raise_error(const DnaArgs &a, int code, int64_t gidx) {
-    atomicCAS(KD(err_code), 0, code);
-    atomicMin(KD(err_index), (unsigned long long)gidx);
-}
-
-__device__ __forceinline__ uint4 load_words(const uint32_t *p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);  // 4-byte aligned 16-byte load
-    return v;
-}
-
 // ---- the filter ring ----------------------------------------------------------
 // Register i (mod 16) is born at position i with the row's dword 0 (groups 0 and 4);
 // the rows of later positions add their groups g (dword g & 3) into the register of
@@ -172,19 +135,6 @@ constexpr int PD = 2;  // table rows in flight (64 % PD == 0)
 struct Pipe {
     uint4 c[PD];
 };
-
-// pair code * 16 of position P of a chunk whose words are ww[1..4] (ww[5], ww[6]:
-// the next chunk's first words)
-template <int P>
-__device__ __forceinline__ uint32_t pair16(const uint32_t (&ww)[7]) {
-    constexpr int rr = P & 15, wi = (P >> 4) + 1;
-    uint32_t v;
-    if constexpr (rr >= 2)
-        v = funnel(ww[wi + 1], ww[wi], 2 * rr - 4);
-    else
-        v = funnel(ww[wi], ww[wi - 1], 28 + 2 * rr);
-    return v & 0xF0u;
-}
 
 // The workgroup tables by LDS address (the kernels have no static LDS: the dynamic
 // block starts at address 0, checked in the prologue), so that the table's offset
@@ -314,166 +264,13 @@ __device__ __forceinline__ double picked_weight(uint32_t win, uint32_t gw, bool 
     return log(S * 1.0) / kLn2;
 }
 
-// Exact binary64 rescan of target sq (wave-uniform) by the whole wavefront: the
-// reference's folds for every window (.fs:759-777), the pick certified against
-// rounding alone, else one lane replays the reference's sequential sums
-// (.fs:747-754).  Writes pos_out / pwms_out (or raises the overrun error) and adds
-// the new segment to the wavefront's aggregates.  Staging in the wavefront's slice:
-// the unpacked sequence at 0, the (PWM, PCV) table at tab_off, scratch after it.
-// BYREF: the kernel arguments through `a` (a function called out of line has no
-// kernarg segment pointer of its own: the caller passes the segment, ArgT =
-// KDnaArgs); else by KD (scalar loads where used).
-template <int WM, bool BYREF = false, class ArgT = DnaArgs>
-__device__ void rescan_target(const ArgT &a, int sq, uint64_t rng_stream, unsigned char *wslice,
-                              int tab_off, const double2 *sPPM, const int64_t *sT, int64_t sumT,
-                              int lane, int32_t *waggC, int64_t *waggT) {
-    const int A = a.A, W = a.W;
-    const uint32_t wmask = W >= 16 ? 0xffffffffu : ((1u << (2 * W)) - 1u);
-    const int Lx = a.len[sq], px = a.pos_in[sq];
-    const int64_t wox = a.pkoff[sq];
-    const int64_t gx = a.global_offset + sq;
-    const double ux = a.u_in ? a.u_in[sq] : uniform(a.seed, rng_stream, (uint64_t)gx);
-    uint32_t gwx = 0;
-    if (px >= 0) {
-        const uint32_t *q = a.pk + wox + (px >> 4);
-        gwx = funnel(q[1], q[0], 2 * (px & 15)) & wmask;
-    }
-    uint8_t *sx = wslice;
-    constexpr int WS = tab_stride(WM);
-    unsigned char *tab = wslice + tab_off;
-    double *mpcv = (double *)(wslice + tab_off + 4 * WS * 16);
-    int32_t *mres = (int32_t *)(wslice + tab_off + 4 * WS * 16 + 32);
-    // hold-one-out PCV (.fs:945-954)
-    if (lane < A) {
-        const int64_t tot = sumT + (px >= 0 ? W : Lx);
-        const int64_t bgc =
-            sT[lane] + (px >= 0 ? sym_count(gwx, lane, wmask) : a.comp[(int64_t)sq * (A + 1) + lane]);
-        mpcv[lane] = ((double)bgc + a.pc) / ((double)tot + a.apc);
-    }
-    // unpack the sequence: one word (16 symbols) per lane step
-    const int nwx = (Lx + 15) >> 4;
-    for (int i = lane; i < nwx; i += 64) {
-        const uint32_t v = a.pk[wox + i];
-        uint32_t d[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) x |= ((v >> (2 * (4 * t + b))) & 3u) << (8 * b);
-            d[t] = x;
-        }
-        *(uint4 *)(sx + 16 * i) = keep_bytes(make_uint4(d[0], d[1], d[2], d[3]), Lx - 16 * i);
-    }
-    for (int i = 16 * nwx + 16 * lane; i < Lx + WM + 96; i += 16 * 64)
-        *(uint4 *)(sx + i) = make_uint4(0, 0, 0, 0);
-    wave_sync();
-    // (PWM, PCV) [e][WS], columns past W (1, 1)
-    for (int c = lane; c < A * WS; c += 64) {
-        const int e = c / WS, j = c - e * WS;
-        double2 v = make_double2(1.0, 1.0);
-        if (j < W) {
-            const bool own = px >= 0 && (int)((gwx >> (2 * j)) & 3u) == e;
-            const double2 pp = sPPM[j * 4 + e];
-            const double pe = mpcv[e];
-            v = make_double2((own ? pp.y : pp.x) / pe, pe);
-        }
-        *(double2 *)(tab + (e * WS + j) * 16) = v;
-    }
-    wave_sync();
-    const double thr_lo = BYREF ? a.thr_lo : KD(thr_lo);
-    auto evx = [&](int k, double &gg, double &mm) {
-        exact_eval<WM>(sx, tab, thr_lo, a.cutoff, k, gg, mm);
-    };
-    const int Kx = Lx - W + 1;
-    const int Rx = (Kx + 63) >> 6;
-    const int kx_lo = lane * Rx, kx_hi = min(Kx, kx_lo + Rx);
-    double xG = 0.0, xM = 0.0;
-    bool neg = false;
-    int xcat = 0;
-    for (int k = kx_lo; k < kx_hi; ++k) {
-        double gg, mm;
-        evx(k, gg, mm);
-        xG = xG + gg;
-        neg |= !(gg >= 0.0);
-        if (mm != -INFINITY) {
-            xM = xM + mm;
-            neg |= !(mm >= 0.0);
-            ++xcat;
-        }
-    }
-    const int xpass = wave_sum_i32(xcat);
-    int pkk = -1;
-    const bool okx = __ballot(neg) == 0;
-    int kk = certified_pick<64>(evx, okx, Kx, Rx, lane, ux, xG, xM, xcat, xpass, 0.0, 0.0, 0.0, pkk);
-    if (kk < 0) {
-        // the reference's sequential sums (.fs:747-754) on one lane
-        if (lane == 0) {
-            atomicAdd(&((BYREF ? a.fallbacks : KD(fallbacks)) + (blockIdx.x % kRepl) * kStatStride)[1], 1ull);
-            double sacc = 0.0, acc = 0.0;
-            int rk = -1, rp = -1;
-            for (int pass = 0; pass < 4 && rk < 0; ++pass) {
-                for (int k = 0; k < Kx && rk < 0; ++k) {
-                    double gg, mm;
-                    evx(k, gg, mm);
-                    const double x = (pass & 1) ? mm : gg;
-                    if ((pass & 1) && mm == -INFINITY) continue;
-                    if (pass < 2) {
-                        sacc = sacc + x;
-                    } else {
-                        const double wgt = x / sacc;
-                        if (acc <= ux && ux <= acc + wgt) {
-                            rk = pass - 2;
-                            rp = k;
-                        }
-                        acc = acc + wgt;
-                    }
-                }
-            }
-            mres[0] = rk;
-            mres[1] = rp;
-        }
-        wave_sync();
-        kk = mres[0];
-        pkk = mres[1];
-    }
-    double xw = 0.0;
-    if (kk >= 0) {
-        double gg, mm;
-        evx(pkk, gg, mm);
-        xw = kk == 0 ? gg : mm;
-    }
-    if (kk < 0) {
-        if (lane == 0) {
-            // every category missed (.fs:752)
-            atomicCAS(BYREF ? a.err_code : KD(err_code), 0, 2);
-            atomicMin(BYREF ? a.err_index : KD(err_index), (unsigned long long)gx);
-            (BYREF ? a.pos_out : KD(pos_out))[sq] = -1;
-        }
-    } else {
-        const int newp = kk == 0 ? -1 : pkk;
-        if (lane == 0) {
-            (BYREF ? a.pos_out : KD(pos_out))[sq] = newp;
-            (BYREF ? a.pwms_out : KD(pwms_out))[sq] = xw;
-        }
-        if (newp >= 0) {
-            // the new segment into the wavefront's aggregates
-            const int e = lane < W ? sx[newp + lane] : 0;
-            if (lane < W) atomicAdd(&waggC[e * W + lane], 1);
-            if (lane < A) {
-                int sc = 0;
-                for (int j = 0; j < W; ++j) sc += sx[newp + j] == lane ? 1 : 0;
-                waggT[lane] += (int64_t)(a.comp[(int64_t)sq * (A + 1) + lane] - sc);
-            }
-        }
-    }
-    wave_sync();  // the staging area is rewritten for the next target
-}
-
-// The exact rescan out of line (a cold path: its registers stay out of the tile loop's,
-// round 6: the live kernel's too, as the long sweep's); the kernel arguments through the
-// kernarg segment the kernel passes (made wave-uniform here, so its fields are scalar
-// loads; a reference to the kernel's by-value argument would copy the whole struct to
-// scratch).
+// The exact rescan (gs_packed.h rescan_packed) out of line, for this kernel and the long
+// sweep's (a cold path: its registers stay out of the tile loop's, round 6: the live
+// kernel's too, as the long sweep's); the kernel arguments through the kernarg segment
+// the kernel passes (made wave-uniform here, so its fields are scalar loads; a reference
+// to the kernel's by-value argument would copy the whole struct to scratch).  Staging in
+// the wavefront's slice: the unpacked sequence at 0, the (PWM, PCV) table at tab_off,
+// scratch after it.
 template <int WM>
 __device__ __attribute__((noinline)) void rescan_ool(KDnaArgs *ka_in, int sq, uint64_t rng_stream,
                                                      unsigned char *wslice, int tab_off, const double2 *sPPM,
@@ -483,9 +280,9 @@ __device__ __attribute__((noinline)) void rescan_ool(KDnaArgs *ka_in, int sq, ui
     const uint64_t pu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pv >> 32)) << 32) |
                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pv);
     KDnaArgs *ka = (KDnaArgs *)pu;
-    rescan_target<WM, true, KDnaArgs>(*ka, sq, rng_stream, wslice, tab_off, sPPM, sT, sumT, lane, waggC, waggT);
+    rescan_packed<WM>(*ka, sq, rng_stream, wslice, 0, tab_off, tab_off + 4 * tab_stride(WM) * 16, sPPM, sT, sumT,
+                      lane, waggC, waggT);
 }
-
 
 // A target without a passing window (its group's ntot is 0): its categories are the K
 // background products alone (.fs:759-784), the reference's binary64 folds of PCV over
@@ -557,7 +354,7 @@ __device__ __attribute__((noinline)) BgPick bg_pick(const uint32_t *words, uint3
     const double Tt = G > 1 ? __shfl(incl, gbase + G - 1, 64) : Bl;
     // each product within (5W + 3K + 20) 2^-53 of the reference's fold, the sums' and
     // the group scan's roundings, the roulette's own: gs_sweep_bg.hip's margins
-    const double rel = (double)(5 * W + 3 * K + 20) * 0x1.0p-53 * (1.0 + 0x1.0p-10);
+    const double rel = bg_walk_rel_err(W, K);
     const double eb = Tt * rel + Tt * (double)(4 * G + 64) * 0x1.0p-53;
     const double ncb = (double)(K + 2);
     const bool okb = bgo && Tt > 4.0 * eb && Tt < INFINITY;
@@ -954,7 +751,7 @@ __global__ void __launch_bounds__(64 * kLiveWaves, GS_LIVE_WAVES_PER_EU) gs_swee
         // ---- hold-one-out background; no symbol outside the alphabet ----
         const int64_t tot = sumT + (p >= 0 ? W : L);
         if (act && tot > 2147483647LL) {  // Checked Array.sum (.fs:117)
-            if (lead) raise_error(a, 3, gidx);
+            if (lead) raise_error(KD(err_code), KD(err_index), 3, gidx);
             keep = false;
         }
 #if defined(GS_LIVE_DEBUG)
@@ -1339,7 +1136,7 @@ __global__ void __launch_bounds__(64 * kLiveWaves, GS_LIVE_WAVES_PER_EU) gs_swee
         // ---- aggregates of the new snapshot: C[a][j] += segment; T[a] = the rank's
         // symbol totals (added once, by the last workgroup's reduction) less every kept
         // segment's symbols and the whole composition of every target left without
-        // one here (rescan_target adds composition - segment for those that keep one) ----
+        // one here (rescan_packed adds composition - segment for those that keep one) ----
         {
             const bool km = lead && keep && !need_fb && pk >= 0 && !(GS_EXP & 4);
             const uint32_t nsw = win;

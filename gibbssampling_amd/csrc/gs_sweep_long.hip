@@ -33,7 +33,7 @@
 //     quotients computed by W lanes of the row;
 //  5. targets the bound cannot settle (a window within the bound of the cut-off, a
 //     pick within it of a CDF boundary) are rescanned exactly by the whole wavefront
-//     (gs_sweep_live.hip rescan_target); targets without a passing window take the
+//     (gs_packed.h rescan_packed); targets without a passing window take the
 //     background walk (bg_pick); aggregates, flush and done counter as the live sweep.
 //
 // Compiled with -ffp-contract=off: no FMA contraction.
@@ -226,22 +226,6 @@ __device__ __forceinline__ void long_scan(const uint32_t (&w)[kRawWords], uint32
     rows[0] = load_row<NG / 2>(row_addr<0>(w, tabv));
     rows[1] = load_row<NG / 2>(row_addr<1>(w, tabv));
     long_steps<NG, PD, 0, NPOS, KU>(R, rows, w, tabv, nwin, thr_hi, thr_lo, bsum, M, dmin);
-}
-
-// The exact rescan out of line (a cold path: its registers stay out of the scan's);
-// the kernel arguments through the kernarg segment the kernel passes (made
-// wave-uniform here, so its fields are scalar loads; a reference to the kernel's
-// by-value argument would copy the whole struct to scratch).
-template <int WM>
-__device__ __attribute__((noinline)) void long_rescan(KDnaArgs *ka_in, int sq, uint64_t rng_stream,
-                                                      unsigned char *wslice, int tab_off, const double2 *sPPM,
-                                                      const int64_t *sT, int64_t sumT, int lane, int32_t *waggC,
-                                                      int64_t *waggT) {
-    const uint64_t pv = (uint64_t)ka_in;
-    const uint64_t pu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pv >> 32)) << 32) |
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pv);
-    KDnaArgs *ka = (KDnaArgs *)pu;
-    rescan_target<WM, true, KDnaArgs>(*ka, sq, rng_stream, wslice, tab_off, sPPM, sT, sumT, lane, waggC, waggT);
 }
 
 // A target without a passing window on the long sweep's row (gs_sweep_live.hip bg_pick's
@@ -555,7 +539,7 @@ __global__ void __launch_bounds__(64 * kLongWaves, GS_LONG_WAVES_PER_EU) gs_swee
         bool keep = act;
         const int64_t tot = sumT + (p >= 0 ? W : L);
         if (act && tot > 2147483647LL) {  // Checked Array.sum (.fs:117)
-            if (q == 0) raise_error(a, 3, gidx);
+            if (q == 0) raise_error(KD(err_code), KD(err_index), 3, gidx);
             keep = false;
         }
         const int K = L - W + 1;
@@ -890,7 +874,7 @@ __global__ void __launch_bounds__(64 * kLongWaves, GS_LONG_WAVES_PER_EU) gs_swee
         // ---- aggregates of the new snapshot: C[a][j] += segment; T[a] = the rank's
         // symbol totals (the last workgroup adds them) less every kept segment's
         // symbols and the whole composition of every target left without one here
-        // (rescan_target adds composition - segment for those that keep one) ----
+        // (rescan_packed adds composition - segment for those that keep one) ----
         const bool km = keep && !need_fb && pk >= 0;
         if (km)
             for (int j = q; j < W; j += kLpt) atomicAdd(&waggC[(int)((win >> (2 * j)) & 3u) * W + j], 1);
@@ -908,7 +892,9 @@ __global__ void __launch_bounds__(64 * kLongWaves, GS_LONG_WAVES_PER_EU) gs_swee
         wave_sync();
         for (unsigned long long fm = fbm; fm != 0ull; fm &= fm - 1ull) {
             const int sqx = __builtin_amdgcn_readfirstlane(__shfl(sq, __ffsll((long long)fm) - 1, 64));
-            long_rescan<WM>(kargs_dna(), sqx, rng_stream, wslice, tab_off, sPPM, sT, sumT, lane, waggC, waggT);
+            // (gs_sweep_live.hip's out-of-line wrapper of gs_packed.h rescan_packed: a cold
+            // path, its registers stay out of the scan's)
+            rescan_ool<WM>(kargs_dna(), sqx, rng_stream, wslice, tab_off, sPPM, sT, sumT, lane, waggC, waggT);
         }
         if (it == GS_LONG_TL_IT) TLINE(tl_w, 6);
         bc = bn;

@@ -41,7 +41,8 @@ SOURCES = ["gibbssampling_amd/csrc/gs_sweep_live.hip", "gibbssampling_amd/csrc/g
            "gibbssampling_amd/csrc/gs_sweep_long.hip",
            "gibbssampling_amd/csrc/gs_bgregime.h", "gibbssampling_amd/csrc/gs_common.h",
            "gibbssampling_amd/csrc/gs_wave.h", "gibbssampling_amd/csrc/gs_fold.h",
-           "gibbssampling_amd/csrc/gs_pick.h", "gibbssampling_amd/csrc/Makefile"]
+           "gibbssampling_amd/csrc/gs_pick.h", "gibbssampling_amd/csrc/gs_packed.h",
+           "gibbssampling_amd/csrc/gs_bgwalk.h", "gibbssampling_amd/csrc/Makefile"]
 VALU_PEAK = 256 * 4 * 2.4e9 / 2  # wave64 VALU instructions per second, whole chip
 SWEEP_KERNELS = ("gs_sweep_live_kernel", "gs_sweep_dna_kernel", "gs_sweep_long_kernel",
                  "gs_sweep_bg_kernel", "gs_sweep_kernel")

@@ -26,7 +26,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 SOURCES = ["gibbssampling_amd/csrc/gs_sweep.hip", "gibbssampling_amd/csrc/gs_common.h",
            "gibbssampling_amd/csrc/gs_wave.h", "gibbssampling_amd/csrc/gs_fold.h",
-           "gibbssampling_amd/csrc/gs_stamps.h", "gibbssampling_amd/csrc/Makefile"]
+           "gibbssampling_amd/csrc/gs_pick.h", "gibbssampling_amd/csrc/gs_stamps.h",
+           "gibbssampling_amd/csrc/Makefile"]
 
 
 def _code_only(text: str) -> str:

@@ -31,7 +31,8 @@ def main():
         name, _, regime = spec.partition(":")  # cfg3:uniform = uniform random starts
         w = synthetic.CONFIGS[name]
         codes, offsets = synthetic.generate(w)
-        ctx = _native.Context(0, lib_path, tuning={"dna_mode": 1})
+        # (live_mode / long_mode 0: the engine would otherwise take the later packed kernels)
+        ctx = _native.Context(0, lib_path, tuning={"dna_mode": 1, "live_mode": 0, "long_mode": 0})
         f = ctx.lib.gs_debug_stamps
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         buf = np.zeros(SLOTS, np.uint64)
