@@ -160,6 +160,11 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_motif_run_batch": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, vp, vp,
                                          vp]),
         "gs_run_batch_last_ms": (C.c_int, [vp, vp]),
+        "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
+                                               vp, vp, vp, vp, vp]),
+        "gs_motif_run_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, u64, i64, i32, vp, vp, vp]),
+        "gs_run_multi_batch_last_ms": (C.c_int, [vp, vp]),
+        "gs_run_multi_batch_last_info": (C.c_int, [vp, vp]),
         "gs_set_fixed_pcv": (C.c_int, [vp, vp]),
         "gs_set_fixed_ppm": (C.c_int, [vp, vp, i32]),
         "gs_site_scan": (C.c_int, [vp, i32, f64, vp, vp, vp]),
@@ -520,6 +525,76 @@ class Context:
         out = np.zeros(2, np.float64)
         self._check(self.lib.gs_run_batch_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
+
+    def motif_run_multi_batch(self, motif_amount: int, W: int, pc: float, cutoff: float,
+                              n_sweeps: int, seeds, cnt=None, pos=None, init_mode: int = 0,
+                              first_sweep: int = 0, cap: int | None = None, u=None,
+                              strict: bool = False):
+        """R independent chains of n_sweeps sweeps with Positions lists (any motifAmount) in
+        one call, row r exactly n_sweeps motif_sweep_multi calls, each fed the previous
+        output, with the counter RNG's uniforms of seeds[r] -> (cnt[R, N], pos[R, N, cap],
+        pwms[R, N], status[R]).  The starts are the lists (cnt[R, N], pos[R, N, cap]; implies
+        init_mode -1) or those of random_starts(W, pc, seeds[r], init_mode) as one-position
+        lists.  u[R, n_sweeps, N] replaces the uniforms.  pwms is unspecified for n_sweeps =
+        0.  A chain that raises (status[r] != 0) leaves the other rows valid; errors of the
+        call itself raise, and with strict=True so does a chain's."""
+        cap = int(cap or motif_amount)
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R = len(seeds)
+        if (cnt is None) != (pos is None):
+            raise ArgumentError(GS_E_ARG, "cnt and pos go together")
+        if cnt is not None:
+            init_mode = -1
+            cnt = np.array(cnt, dtype=np.int32, copy=True)
+            pos = np.array(pos, dtype=np.int32, copy=True)
+            if cnt.shape != (R, self.n_local) or pos.size != R * self.n_local * max(cap, 0):
+                raise ArgumentError(GS_E_ARG, "cnt / pos need one row per seed, one list per sequence")
+            pos = np.ascontiguousarray(pos.reshape(R, self.n_local, cap))
+        else:
+            if init_mode not in (0, 1):
+                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
+            cnt = np.zeros((R, self.n_local), np.int32)
+            pos = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (R, max(int(n_sweeps), 0), self.n_local):
+                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        st = self.lib.gs_motif_run_multi_batch(
+            self.h, int(motif_amount), int(W), float(pc), float(cutoff), int(n_sweeps), _ptr(seeds),
+            R, int(first_sweep), int(init_mode), cap, _ptr(u), _ptr(cnt), _ptr(pos), _ptr(pwms),
+            _ptr(status))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        return cnt, pos, pwms, status
+
+    def motif_run_multi(self, motif_amount: int, W: int, pc: float, cutoff: float, n_sweeps: int,
+                        seed: int, cnt, pos, first_sweep: int = 0, cap: int | None = None):
+        """n_sweeps chained sweeps with Positions lists on the device from (cnt, pos) ->
+        (cnt, pos[N, cap], pwms): motif_run_multi_batch with one chain."""
+        cap = int(cap or motif_amount)
+        cnt, pos = self._lists(cnt, pos, cap)
+        pwms = np.zeros(self.n_local, np.float64)
+        self._check(self.lib.gs_motif_run_multi(self.h, int(motif_amount), int(W), float(pc),
+                                                float(cutoff), int(n_sweeps),
+                                                int(seed) & (2**64 - 1), int(first_sweep), cap,
+                                                _ptr(cnt), _ptr(pos), _ptr(pwms)))
+        return cnt, pos, pwms
+
+    def run_multi_batch_last_ms(self):
+        """Device milliseconds of the last motif_run_multi_batch: (starts and their
+        aggregates, sweeps)."""
+        out = np.zeros(2, np.float64)
+        self._check(self.lib.gs_run_multi_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def run_multi_batch_last_info(self) -> dict:
+        """Overflow handling of the last motif_run_multi_batch: pairs rescored by overflow
+        launches, chains parked, resume rounds, the first arena's capacity."""
+        out = np.zeros(4, np.int32)
+        self._check(self.lib.gs_run_multi_batch_last_info(self.h, _ptr(out)))
+        return dict(zip(("rescored", "parked", "resume_rounds", "arena"), (int(v) for v in out)))
 
     def set_fixed_pcv(self, pcv49) -> None:
         """The caller's ProbabilityCompositeVector (49 slots) for the ByPCV / WithBPV

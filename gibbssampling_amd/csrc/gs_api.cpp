@@ -50,6 +50,7 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(multi_batch_fill, v >= 1 && v <= 4096),
     GS_TUNING_FIELD(run_batch_clear, v == 0 || v == 1),
     GS_TUNING_FIELD(run_batch_blocks, v >= 1 && v <= 32),
+    GS_TUNING_FIELD(run_multi_arena_max, v >= 2048 && v <= (double)(1 << 28)),
     GS_TUNING_FIELD(batch_starts, v == -1 || v == 0 || v == 1),
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
     GS_TUNING_FIELD(site_switch, v >= 0 && v <= 1e9),
@@ -1055,6 +1056,57 @@ int gs_run_batch_last_ms(const gs_ctx *c, double out[2]) {
     if (!c || !out) return GS_E_ARG;
     out[0] = c->run_batch_ms[0];
     out[1] = c->run_batch_ms[1];
+    return GS_OK;
+}
+
+int gs_motif_run_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,
+                             int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains,
+                             int64_t first_sweep, int32_t init_mode, int32_t cap, const double *u,
+                             int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
+                             int32_t *status_out) {
+    if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
+        return GS_E_ARG;
+    if (motif_amount < 1 || motif_amount > kMultiMaxAmount || cap < motif_amount ||
+        cap > kMultiMaxAmount)
+        return fail(c, GS_E_ARG, "motifAmount / list capacity out of range");
+    if (n_chains == 0) return GS_OK;
+    if (!seeds || (c->n_local > 0 && (!cnt_inout || !pos_inout || !pwms_out))) return GS_E_ARG;
+    int rc;
+    if ((rc = batch_entry_checks(
+             c, "gs_motif_run_multi_batch", W,
+             "a chain's aggregates are summed on one device: it needs all sequences there and "
+             "no communicator",
+             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
+             "gs_motif_sweep_multi)")))
+        return rc;
+    if (init_mode == -1)
+        for (int32_t r = 0; r < n_chains; ++r)
+            if ((rc = validate_lists(c, motif_amount, W, cap, cnt_inout + (int64_t)r * c->n_local,
+                                     pos_inout + (int64_t)r * c->n_local * cap)))
+                return rc;
+    drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
+    takeover_reset(c);
+    return run_multi_batch(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
+                           init_mode, cap, u, cnt_inout, pos_inout, pwms_out, status_out);
+}
+
+int gs_motif_run_multi(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,
+                       int32_t n_sweeps, uint64_t seed, int64_t first_sweep, int32_t cap,
+                       int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out) {
+    return gs_motif_run_multi_batch(c, motif_amount, W, pc, cutoff, n_sweeps, &seed, 1, first_sweep,
+                                    -1, cap, nullptr, cnt_inout, pos_inout, pwms_out, nullptr);
+}
+
+int gs_run_multi_batch_last_ms(const gs_ctx *c, double out[2]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->run_multi_batch_ms[0];
+    out[1] = c->run_multi_batch_ms[1];
+    return GS_OK;
+}
+
+int gs_run_multi_batch_last_info(const gs_ctx *c, int32_t out[4]) {
+    if (!c || !out) return GS_E_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = c->run_multi_batch_info[i];
     return GS_OK;
 }
 

@@ -1,9 +1,10 @@
-// gs_batch.cpp — the host drivers of the batched entry points (DESIGN.md §9.10-§9.15):
+// gs_batch.cpp — the host drivers of the batched entry points (DESIGN.md §9.10-§9.15, §9.19):
 // motif_batch (gs_motif_sampling_batch), site_batch (gs_site_sampling_batch), multi_batch
-// (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch) and starts_batch
-// (gs_random_starts_batch), over one copy of the stages they share.  gs_api.cpp validates
-// the arguments; the single-chain pieces they reuse (set_snapshot_dev, starts_enqueue,
-// starts_pass, greedy_carve, one_sweep) are in gs_engine.cpp.
+// (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch), run_multi_batch
+// (gs_motif_run_multi_batch) and starts_batch (gs_random_starts_batch), over one copy of the
+// stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
+// (set_snapshot_dev, starts_enqueue, starts_pass, greedy_carve, one_sweep) are in
+// gs_engine.cpp.
 #include "gs_ctx.h"
 
 namespace gs_host {
@@ -995,6 +996,301 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return report_chain_errors(c, herr, status_out, nullptr);
+}
+
+// R independent chains of T synchronous sweeps with Positions lists (any motifAmount),
+// DESIGN.md §9.19.  Stage 1: the chains' lists, uploaded (mode -1) or their starts as
+// one-position lists as in multi_batch; then the aggregates of every chain's lists.  Stage 2:
+// per sweep one launch of gs_run_multi_batch_sweep_kernel over the (chain, target) pairs, for
+// motifAmount >= 3 followed by a second one with a small grid of 16x arenas that takes the
+// overflowed pairs from a device list; lists double-buffered, aggregate rows rotating over
+// three buffers (the third cleared in-kernel).  One synchronisation; then, while a pair
+// overflowed the larger arena as well and parked its chain at sweep t, a further round runs
+// the chains parked at t from their intact snapshot of sweep t with the next arena size up,
+// their aggregates rebuilt from the lists.  One download.  The caller validated the arguments.
+int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
+                    const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
+                    const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
+                    int32_t *status_out) {
+    const int64_t n = c->n_local;
+    c->run_multi_batch_ms[0] = c->run_multi_batch_ms[1] = 0.0;
+    for (int i = 0; i < 4; ++i) c->run_multi_batch_info[i] = 0;
+    if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
+    if (n == 0) return GS_OK;
+    MultiArgs a{};
+    const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, false);
+    // (the kernel stages its pick in static LDS beside the carve: both have to fit)
+    size_t static_lds = 0;
+    HIP_TRY(c, gs_run_multi_batch_static_lds(&static_lds));
+    GS_TRY(multi_lds_check(c, lds + (int64_t)static_lds));
+    const int32_t cells = c->A * W + c->A;
+    const int64_t rows = (int64_t)R * n, agg_elems = (int64_t)R * cells + R;
+    const int64_t cpart_bytes = mode == 0 ? c->n_global * c->A * W * 4 : 0;
+    const int64_t u_elems = u ? rows * T : 0;
+    // the overflow list and its count a sweep: motifAmount >= 3 only
+    const int64_t ovf_elems = M >= 3 ? rows : 0, novf_elems = M >= 3 ? T : 0;
+    const int64_t arena_max = c->tune.run_multi_arena_max;
+    int blocks = 0;
+    HIP_TRY(c, gs_run_multi_batch_occupancy(&blocks, (size_t)lds));
+    blocks = std::max(1, std::min(blocks, c->tune.run_batch_blocks));
+    // motifAmount = 1 builds no level; for 2, level 1 has at most kmax entries: the first
+    // arena always holds it.  From 3 on a sweep has its overflow launch, while 16x arenas fit
+    // (its grid: a workgroup a CU, as many as 256 MiB of 16x arenas hold)
+    const int64_t kOvfGrid = c->n_cu, kOvfBytes = 256ll << 20;
+    const int64_t arena0 = M == 1 ? 0 : std::max<int64_t>(2048, 4 * (int64_t)a.kmax);
+    auto slot_bytes = [&](int64_t arena) { return (2 * (int64_t)a.kmax + 3 * arena) * 8; };
+    auto main_grid = [&](int64_t pairs, int64_t arena) {
+        const int64_t g = std::min<int64_t>(pairs, (int64_t)c->n_cu * blocks);
+        return std::max<int64_t>(1, std::min<int64_t>(g, kArenaBudget / slot_bytes(arena)));
+    };
+    auto ovf_arena = [&](int64_t arena) -> int64_t {
+        const int64_t big = arena * 16;
+        return M >= 3 && big <= arena_max && slot_bytes(big) <= kOvfBytes ? big : 0;
+    };
+    auto ovf_grid = [&](int64_t big) {
+        return std::max<int64_t>(1, std::min<int64_t>(kOvfGrid, kOvfBytes / slot_bytes(big)));
+    };
+    auto scratch_bytes = [&](int64_t pairs, int64_t arena) {
+        const int64_t big = ovf_arena(arena);
+        return std::max(main_grid(pairs, arena) * slot_bytes(arena),
+                        big ? ovf_grid(big) * slot_bytes(big) : 0);
+    };
+    // per chain: two list slabs, a PWMS row, three aggregate rows and skip words, error and
+    // park words, seed, control block, chain index (and the shared draws); the overflow
+    // list and counts; the explicit uniforms; the first round's arenas
+    GS_TRY(batch_bytes_refuse(
+        c, "gs_motif_run_multi_batch",
+        (int64_t)R * (n * (2 * (4 + 4 * (int64_t)cap) + 8 + (mode == 1 ? 4 : 0)) +
+                      3 * 8 * ((int64_t)cells + 1) + 8 + 4 + 8 + (int64_t)sizeof(SpecCtl) + 4) +
+            (ovf_elems + novf_elems) * 4 + u_elems * 8 + cpart_bytes +
+            scratch_bytes(rows, arena0)));
+    if (mode >= 0) GS_TRY(ensure_state(c, W));
+    {  // the first round's arenas, so that no sweep waits for an allocation
+        MultiArgs sized = a;
+        if (const int64_t big = ovf_arena(arena0)) GS_TRY(multi_scratch(c, sized, ovf_grid(big), big));
+        GS_TRY(multi_scratch(c, sized, main_grid(rows, arena0), arena0));
+    }
+    // the slabs (row r = chain r)
+    DevBuf<int32_t> b_cnt[2], b_pos[2];
+    DevBuf<int64_t> b_agg[3];  // rows, then the chains' skip words
+    DevBuf<double> b_pwms, b_u;
+    DevBuf<unsigned long long> b_err;
+    DevBuf<uint64_t> b_seeds;
+    DevBuf<SpecCtl> b_ctl;
+    DevBuf<int32_t> b_park, b_chains, b_ovf, b_novf, cpart;
+    SharedStarts starts;
+    BatchStarts bs;
+    DevBuf<int32_t> s_err;  // batched starts: the chains' (code, index) words
+    DevBuf<unsigned long long> s_erri;
+    for (auto &q : b_cnt) GS_TRY(q.alloc(c, rows));
+    for (auto &q : b_pos) GS_TRY(q.alloc(c, rows * cap));
+    for (auto &q : b_agg) GS_TRY(q.alloc(c, agg_elems));
+    GS_TRY(b_pwms.alloc(c, rows));
+    GS_TRY(b_err.alloc(c, R));
+    GS_TRY(b_seeds.alloc(c, R));
+    GS_TRY(b_park.alloc(c, R));
+    GS_TRY(b_chains.alloc(c, R));
+    if (ovf_elems > 0) GS_TRY(b_ovf.alloc(c, ovf_elems));
+    if (novf_elems > 0) GS_TRY(b_novf.alloc(c, novf_elems));
+    if (u_elems > 0) {
+        GS_TRY(b_u.alloc(c, u_elems));
+        HIP_TRY(c, hipMemcpyAsync(b_u, u, (size_t)u_elems * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b_park, 0xff, (size_t)R * 4, c->stream));
+    RunMultiBatchArgs ba{};
+    ba.cells = cells;
+    ba.n_all = R;
+    ba.seeds = b_seeds;
+    ba.err = b_err;
+    ba.park = b_park;
+    ba.u_stride = (int64_t)T * n;
+    a.u = nullptr;
+    a.targets = nullptr;
+    a.n_targets = 0;
+    std::vector<unsigned long long> herr((size_t)R, ~0ull);
+    std::vector<int32_t> hpark((size_t)R, -1), hnovf((size_t)novf_elems, 0);
+    std::vector<char> given_up((size_t)R, 0);
+    int32_t info[4] = {0, 0, 0, (int32_t)arena0};
+    // One round: the sweeps t0 .. T - 1 of `chains` (empty: all of them, from the starts)
+    // with `arena` as the first arena.
+    struct Round {
+        std::vector<int32_t> chains;
+        int32_t t0;
+        int64_t arena;
+    };
+    StageEvents<3> ev(c);
+    auto enqueue_round = [&](const Round &rd, bool first) -> int {
+        const int32_t nc = first ? R : (int32_t)rd.chains.size();
+        const int64_t pairs = (int64_t)nc * n, big = ovf_arena(rd.arena);
+        const int64_t grid = main_grid(pairs, rd.arena), ogrid = big ? ovf_grid(big) : 0;
+        // both launches carve the same scratch: the stream runs them one after the other
+        MultiArgs am = a, ao = a;
+        const bool big_first = big && ogrid * slot_bytes(big) > grid * slot_bytes(rd.arena);
+        if (big && big_first) GS_TRY(multi_scratch(c, ao, ogrid, big));
+        GS_TRY(multi_scratch(c, am, grid, rd.arena));
+        if (big && !big_first) GS_TRY(multi_scratch(c, ao, ogrid, big));
+        ba.n_chains = nc;
+        ba.chains = first ? nullptr : b_chains.p;
+        ba.n_pairs = pairs;
+        for (auto &q : b_agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
+        if (novf_elems > 0)
+            HIP_TRY(c, hipMemsetAsync(b_novf, 0, (size_t)novf_elems * 4, c->stream));
+        if (!first) {
+            // the parked chains forget their sweep t0, its error word included
+            HIP_TRY(c, hipMemcpyAsync(b_chains, rd.chains.data(), (size_t)nc * 4,
+                                      hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b_err, herr.data(), (size_t)R * 8, hipMemcpyHostToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b_park, hpark.data(), (size_t)R * 4, hipMemcpyHostToDevice,
+                                      c->stream));
+        }
+        if (T > rd.t0) {
+            am.cnt_in = b_cnt[rd.t0 & 1];
+            am.pos_in = b_pos[rd.t0 & 1];
+            ba.agg_out = b_agg[0];
+            HIP_TRY(c, gs_run_multi_batch_agg_launch(am, ba, agg_blocks(c, n, nc), c->stream));
+        }
+        if (first) HIP_TRY(c, ev.mark());
+        for (int32_t t = rd.t0; t < T; ++t) {
+            const int k = t - rd.t0, cur = k % 3, nxt = (k + 1) % 3, aft = (k + 2) % 3;
+            for (MultiArgs *m : {&am, &ao}) {
+                m->cnt_in = b_cnt[t & 1];
+                m->pos_in = b_pos[t & 1];
+                m->cnt_out = b_cnt[(t + 1) & 1];
+                m->pos_out = b_pos[(t + 1) & 1];
+                m->pwms_out = t == T - 1 ? b_pwms.p : nullptr;
+                m->stream = stream_sweep((uint64_t)(first_sweep + t));
+            }
+            ba.sweep = t;
+            ba.agg_in = b_agg[cur];
+            ba.agg_out = b_agg[nxt];
+            ba.u = b_u ? b_u + (int64_t)t * n : nullptr;
+            // buffer nxt is zero from the round's start (k < 2) or from sweep t - 1
+            RunMultiBatchArgs bm = ba;
+            bm.agg_clear = k >= 1 ? b_agg[aft].p : nullptr;
+            bm.pairs = bm.pairs_count = nullptr;
+            bm.ovf_list = big ? b_ovf.p : nullptr;
+            bm.ovf_count = big ? b_novf + t : nullptr;
+            HIP_TRY(c, gs_run_multi_batch_sweep_launch(am, bm, (int)grid, (size_t)lds, c->stream));
+            if (big) {
+                // unconditionally: an almost empty launch when the sweep listed no pair
+                RunMultiBatchArgs bo = ba;
+                bo.agg_clear = nullptr;
+                bo.pairs = b_ovf;
+                bo.pairs_count = b_novf + t;
+                bo.ovf_list = bo.ovf_count = nullptr;
+                HIP_TRY(c, gs_run_multi_batch_sweep_launch(ao, bo, (int)ogrid, (size_t)lds,
+                                                           c->stream));
+            }
+        }
+        return GS_OK;
+    };
+    int rc = [&]() -> int {
+        // ---- stage 1: every chain's lists and their aggregates ----
+        HIP_TRY(c, ev.mark());
+        if (mode < 0) {
+            HIP_TRY(c, hipMemcpyAsync(b_cnt[0], cnt_inout, (size_t)rows * 4, hipMemcpyHostToDevice,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(b_pos[0], pos_inout, (size_t)(rows * cap) * 4,
+                                      hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemsetAsync(b_err, 0xff, (size_t)R * 8, c->stream));
+        } else {
+            const bool batched = batched_starts(c);
+            if (batched) {
+                // (the next lists' slab and the PWMS slab are free until the sweeps: the
+                // starts and their scores go there)
+                GS_TRY(bs.prepare(c, W, pc, seeds, R, mode));
+                GS_TRY(s_err.alloc(c, R));
+                GS_TRY(s_erri.alloc(c, R));
+                GS_TRY(bs.enqueue(c, b_pwms, b_cnt[1], s_err, s_erri));
+                HIP_TRY(c, gs_starts_batch_lists_launch(b_cnt[1], rows, cap, b_cnt[0], b_pos[0], R,
+                                                        s_err, s_erri, b_err, nullptr, c->stream));
+            } else if (mode == 0)
+                GS_TRY(cpart.alloc(c, std::max<int64_t>(cpart_bytes, 4) / 4));
+            else
+                GS_TRY(starts.draw(c, W, seeds, R));
+            if (!batched) GS_TRY(b_ctl.alloc(c, R));
+            for (int32_t r = 0; !batched && r < R; ++r) {
+                GS_TRY(chain_starts(c, mode, W, pc, seeds[r], starts.row(c, r), cpart));
+                HIP_TRY(c, gs_multi_batch_lists_launch(c->d_pos[1], (int32_t)n, cap, b_cnt[0] + r * n,
+                                                       b_pos[0] + r * n * cap, c->d_err_code,
+                                                       c->d_err_index, b_err + r, b_ctl + r,
+                                                       c->stream));
+            }
+            GS_TRY(clear_ctx_error_words(c));
+        }
+        // ---- stage 2: the sweeps, then the parked chains again with larger arenas ----
+        std::vector<Round> todo;
+        todo.push_back(Round{{}, 0, arena0});
+        for (bool first = true; !todo.empty(); first = false) {
+            const Round rd = std::move(todo.back());
+            todo.pop_back();
+            GS_TRY(enqueue_round(rd, first));
+            if (M < 3 || T == 0) {  // no pair can overflow: nothing to look at
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                break;
+            }
+            HIP_TRY(c, hipMemcpyAsync(hpark.data(), b_park, (size_t)R * 4, hipMemcpyDeviceToHost,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(hnovf.data(), b_novf, (size_t)T * 4, hipMemcpyDeviceToHost,
+                                      c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            for (int32_t v : hnovf) info[0] += v;
+            // the chains this round parked, by sweep: each group is a round of its own
+            const int64_t big = ovf_arena(rd.arena), next = (big ? big : rd.arena) * 16;
+            std::vector<std::pair<int32_t, int32_t>> parked;  // (sweep, chain)
+            for (int32_t i = 0; i < (first ? R : (int32_t)rd.chains.size()); ++i) {
+                const int32_t r = first ? i : rd.chains[(size_t)i];
+                if (hpark[(size_t)r] >= 0) parked.emplace_back(hpark[(size_t)r], r);
+            }
+            std::sort(parked.begin(), parked.end());
+            info[1] += (int32_t)parked.size();
+            for (const auto &p : parked) {
+                hpark[(size_t)p.second] = -1;
+                herr[(size_t)p.second] = ~0ull;
+                if (next > arena_max) {
+                    given_up[(size_t)p.second] = 1;
+                    continue;
+                }
+                if (todo.empty() || todo.back().t0 != p.first || todo.back().arena != next) {
+                    todo.push_back(Round{{}, p.first, next});
+                    ++info[2];
+                }
+                todo.back().chains.push_back(p.second);
+            }
+        }
+        HIP_TRY(c, ev.mark());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    // uploaded lists never touched the single-chain buffers: only the snapshot goes
+    if (mode >= 0)
+        scratch_used(c);
+    else
+        c->have_state = false;
+    GS_TRY(ev.finish(rc, c->run_multi_batch_ms));
+    for (int i = 0; i < 4; ++i) c->run_multi_batch_info[i] = info[i];
+    // ---- stage 3: one download ----
+    if (T > 0 || mode >= 0) {
+        HIP_TRY(c, hipMemcpyAsync(cnt_inout, b_cnt[T & 1], (size_t)rows * 4, hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(pos_inout, b_pos[T & 1], (size_t)(rows * cap) * 4,
+                                  hipMemcpyDeviceToHost, c->stream));
+    }
+    if (T > 0)
+        HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int32_t r = 0; r < R; ++r)
+        if (given_up[(size_t)r])
+            herr[(size_t)r] = ((unsigned long long)c->global_offset << 4) |
+                              (unsigned long long)kMultiErrUnsupported;
+    return report_chain_errors(c, herr, status_out,
+                               "a sequence has more than 2^28 motif combinations (.fs:727-742)");
 }
 
 // R independent getPWMOfRandomStarts runs (.fs:589-611), DESIGN.md §9.15: the launches of

@@ -53,6 +53,7 @@ struct gs_tuning {
     int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
     int32_t run_batch_clear = 1;  // chain batch: the next aggregate rows zeroed by a memset before each sweep (0) or a third row cleared in-kernel (1: 1 - 3 % faster at 200 and 2 000 sequences)
     int32_t run_batch_blocks = 32;  // chain batch: cap on the one-wavefront workgroups per CU of its sweep launches (8 / 16 / 32, i.e. what fits: 18.1 / 12.6 / 11.3 ms for 64 chains x 200 sweeps x 200 sequences)
+    int32_t run_multi_arena_max = 1 << 28;  // list chain batch (gs_motif_run_multi_batch): the categories a target's levels 1 .. M - 1 may take (kArenaMax) before its chain is given up with GS_E_UNSUPPORTED; tests lower it to reach that branch with small arenas.  The one field a chain's status can depend on
     int32_t batch_starts = -1;  // batch drivers: the chains' starts chain after chain on the single-chain state (0), all chains in the launches of gs_random_starts_batch (1), or -1: the latter while a chain has fewer targets than a launch has workgroups (8 a CU), the size range where it measured faster; the results do not depend on it
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
     int32_t ftab_mode = 0;  // four-symbol sweep's workgroup tables: 0 built by every workgroup, 1 by a table kernel before the sweep, 2 handed over by the previous sweep's last workgroup (one GPU; else 1); 1 and 2 need the -DGS_FTAB build
@@ -184,6 +185,37 @@ hipError_t gs_run_batch_agg_launch(const MultiArgs &a, const RunBatchArgs &b, in
 hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, int grid, size_t lds,
                                      hipStream_t s);
 hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds);
+// What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
+// of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
+// names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
+// one, pwms_out: null unless the chains' last sweep; rows of n_local targets, chain r on row
+// r) and the arena of the launch.  The aggregate buffers are RunBatchArgs': [n_all][cells]
+// rows, then one skip word a chain.  A launch runs over the pairs (c, n) of its `chains`, or
+// over the device list `pairs` of such pairs that an earlier launch of the sweep appended.
+struct RunMultiBatchArgs {
+    int32_t n_chains, cells;     // chains of this launch (entries of `chains`), A*W + A
+    int32_t n_all;               // R: rows of the aggregate buffers and words of err / park
+    int32_t sweep;               // t, what a parking pair records
+    const int32_t *chains;       // [n_chains]: the chain of every launch index, or null: itself
+    const uint64_t *seeds;       // [R]
+    unsigned long long *err;     // [R]: packed (global index << 4) | status, atomicMin
+    int32_t *park;               // [R]: -1, or the sweep in which a pair overflowed the last arena
+    const int64_t *agg_in;       // the snapshot's buffer
+    int64_t *agg_out;            // the next snapshot's, zero at launch, filled by this sweep
+    int64_t *agg_clear;          // a third buffer to zero for the sweep after, or null
+    const double *u;             // explicit uniforms of this sweep: u[r * u_stride + n], or null
+    int64_t u_stride;
+    int64_t n_pairs;             // n_chains * n_local (pairs null)
+    const int32_t *pairs;        // device list of linear (c * n_local + n) indices, or null: all
+    const int32_t *pairs_count;  // its length, read from device memory
+    int32_t *ovf_list, *ovf_count;   // where an overflowing pair goes; null: it parks its chain
+};
+hipError_t gs_run_multi_batch_agg_launch(const MultiArgs &a, const RunMultiBatchArgs &b,
+                                         int blocks_per_chain, hipStream_t s);
+hipError_t gs_run_multi_batch_sweep_launch(const MultiArgs &a, const RunMultiBatchArgs &b, int grid,
+                                           size_t lds, hipStream_t s);
+hipError_t gs_run_multi_batch_occupancy(int *blocks_per_cu, size_t lds);
+hipError_t gs_run_multi_batch_static_lds(size_t *bytes);
 // What gs_random_starts_batch adds to StartsArgs / PartialArgs (a second by-value kernel
 // argument, gs_starts.hip): the chains of one launch side by side, chain
 // r on row r of the score / position slabs and error words that the StartsArgs names.
@@ -325,6 +357,8 @@ struct gs_ctx {
     double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
     double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
     double starts_batch_ms[2] = {0.0, 0.0};  // the last gs_random_starts_batch: counts / aggregates, scans
+    double run_multi_batch_ms[2] = {0.0, 0.0};  // the last list chain batch (gs_motif_run_multi_batch): starts, sweeps
+    int32_t run_multi_batch_info[4] = {0, 0, 0, 0};  // ... pairs rescored by overflow launches, chains parked, resume rounds, first arena
     int32_t multi_batch_info[4] = {0, 0, 0, 0};  // ... sweep arena rounds, greedy restart rounds, chains restarted, slots
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     // hipGraph replay of sweep chains: one graph = a uniforms kernel (the counter-RNG
@@ -519,5 +553,9 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
               double *pwms_out, int32_t *status_out);
 int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
                  double *score_out, int32_t *pos_out, int32_t *status_out);
+int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
+                    const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
+                    const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
+                    int32_t *status_out);
 
 }  // namespace gs_host

@@ -546,6 +546,36 @@ __device__ int greedy_pick(const MultiArgs &a, const Slot &sl, int K, GPick &out
     return 0;
 }
 
+// A workgroup's share of the aggregates of one list snapshot (cnt_in[n], pos_in[n * cap_in +
+// i]): the targets first, first + step, ... summed in LDS (acc: A*W + A cells, C then T),
+// then the cells that are not zero added to `out`.  Every thread of the workgroup.
+__device__ __forceinline__ void agg_lists(const MultiArgs &a, const int32_t *cnt_in,
+                                          const int32_t *pos_in, int first, int step,
+                                          unsigned long long *acc, int64_t *out) {
+    const int A = a.A, W = a.W, cells = A * W + A;
+    for (int x = threadIdx.x; x < cells; x += blockDim.x) acc[x] = 0ull;
+    __syncthreads();
+    for (int n = first; n < a.n_local; n += step) {
+        const uint8_t *s = a.seq + a.doff[n];
+        const int cnt = cnt_in[n];
+        for (int i = 0; i < cnt; ++i) {
+            const int p = pos_in[(int64_t)n * a.cap_in + i];
+            for (int x = 0; x < A; ++x)
+                atomicAdd(&acc[A * W + x], (unsigned long long)a.comp[(int64_t)n * (a.E + 1) + x]);
+            for (int j = 0; j < W; ++j) {
+                const int e = s[p + j];
+                if (e < A) {
+                    atomicAdd(&acc[e * W + j], 1ull);
+                    atomicAdd(&acc[A * W + e], ~0ull);  // -1
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < cells; x += blockDim.x)
+        if (acc[x]) atomicAdd((unsigned long long *)&out[x], acc[x]);
+}
+
 }  // namespace
 
 // Aggregates of a list snapshot: C[a][j] over every listed segment, T[a] = Σ over
@@ -1323,4 +1353,171 @@ hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, 
 hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, gs_run_batch_sweep_kernel, 64,
                                                         lds);
+}
+
+// ---- R chains of synchronous sweeps with Positions lists (gs_motif_run_multi_batch,
+// DESIGN.md §9.19) ----
+// gs_run_batch_sweep_kernel's scheme for any motifAmount: the chains' lists are
+// double-buffered slabs, the aggregate rows rotate over three buffers with one skip word a
+// chain, and the kernel boundary is the only synchronisation.  Levels 1..M-1 go into the
+// workgroup's arena slot as in gs_multi_batch_sweep_kernel.  A pair whose levels overflow
+// the arena writes nothing: it goes onto the sweep's device list, from which a second launch
+// with larger arenas takes exactly those pairs (list and count read from device memory); a
+// pair that overflows there too parks its chain (b.park, and the skip word), whose snapshot of
+// this sweep then stays intact for the host to resume from.
+
+// The aggregates of every chain's lists into row r of the zeroed b.agg_out
+// (gs_multi_batch_agg_kernel's sums, gs_run_batch_agg_kernel's skip word for a chain that
+// raised in its starts).
+extern "C" __global__ void __launch_bounds__(256)
+gs_run_multi_batch_agg_kernel(MultiArgs a, RunMultiBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    unsigned long long *acc = (unsigned long long *)lds;
+    const int cells = b.cells;
+    const int bpc = gridDim.x / b.n_chains;
+    const int c = blockIdx.x / bpc, blk = blockIdx.x - c * bpc;
+    const int r = b.chains ? b.chains[c] : c;
+    if (b.err[r] != ~0ull) {
+        if (blk == 0 && threadIdx.x == 0) b.agg_out[(int64_t)b.n_all * cells + r] = 1;
+        return;
+    }
+    agg_lists(a, a.cnt_in + (int64_t)r * a.n_local, a.pos_in + (int64_t)r * a.n_local * a.cap_in,
+              blk * blockDim.x + threadIdx.x, bpc * blockDim.x, acc,
+              b.agg_out + (int64_t)r * cells);
+}
+
+// One sweep (.fs:935-970) of every chain, one wavefront a (chain, target) pair: stage,
+// prepare_target with the chain's list, levels 1..M-1, roulette, the pick into the chain's
+// next lists (entries past cnt: -1); then the picked list's segments into the chain's row
+// of the next snapshot's aggregates (a list of p positions adds p * comp - sum of its
+// segments to T), 64-bit adds whose order does not matter.  A chain that raises keeps the
+// lowest (index, status) of the sweep in its word of b.err and sets its skip word of
+// b.agg_out, which the later sweeps hand on.
+extern "C" __global__ void __launch_bounds__(64)
+gs_run_multi_batch_sweep_kernel(MultiArgs a, RunMultiBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double *tab = (double *)(lds + a.o_tab);
+    double *pcv = (double *)(lds + a.o_pcv);
+    uint8_t *sseq = lds + a.o_seq;
+    __shared__ int flag;
+    __shared__ int32_t pick_cnt;
+    __shared__ int32_t pick_pos[kMultiMaxAmount];
+    __shared__ double pick_pw;
+    const int lane = threadIdx.x;
+    const Slot sl = slot_of(a, blockIdx.x, lds);
+    const int A = a.A, W = a.W, AW = A * W, cells = b.cells, cap = a.cap_out;
+    const int64_t rows = (int64_t)b.n_all * cells;
+    const int64_t n_pairs = b.pairs ? (int64_t)*b.pairs_count : b.n_pairs;
+    for (int64_t i = blockIdx.x; i < n_pairs; i += gridDim.x) {
+        const int64_t pair = b.pairs ? (int64_t)b.pairs[i] : i;
+        const int c = (int)(pair / a.n_local);
+        const int n = (int)(pair - (int64_t)c * a.n_local);
+        const int r = b.chains ? b.chains[c] : c;
+        if (!b.pairs) {  // (a listed pair's chain was running when this sweep listed it)
+            if (n == 0 && b.agg_clear) {  // the row the sweep after this one fills
+                for (int x = lane; x < cells; x += 64) b.agg_clear[(int64_t)r * cells + x] = 0;
+                if (lane == 0) b.agg_clear[rows + r] = 0;
+            }
+            if (b.agg_in[rows + r]) {  // raised or parked: in its starts or an earlier sweep
+                if (n == 0 && lane == 0) b.agg_out[rows + r] = 1;
+                continue;
+            }
+        }
+        const int64_t *C = b.agg_in + (int64_t)r * cells, *T = C + AW;
+        const int64_t row = (int64_t)r * a.n_local + n;
+        const int L = a.len[n];
+        const int K = L - W + 1;
+        const int64_t gidx = a.global_offset + n;
+        __syncthreads();
+        stage(a.seq + a.doff[n], L, sseq);
+        __syncthreads();
+        const int cnt = a.cnt_in[row];
+        const int32_t *pos = a.pos_in + row * a.cap_in;
+        const int st = prepare_target(a, n, L, sseq, cnt, pos, C, T, tab, pcv, sl, &flag);
+        RPick pk{-2, -1, -1, 0.0};
+        if (!st) {
+            // levels 1..M-1 (the last level's parents) in the arena; the last level virtual
+            int lo, hi;
+            const int total = build_levels(a, sl, K, a.M - 1, lane, &lo, &hi);
+            if (total < 0) {
+                if (lane == 0) {
+                    if (b.ovf_list) {
+                        b.ovf_list[atomicAdd(b.ovf_count, 1)] = (int32_t)pair;
+                    } else {
+                        b.park[r] = b.sweep;
+                        b.agg_out[rows + r] = 1;
+                    }
+                }
+                continue;
+            }
+            const double u = b.u ? b.u[(int64_t)r * b.u_stride + n]
+                                 : uniform(b.seeds[r], a.stream, (uint64_t)gidx);
+            pk = roulette(a, sl, K, total, a.M == 1 ? -1 : lo, a.M == 1 ? 0 : hi, u, lane);
+        }
+        if (st || pk.c == -2) {  // .fs:117 / list index past the end (.fs:752)
+            if (lane == 0) {
+                atomicMin(b.err + r, ((unsigned long long)gidx << 4) | (unsigned long long)(st ? st : 2));
+                b.agg_out[rows + r] = 1;
+            }
+            continue;
+        }
+        if (lane == 0) {
+            if (pk.c == -1)
+                emit(sl, pk.j, pk.q, pk.w, &pick_cnt, pick_pos, &pick_pw);
+            else
+                emit(sl, -1, pk.c < K ? -1 : pk.c - K, pk.c < K ? sl.G[pk.c] : sl.wgt[pk.c - K],
+                     &pick_cnt, pick_pos, &pick_pw);
+        }
+        __syncthreads();
+        const int pcnt = pick_cnt;
+        if (lane < cap) a.pos_out[row * cap + lane] = lane < pcnt ? pick_pos[lane] : -1;
+        if (lane == 0) {
+            a.cnt_out[row] = pcnt;
+            if (a.pwms_out) a.pwms_out[row] = pick_pw;
+        }
+        if (pcnt > 0) {
+            unsigned long long *Cn = (unsigned long long *)(b.agg_out + (int64_t)r * cells);
+            for (int x = lane; x < pcnt * W; x += 64) {
+                const int k = x / W, j = x - k * W;
+                const int e = sseq[pick_pos[k] + j];
+                if (e < A) atomicAdd(&Cn[e * W + j], 1ull);
+            }
+            if (lane < A) {
+                int64_t t = (int64_t)pcnt * a.comp[(int64_t)n * (a.E + 1) + lane];
+                for (int k = 0; k < pcnt; ++k)
+                    for (int j = 0; j < W; ++j) t -= sseq[pick_pos[k] + j] == lane;
+                if (t) atomicAdd(&Cn[AW + lane], (unsigned long long)t);
+            }
+        }
+    }
+}
+
+hipError_t gs_run_multi_batch_agg_launch(const MultiArgs &a, const RunMultiBatchArgs &b,
+                                         int blocks_per_chain, hipStream_t s) {
+    if (a.n_local <= 0 || b.n_chains <= 0) return hipSuccess;
+    const size_t lds = 8 * (size_t)b.cells;
+    hipLaunchKernelGGL(gs_run_multi_batch_agg_kernel, dim3(b.n_chains * blocks_per_chain), dim3(256),
+                       lds, s, a, b);
+    return hipGetLastError();
+}
+
+hipError_t gs_run_multi_batch_sweep_launch(const MultiArgs &a, const RunMultiBatchArgs &b, int grid,
+                                           size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(gs_run_multi_batch_sweep_kernel, dim3(grid), dim3(64), lds, s, a, b);
+    return hipGetLastError();
+}
+
+// The sweep kernel's static LDS (flag and the staged pick), which its launch needs beside
+// the dynamic carve.
+hipError_t gs_run_multi_batch_static_lds(size_t *bytes) {
+    hipFuncAttributes attr;
+    const hipError_t e =
+        hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(gs_run_multi_batch_sweep_kernel));
+    *bytes = e == hipSuccess ? attr.sharedSizeBytes : 0;
+    return e;
+}
+
+hipError_t gs_run_multi_batch_occupancy(int *blocks_per_cu, size_t lds) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu,
+                                                        gs_run_multi_batch_sweep_kernel, 64, lds);
 }

@@ -126,23 +126,34 @@ class MotifSampler:
     @staticmethod
     def runSweeps(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,
                   motifMem: Sequence[MotifIndex], sweeps: int, seed: int, first_sweep: int = 0,
-                  device: int = 0) -> list[MotifIndex]:
-        """`sweeps` chained sweeps on the device (uniforms from the counter RNG)."""
+                  device: int = 0, motifAmount: int = 1) -> list[MotifIndex]:
+        """`sweeps` chained sweeps on the device (uniforms from the counter RNG).  With
+        motifAmount >= 2, or a MotifIndex of more than one position, the chain runs on the
+        Positions-list path (Context.motif_run_multi)."""
         ctx = _bind(alphabet, sources, device)
-        pos, pwms = ctx.motif_run(motifLength, pseudoCount, cutOff, sweeps, seed,
-                                  _single_positions(motifMem), first_sweep)
-        return _motif_indices(pos, pwms)
+        if _is_single(motifAmount, motifMem):
+            pos, pwms = ctx.motif_run(motifLength, pseudoCount, cutOff, sweeps, seed,
+                                      _single_positions(motifMem), first_sweep)
+            return _motif_indices(pos, pwms)
+        cap, cnt, pos = _lists(motifAmount, motifMem)
+        co, po, pw = ctx.motif_run_multi(motifAmount, motifLength, pseudoCount, cutOff, sweeps,
+                                         seed, cnt, pos, first_sweep, cap)
+        return _motif_lists(co, po, pw)
 
     @staticmethod
     def runSweepsBatched(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,
                          sweeps: int, seeds, motifMems=None, init_mode: int = 0,
-                         first_sweep: int = 0, device: int = 0) -> list[list[MotifIndex]]:
+                         first_sweep: int = 0, device: int = 0,
+                         motifAmount: int = 1) -> list[list[MotifIndex]]:
         """One independent chain of `sweeps` chained sweeps per seed, all in one
         Context.motif_run_batch call: entry r is runSweeps(..., motifMems[r], sweeps,
         seeds[r], first_sweep).  Without motifMems chain r starts from getPWMOfRandomStarts
         of seeds[r] (init_mode as in doMotifSampling).  A chain that raised raises here.
         Faster than the loop up to about 2 000 sequences a chain, slower beyond
-        (DESIGN.md §9.13)."""
+        (DESIGN.md §9.13).  With motifAmount >= 2, or a MotifIndex of more than one
+        position, the chains run on the Positions-list path in one
+        Context.motif_run_multi_batch call: faster than the loop at every shape measured,
+        5 to 2 000 sequences a chain; not measured beyond."""
         seeds = [int(s) & (2**64 - 1) for s in seeds]
         pos = None
         if motifMems is not None:
@@ -151,15 +162,17 @@ class MotifSampler:
             if any(len(m) != len(sources) for m in motifMems):
                 raise _native.ArgumentError(_native.GS_E_ARG,
                                             "a motifMem and sources differ in length")
+        if not all(_is_single(motifAmount, m) for m in motifMems or [[]]):
+            return _run_lists_batched(motifAmount, motifLength, pseudoCount, cutOff, alphabet,
+                                      sources, sweeps, seeds, motifMems, init_mode, first_sweep,
+                                      device)
+        if motifMems is not None:
             pos = np.array([_single_positions(m) for m in motifMems],
                            np.int32).reshape(len(seeds), len(sources))
         ctx = _bind(alphabet, sources, device)
         pos, pwms, status = ctx.motif_run_batch(motifLength, pseudoCount, cutOff, sweeps, seeds,
                                                 pos, init_mode, first_sweep)
-        for r, st in enumerate(status):
-            if st != _native.GS_OK:
-                raise _native._ERRORS.get(int(st), _native.DeviceError)(
-                    int(st), f"chain {r} of the batch failed")
+        _raise_failed_chain(status)
         return [_motif_indices(pos[r], pwms[r]) for r in range(len(seeds))]
 
     @staticmethod
@@ -366,6 +379,34 @@ def _sampling(ctx, motifAmount, motifLength, pseudoCount, cutOff, seed, init_mod
     co, po, pw, _ = ctx.motif_sampling_multi(motifAmount, motifLength, pseudoCount, cutOff, seed,
                                              init_mode, UNBOUNDED)
     return _motif_lists(co, po, pw)
+
+
+def _raise_failed_chain(status) -> None:
+    for r, st in enumerate(status):
+        if st != _native.GS_OK:
+            raise _native._ERRORS.get(int(st), _native.DeviceError)(
+                int(st), f"chain {r} of the batch failed")
+
+
+def _run_lists_batched(motifAmount, motifLength, pseudoCount, cutOff, alphabet, sources, sweeps,
+                       seeds, motifMems, init_mode, first_sweep, device):
+    """runSweepsBatched on the Positions-list path: one Context.motif_run_multi_batch call,
+    the chains' lists at one capacity (the longest list's, at least motifAmount)."""
+    cnt = pos = None
+    cap = motifAmount
+    if motifMems is not None:
+        cap = max([motifAmount] + [_lists(motifAmount, m)[0] for m in motifMems])
+        cnt = np.zeros((len(seeds), len(sources)), np.int32)
+        pos = np.full((len(seeds), len(sources), cap), -1, np.int32)
+        for r, mem in enumerate(motifMems):
+            c1, cnt[r], p1 = _lists(motifAmount, mem)
+            pos[r, :, :c1] = p1
+    ctx = _bind(alphabet, sources, device)
+    cnt, pos, pwms, status = ctx.motif_run_multi_batch(motifAmount, motifLength, pseudoCount,
+                                                       cutOff, sweeps, seeds, cnt, pos, init_mode,
+                                                       first_sweep, cap)
+    _raise_failed_chain(status)
+    return [_motif_lists(cnt[r], pos[r], pwms[r]) for r in range(len(seeds))]
 
 
 def _motif_indices(pos, pwms) -> list[MotifIndex]:

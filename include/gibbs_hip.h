@@ -241,6 +241,51 @@ int gs_motif_run_batch(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_o
 /* Device times of the last gs_motif_run_batch, ms: starts (and first aggregates), sweeps. */
 int gs_run_batch_last_ms(const gs_ctx *ctx, double out[2]);
 
+/* R independent chains of n_sweeps synchronous sweeps each with Positions lists (any
+ * motifAmount) in one call: chain r is exactly n_sweeps calls of gs_motif_sweep_multi(ctx,
+ * motif_amount, W, pc, cut_off, cap, ...), each fed the previous output.  init_mode -1:
+ * chain r starts from the caller's lists (cnt_inout[r], pos_inout[r]; lists longer than
+ * motif_amount are allowed up to cap); 0 / 1: from the positions of gs_random_starts(ctx, W,
+ * pc, seeds[r], init_mode, ...) as one-position lists, the lists are output only.  The
+ * uniform of sequence n in sweep t is gs_uniform(seeds[r], gs_stream_sweep(first_sweep + t),
+ * global n), or u[r][t][n] with u non-null; a second call with init_mode -1 and first_sweep
+ * + n_sweeps continues the chains.  One sweep of all chains is one launch over the (chain,
+ * target) pairs (motif_amount >= 3: and a second, small one that rescores the pairs whose
+ * combinations overflowed the first arena, taken from a device list), the launches back
+ * to back with one synchronisation at the end; only a chain with a target beyond the second
+ * arena (16 x max(2048, 4 (L - W + 1)) combinations of up to motif_amount - 1 windows) is
+ * run again afterwards from the sweep it stopped in, with larger arenas.  PWMS are those of
+ * the last sweep, list entries past cnt are -1; n_sweeps == 0 leaves the lists as they are
+ * (init_mode 0 / 1: the starts) and does not write pwms_out; n_chains == 0 does nothing.
+ * Returns the status of the lowest-index failing chain (gs_error_index: its sequence), GS_OK
+ * if none: a chain that raises (.fs:752, .fs:117) keeps its status in status_out[r], its
+ * later sweeps are skipped and its rows unspecified; the other chains finish.  A chain with
+ * more than 2^28 combinations in a target gets GS_E_UNSUPPORTED in its own status_out entry.
+ * GS_E_ARG before any launch: motif_amount or cap outside 1 .. 16, cap < motif_amount, a bad
+ * W or init_mode, n_sweeps < 0, first_sweep < 0, a null seeds or output, a cnt outside
+ * [0, cap] or a position outside its sequence (init_mode -1).  GS_E_UNSUPPORTED: sharded
+ * sequences or a communicator, a fixed PCV or PPM, chain slabs beyond 4 GiB, sequences too
+ * long for the list path's LDS carve.  The context holds no snapshot afterwards and its
+ * error words are clear. */
+int gs_motif_run_multi_batch(gs_ctx *ctx, int32_t motif_amount, int32_t W, double pseudo_count,
+                             double cut_off, int32_t n_sweeps, const uint64_t *seeds,
+                             int32_t n_chains, int64_t first_sweep, int32_t init_mode, int32_t cap,
+                             const double *u,      /* nullable: [n_chains][n_sweeps][n_local] */
+                             int32_t *cnt_inout,   /* [n_chains][n_local]                      */
+                             int32_t *pos_inout,   /* [n_chains][n_local][cap], F# list order  */
+                             double *pwms_out,     /* [n_chains][n_local]                      */
+                             int32_t *status_out   /* [n_chains], nullable                     */);
+/* The same for one chain from the caller's lists (init_mode -1). */
+int gs_motif_run_multi(gs_ctx *ctx, int32_t motif_amount, int32_t W, double pseudo_count,
+                       double cut_off, int32_t n_sweeps, uint64_t seed, int64_t first_sweep,
+                       int32_t cap, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out);
+/* Device times of the last gs_motif_run_multi_batch, ms: starts (and first aggregates),
+ * sweeps (resumed chains included). */
+int gs_run_multi_batch_last_ms(const gs_ctx *ctx, double out[2]);
+/* Its overflow handling: out[0] pairs rescored by overflow launches, out[1] chains parked,
+ * out[2] resume rounds, out[3] the first arena's capacity. */
+int gs_run_multi_batch_last_info(const gs_ctx *ctx, int32_t out[4]);
+
 /* Global aggregates of a snapshot (parity hook): C[a*W+j] = number of motif
  * segments with alphabet[a] at column j (the PFM of .fs:955-962 over ALL
  * sequences), T[a] = sum over sequences with a motif of the alphabet[a] count
@@ -435,6 +480,9 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots, multi_batch_fill,
  * run_batch_clear (gs_motif_run_batch: 0 a memset of the next aggregate rows before each
  * sweep, 1 a third row cleared in-kernel), run_batch_blocks (its workgroups per CU),
+ * run_multi_arena_max (gs_motif_run_multi_batch: the combinations of up to motif_amount - 1
+ * windows a target may have before its chain gets GS_E_UNSUPPORTED, 2048 .. 2^28, default
+ * 2^28; for tests of that status, and the one field a chain's status depends on),
  * batch_starts (the four batched drivers' starts: 0 chain after chain on the single-chain
  * state, 1 all chains in the launches of gs_random_starts_batch, -1 automatic: 1 while the
  * sequences are fewer than 8 per compute unit, the size range where it measured faster),
