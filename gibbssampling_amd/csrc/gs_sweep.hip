@@ -416,6 +416,7 @@ __device__ void ek4_build_tables(unsigned char *lds, const int64_t *rep, int str
     __syncthreads();
     // sum T: exact (integers below 2^53, any order)
     const double q = (double)T[0] + (double)T[1] + (double)T[2] + (double)T[3];
+    if (tid == 0) T[4] = (int64_t)q;  // (the sweep's sum T; read by no thread of this pass)
     for (int c = tid; c < AW + nT + 1; c += nthr) {
         if (c < AW) {
             const int32_t cc = cg[c];
@@ -871,6 +872,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         if (hasT && tt <= nT)
             lTab[tt] = tt < nT ? log2((double)(v + (tt - acell * (W + 1))) + a.pc)
                                : log2((q + (double)W) + a.apc);
+        if (hasT && tt == nT) T[A] = (int64_t)q;  // sum T, for every wavefront after the barrier
         TLP(tl_w, 4);
     }
     if (EK == 4 && useF) {
@@ -967,7 +969,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     TLP(tl_w, 6);
 
     // Σ_a T[a] (exact: integers far below 2^53)
-    const int64_t sumT = (int64_t)wave_sum_f64(lane < A ? (double)T[lane] : 0.0);
+    // (EK = 4: the prologue's quad sum, kept beside the totals)
+    const int64_t sumT = EK == 4 ? T[A] : (int64_t)wave_sum_f64(lane < A ? (double)T[lane] : 0.0);
     // background error-bound coefficients: |log2 PCV| <= tG, each
     // binary32 entry carries kLog2AbsErr + tG 2^-24, the pair table and the tree sum
     // add <= levels * (W tG) 2^-24.  (The motif part's bound is per sequence, below.)
@@ -1415,8 +1418,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 // window's background weight is 2^(lg - r), one v_sub_f32 and one v_exp_f32;
                 // outside (-kBg32Range, kBg32Range) the sequence is flagged for the rescan
                 float sG32 = 0.0f;  // the lane's sum of 2^(lg - r)
-                auto take = [&](int kk, int rr, uint32_t so, float lgo) {
-                    const bool ok = rr < R && kk < K;
+                // the lane's windows that exist (as the pick's count): one compare a window
+                const int nvl = min(max(K - k_lo, 0), R);
+                auto take = [&](int rr, uint32_t so, float lgo) {
+                    const bool ok = rr < nvl;
                     const float d = lgo - rG;
                     const bool xo = !(fabsf(d) < kBg32Range);
                     sG32 = sG32 + (ok ? __builtin_amdgcn_exp2f(d) : 0.0f);
@@ -1435,12 +1440,12 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     uint32_t s0, s1, s2, s3;
                     float l0, l1, l2, l3;
                     window_logs_q<WM, 0, EK == 4>(q, ltab, s0, s1, l0, l1);
-                    take(k0, r, s0, l0);
-                    take(k0 + 1, r + 1, s1, l1);
+                    take(r, s0, l0);
+                    take(r + 1, s1, l1);
                     __builtin_amdgcn_sched_barrier(0);  // 12 table reads in flight at a time
                     window_logs_q<WM, 2, EK == 4>(q, ltab, s2, s3, l2, l3);
-                    take(k0 + 2, r + 2, s2, l2);
-                    take(k0 + 3, r + 3, s3, l3);
+                    take(r + 2, s2, l2);
+                    take(r + 3, s3, l3);
                 }
                 // the lane's sum back at its absolute scale: an exact power of two
                 sG = ldexp((double)sG32, (int)rG);
