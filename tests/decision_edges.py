@@ -415,7 +415,24 @@ SHAPES = {
     "dna15_526": (32, 526, 15, b"ACGT", "init", CUT, 16),
     "protein": (32, 160, 20, PROTEIN, "init", CUT, 17),     # H = 1: binary32 scores
     "pcv10": (64, 120, 10, b"ACGT", "init", CUT, 18),       # the fixed-PCV twin
+    # the wide width classes (WM = 64, 28, 20, 24, 48, 40; W = 61 and 41 with padding columns):
+    # the bands' W terms at their largest, background products below the binary32 range
+    "atgc5_w64": (32, 160, 64, b"ATGC-", "init", CUT, 31),  # the pair tables with fewer than 4 wavefronts
+    "dna_w61": (32, 160, 61, b"ACGT", "init", CUT, 32),
+    "dna_w28": (32, 120, 28, b"ACGT", "init", CUT, 33),     # the four-symbol kernel's unsplit table build
+    "dna_w20": (32, 120, 20, b"ACGT", "init", CUT, 36),
+    "dna_w24_300": (32, 300, 24, b"ACGT", "init", CUT, 37),
+    "protein_w64": (32, 200, 64, PROTEIN, "init", CUT, 34),
+    "protein_w41": (32, 200, 41, PROTEIN, "init", CUT, 35),
+    "pcv_w40": (32, 160, 40, b"ACGT", "init", CUT, 38),
 }
+# the cut-off probe windows each shape yields (cutoff_windows): at W = 61 and 64 the window
+# scores run from about -500 to +110 and no failing window scores above 0, so there is no
+# strongest failing one to put a positive cut-off next to
+CUTOFF_ALL = frozenset({"best", "weakest_passing", "strongest_failing", "no_motif_target", "global_max"})
+CUTOFF_KEYS = {name: CUTOFF_ALL for name in SHAPES}
+for _name in ("atgc5_w64", "dna_w61", "protein_w64"):
+    CUTOFF_KEYS[_name] = CUTOFF_ALL - {"strongest_failing"}
 _cache = {}
 
 

@@ -23,6 +23,14 @@ GEO = {
     "dna15_526": de.geometry_long(),
     "protein": de.geometry_groups(16),
     "pcv10": de.geometry_groups(16, quad=True),
+    "atgc5_w64": de.geometry_groups(16, quad=True),
+    "dna_w61": de.geometry_groups(16, quad=True),
+    "dna_w28": de.geometry_groups(16, quad=True),
+    "dna_w20": de.geometry_groups(16, quad=True),
+    "dna_w24_300": de.geometry_groups(32),
+    "protein_w64": de.geometry_groups(32),
+    "protein_w41": de.geometry_groups(32),
+    "pcv_w40": de.geometry_groups(16, quad=True),
 }
 
 
@@ -81,13 +89,18 @@ def test_restatement_on_edges_of_log_free_snapshots(name):
     assert ei.value.code == ol.GO_E_ROULETTE_OVERRUN and ei.value.index == n
 
 
-@pytest.mark.parametrize("name", ["atgc5", "dna12", "protein", "pcv10"])
+@pytest.mark.parametrize("name", sorted(de.SHAPES))
 def test_cutoff_probe_windows(name):
     """Every cut-off probe clears every other window of every target by d / 2 at least,
-    and the restatement at that cut-off picks what the oracle picks."""
+    and the restatement at that cut-off picks what the oracle picks.  Each shape yields
+    exactly the windows decision_edges.CUTOFF_KEYS names for it."""
     snap = de.snapshot(name)
     wins = de.cutoff_windows(snap.ts, snap.pos)
-    assert {"best", "weakest_passing", "strongest_failing", "global_max"} <= set(wins)
+    assert set(wins) == de.CUTOFF_KEYS[name]
+    if "strongest_failing" not in wins:  # no failing window scores above 0
+        for t in snap.ts:
+            f = t.l2[t.l2 <= de.CUT]
+            assert f.size == 0 or f.max() <= 0.0
     u = snap.random_u(2)
     for key, (n, k, l2) in wins.items():
         for d in de.D_CUTOFF:

@@ -33,23 +33,23 @@ RTOL = 1e-12
 # the cut-off probes)
 ROWS = {
     "general": dict(tuning={"dna_mode": 0}, kernel="gs_sweep_kernel", launch={"ek": 0, "gl": 16},
-                    geo=de.geometry_groups(16, quad=True), shapes=["atgc5"]),
+                    geo=de.geometry_groups(16, quad=True), shapes=["atgc5", "atgc5_w64", "dna_w61", "pcv_w40"]),
     "ek4_loop": dict(tuning={"dna_mode": 0, "sweep_one": 0, "bg_mode": 0}, kernel="gs_sweep_kernel",
                      launch={"ek": 4, "gl": 16, "one": 0}, geo=de.geometry_groups(16, quad=True),
-                     shapes=["dna12"]),
+                     shapes=["dna12", "dna_w28", "dna_w20"]),
     "ek4_one": dict(tuning={"dna_mode": 0, "sweep_one": 1, "bg_mode": 0}, kernel="gs_sweep_kernel",
                     launch={"ek": 4, "gl": 16, "one": 1}, geo=de.geometry_groups(16, quad=True),
-                    shapes=["dna12"]),
+                    shapes=["dna12", "dna_w28", "dna_w20"]),
     "ek4_gl32": dict(tuning={"dna_mode": 0, "sweep_one": 0}, kernel="gs_sweep_kernel",
                      launch={"ek": 4, "gl": 32, "one": 0}, geo=de.geometry_groups(32),
-                     shapes=["dna8_300"]),
+                     shapes=["dna8_300", "dna_w24_300"]),
     "protein": dict(tuning={}, kernel="gs_sweep_kernel", launch={"ek": 0, "gl": 32},
-                    geo=de.geometry_groups(32), shapes=["protein"]),
+                    geo=de.geometry_groups(32), shapes=["protein", "protein_w64", "protein_w41"]),
     # the binary64-for-every-window scan: one 64-lane group a target, the band is rounding only
     "general_exact": dict(tuning={"dna_mode": 0}, exact=True, kernel="gs_sweep_kernel", launch={"ek": 0},
-                          geo=de.geometry_groups(64), shapes=["atgc5"]),
+                          geo=de.geometry_groups(64), shapes=["atgc5", "atgc5_w64"]),
     "protein_exact": dict(tuning={}, exact=True, kernel="gs_sweep_kernel", launch={"ek": 0},
-                          geo=de.geometry_groups(64), shapes=["protein"]),
+                          geo=de.geometry_groups(64), shapes=["protein", "protein_w64"]),
     "long": dict(tuning={"dna_mode": 1, "long_mode": 1}, kernel="gs_sweep_long_kernel",
                  geo=de.geometry_long(), shapes=["dna15_526", "dna12_300"]),
     "live1": dict(tuning={"live_mode": 1, "live_G": 1}, kernel="gs_sweep_live_kernel",
@@ -70,7 +70,12 @@ BG_ROWS = {f"bg{g}": dict(tuning={"bg_mode": 1, "bg_G": g}, geo=de.geometry_pack
 RESCAN_FIRST = {"gs_sweep_kernel", "gs_sweep_long_kernel", "gs_sweep_live_kernel", "gs_sweep_dna_kernel"}
 
 CASES = [(r, s) for r, row in ROWS.items() for s in row["shapes"]]
-CUT_CASES = [(r, row["shapes"][0]) for r, row in ROWS.items()]
+# the wide shapes (W = 20 .. 64) take the cut-off probes in every row they are in
+WIDE = ("atgc5_w64", "dna_w61", "dna_w28", "dna_w20", "dna_w24_300", "protein_w64", "protein_w41", "pcv_w40")
+CUT_CASES = [(r, s) for r, row in ROWS.items() for i, s in enumerate(row["shapes"]) if i == 0 or s in WIDE]
+# the alphabet's wavefronts a workgroup (gs_common.h sweep_waves) where the LDS carve cannot
+# hold them: these shapes launch fewer (launch_sweep halves them until the workgroup fits)
+FEWER_WAVES = {"atgc5_w64": 4, "protein_w64": 12}
 
 
 @pytest.fixture(scope="module")
@@ -98,13 +103,12 @@ def load(ctxs, row, snap, bg_off=False):
     c = ctxs(row)
     c.set_tuning("bg_mode", 0 if bg_off else spec["tuning"].get("bg_mode", -1))
     c.set_sequences(snap.codes, snap.offsets, snap.alpha)
-    if snap.pcv is not None:
-        c.set_fixed_pcv(snap.pcv)
+    c.set_fixed_pcv(snap.pcv)  # (None clears the one a row's earlier shape set)
     c.set_scan_mode(exact=bool(spec.get("exact")))
     return c, spec
 
 
-def ran(c, spec, row):
+def ran(c, spec, row, shape=None):
     """The intended kernel and path ran."""
     if "kernel" not in spec:
         return
@@ -113,6 +117,8 @@ def ran(c, spec, row):
         launch = c.last_sweep_launch()
         for k, v in spec.get("launch", {}).items():
             assert launch[k] == v, (row, launch)
+        if shape in FEWER_WAVES:
+            assert 1 <= launch["waves"] < FEWER_WAVES[shape], (row, shape, launch)
 
 
 def same(g, o, what):
@@ -147,7 +153,7 @@ def test_roulette_edges_at_distance(ctxs, row, shape):
             assert np.array_equal(rpos, o[0]) and np.array_equal(rmg, np.asarray(o[2]))
             assert (rmg <= np.abs(u - edges)).all()
             g = c.motif_sweep(snap.W, de.PC, snap.cutoff, snap.pos, u)
-            ran(c, spec, row)
+            ran(c, spec, row, shape)
             same(g, o, f"{row} {shape} u = acc_c {sign} {d:g} (kinds {kind[:6]}...)")
     st = c.stats()
     assert st["rescan_recheck"] == 0 and st["desc_oob"] == 0, st
@@ -176,7 +182,7 @@ def test_log_free_edges(ctxs, row, shape):
         s0 = c.stats()
         g = c.motif_sweep(snap.W, de.PC, snap.cutoff, snap.pos, u)
         dl = delta(c, s0)
-        ran(c, spec, row)
+        ran(c, spec, row, shape)
         same(g, o, f"{row} {shape} log-free, u {key} the edge")
         if bg:
             assert dl["bg_path"] == snap.N, dl
@@ -206,13 +212,14 @@ def test_log_free_edges(ctxs, row, shape):
 def test_cutoff_edges(ctxs, row, shape):
     """The cut-off d above and below a window's log2 score (never on it: the device's
     log may differ in the last place), nothing else nearer than d / 2 (asserted): the
-    target's best window, its weakest passing and strongest failing one at cut-off 1, a
-    window of a target without a motif, and the snapshot's maximum -- just above it no
+    target's best window, its weakest passing and strongest failing one at cut-off 1 (where
+    the shape has one: decision_edges.CUTOFF_KEYS), a window of a target without a motif, and
+    the snapshot's maximum -- just above it no
     target has a motif category, just below one target has one."""
     snap = de.snapshot(shape)
     c, spec = load(ctxs, row, snap)
     wins = de.cutoff_windows(snap.ts, snap.pos)
-    assert set(wins) == {"best", "weakest_passing", "strongest_failing", "no_motif_target", "global_max"}
+    assert set(wins) == de.CUTOFF_KEYS[shape]
     u = snap.random_u(3)
     for key, (n, k, l2) in wins.items():
         for d in de.D_CUTOFF:
@@ -220,7 +227,7 @@ def test_cutoff_edges(ctxs, row, shape):
                 assert de.cutoff_clearance(snap.ts, cut) >= d / 2, (key, d)
                 o = snap.oracle(u, cutoff=cut)
                 g = c.motif_sweep(snap.W, de.PC, cut, snap.pos, u)
-                ran(c, spec, row)
+                ran(c, spec, row, shape)
                 same(g, o, f"{row} {shape} cut-off = l2[{n}][{k}] {cut - l2:+.1e} ({key})")
                 if key == "global_max" and cut > l2:
                     assert (g[0] == -1).all()
