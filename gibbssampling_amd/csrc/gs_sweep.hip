@@ -536,8 +536,9 @@ __device__ __attribute__((noinline)) ExactPick rescan_group_h1(KSweepArgs *ka_in
 // issued before the first is consumed).  EK = 0: E from the arguments.
 // ONE (EK = 4 only): no wavefront of the launch has more than G = 64 / GL slots (the
 // host's dispatch, gs_engine.cpp launch_sweep), so each group scores its one sequence in
-// straight-line code: its lanes load their own slot's descriptor, position and uniform
-// (no 64-slot batch in lane registers, no permutes out of it), nothing is prefetched,
+// straight-line code: its lanes load their own slot's descriptor, position and given
+// uniform (no 64-slot batch in lane registers, no permutes out of it; uniforms that are
+// not given are drawn once a workgroup, by one wavefront), nothing is prefetched,
 // and the group's first lane stores the result itself (no res[] round trip through LDS).
 // The per-sequence math is the loop's own body, run once.
 template <int WM, int H, int GL, int EK, bool ONE = false>
@@ -557,6 +558,13 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // background weights in binary32 relative to a per-sequence reference (gs_common.h
     // kBg32Range)
     constexpr bool kQuad = H == 2 && GL == 16;
+    // EK = 4, 16-lane groups: the lane that owns a motif column writes its four table
+    // cells itself
+    constexpr bool kColCells = EK == 4 && GL == 16;
+    // ONE: the uniforms drawn once a workgroup (not with the caller's, a.u_in)
+    constexpr bool kWgU = ONE;
+    // EK = 4: pcv[] holds the PCV's numerators, divided where a quotient is read
+    constexpr bool kPcvLate = EK == 4;
     // EK = 4 kernels run for W == WM only (gs_sweep_ek): the motif width is static too
     const int A = EK ? EK : a.A, E = EK ? EK : a.E, W = EK ? WM : a.W, AW = A * W, CS = E + 1,
               E2 = E * E;
@@ -593,6 +601,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     int64_t *aggT = (int64_t *)(wl + w_aggT);       // [A] background outside segments
     unsigned char *tab = wl + w_tab;                // [E][WS] exact (PWM, PCV): rescans
     SweepResult *res = (SweepResult *)(wl + w_res);  // [64] batch results
+    // ONE: the workgroup's uniforms, [<= 4 G] (the first wavefront's batch results' slot:
+    // the one-iteration path stores its results itself)
+    double *const wg_u = (double *)(lds + o_wave + w_res);
+    (void)wg_u;
     int32_t *misc = (int32_t *)(wl + w_misc);
     // this lane's group slice
     unsigned char *gsl = wl + w_group + gi * a.group_bytes;
@@ -806,10 +818,22 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         }
         if (rd) {
             b_pos = a.pos_in[nb];
-            b_u = a.u_in ? a.u_in[nb] : uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + nb));
+            if constexpr (kWgU) {
+                if (a.u_in) b_u = a.u_in[nb];
+            } else {
+                b_u = a.u_in ? a.u_in[nb] : uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + nb));
+            }
             if (b_len <= 16 * GL && li * 16 < b_len) pf = *(const uint4 *)(gseq + b_off + li * 16);
             if (li < CS) cpf = a.comp[(int64_t)nb * CS + li];
         }
+        // the counter RNG once a workgroup: lane i of one wavefront draws the uniform of
+        // the workgroup's sequence wn0 + i (at most 4 G <= 16 of them), for every group to
+        // read after the prologue's barrier.  The wavefront is one that takes no binary64
+        // log before that barrier (the third while the fourth has the count-minus-one
+        // cells, else the fourth), and it draws whether or not it has a sequence itself.
+        if constexpr (kWgU)
+            if (!a.u_in && wid == min(kSplitM ? 2 : 3, kWavesPerBlock - 1) && lane < wcnt)
+                wg_u[lane] = uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + wn0 + lane));
     } else {
         int dl = 0;
         int64_t dof = 0;
@@ -967,6 +991,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     TLINE(tl_w, 2);
     TLF(tl_w, 1);
     TLP(tl_w, 6);
+    if constexpr (kWgU)  // the group's uniform of the workgroup's draw
+        if (!a.u_in && gi < cnt) b_u = wg_u[n0 - wn0 + gi];
 
     // Σ_a T[a] (exact: integers far below 2^53)
     // (EK = 4: the prologue's quad sum, kept beside the totals)
@@ -1135,8 +1161,15 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // PCV (.fs:119); outside the alphabet the raw count (Q3).  The ...ByPCV
             // variants (.fs:828-853) take the caller's vector instead.
             const double sbg = (double)tot + a.apc;
-            const double pe = pcv_fixed ? pcv_fixed[li < E ? li : 0]
-                                          : (li < A ? ((double)bgc + a.pc) / sbg : (double)my_comp);
+            // kPcvLate (EK = 4: no caller's vector, every lane symbol in the alphabet): the
+            // quotient's numerator is kept in its place, pcv[] holds numerators, and
+            // every reader divides by sbg, formed from the same two operands (the rescan's:
+            // sbgx), so a motif-bearing target, whose log comes from lTab, divides for its
+            // PWMS only
+            const double pnum = (double)bgc + a.pc;
+            double pe = 0.0;
+            if constexpr (!kPcvLate)
+                pe = pcv_fixed ? pcv_fixed[li < E ? li : 0] : (li < A ? pnum / sbg : (double)my_comp);
             float lq;
             if constexpr (H == 2) {
                 double lq64 = 0.0;
@@ -1145,7 +1178,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     // - log2(sbg) (the rounding of PCV's division is < 2^-52 in the log)
                     if (certified && li < E)
                         lq64 = (p >= 0 && !pcv_fixed) ? lTab[li * (W + 1) + segc] - lTab[4 * (W + 1)]
-                                                        : log2_ool(pe);
+                                                        : log2_ool(kPcvLate ? pnum / sbg : pe);
                 } else {
                     lq64 = certified && li < E ? log2(pe) : 0.0;
                 }
@@ -1155,9 +1188,25 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 lq = certified ? flog2(pe) : 0.0f;
                 if (li < E) ((float *)lpcv)[li] = lq;
             }
-            if (li < E) pcv[li] = pe;
+            if (li < E) pcv[li] = kPcvLate ? pnum : pe;
             // a zero PCV of an alphabet symbol makes PWM entries +inf / NaN: binary64
-            const unsigned long long zero_pcv = seg_ballot<GL>(li < A && !(pe > 0.0), lane);
+            // (kPcvLate: taken from the numerator.  With pnum >= 2^-960 (+inf included) and
+            // 2^-60 <= sbg < 2^64 the quotient is at least 2^-1024, a nonzero subnormal, or
+            // +inf: pnum / sbg > 0 holds and no division is needed.  sbg = tot + A pc with
+            // 1 <= tot < 2^31 wherever the pick is kept, so the second condition fails only
+            // for a pseudo-count that is negative, huge or NaN.  Everything else (a zero
+            // numerator, pc = 0 with no background count of the symbol, an all-zero
+            // background included; a subnormal or negative one; NaN) divides here and
+            // tests the quotient itself, as before.)
+            bool pe_zero;
+            if constexpr (kPcvLate) {
+                pe_zero = false;
+                if (li < A && (!(pnum >= 0x1.0p-960) || !(sbg >= 0x1.0p-60 && sbg < 0x1.0p64)))
+                    pe_zero = !(pnum / sbg > 0.0);
+            } else {
+                pe_zero = !(pe > 0.0);
+            }
+            const unsigned long long zero_pcv = seg_ballot<GL>(li < A && pe_zero, lane);
             bool fast = keep && certified && zero_pcv == 0;
             const float tG = __int_as_float(seg_last_i32<GL>(
                 seg_scan_max_i32<GL>(__float_as_int(li < E && fabsf(lq) < INFINITY ? fabsf(lq) : 0.0f)),
@@ -1212,6 +1261,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 double csum = 0.0;
                 constexpr int NJ = (WM + GL - 1) / GL;  // columns per lane (EK path)
                 double mj[NJ];
+                double tj[kColCells ? NJ : 1][4];  // (kColCells) the lane's columns' four terms
+                (void)tj;
                 if constexpr (EK == 4) {
                     // the column maxima with every read of the lane issued at once
                     const double lq0 = lpcv[0], lq1 = lpcv[1], lq2 = lpcv[2], lq3 = lpcv[3];
@@ -1228,7 +1279,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                             const double t3 = (o == 3 ? lo : lppmG[3 * W + j]) - lq3;
                             const double m = fmax(fmax(fmax(fmax(-INFINITY, t0), t1), t2), t3);
                             mj[q] = m;
-                            cmax[j] = make_double2(m, lo);
+                            if constexpr (kColCells)
+                                tj[q][0] = t0, tj[q][1] = t1, tj[q][2] = t2, tj[q][3] = t3;
+                            else
+                                cmax[j] = make_double2(m, lo);
                             csum = csum + m;
                         }
                     }
@@ -1260,7 +1314,25 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 fast = fast && sc >= 8;
                 const double scale = ldexp(1.0, sc);
                 epsS = (double)W * (ldexp(1.0, -sc - 1) + 4e-12) + 1e-9 + 1e-11;
-                if constexpr (EK == 4) {
+                if constexpr (kColCells) {
+                    // ---- the 4 W fixed-point terms t[e][j], by the lane that owns column j
+                    // out of the registers its column maximum was taken from: clamped at
+                    // the column's floor Fc_j = cutOff - 1 - (Smax - cmax_j), to the group's
+                    // cells (the lanes' earlier `fast`: a later refusal goes to the rescan,
+                    // which reads no cell) ----
+                    uint32_t *const cell = (uint32_t *)(gsl + L4.g_cell);  // [4][WM]
+#pragma unroll
+                    for (int q = 0; q < NJ; ++q) {
+                        const int j = li + q * GL;
+                        if (fast && j < W) {
+                            const double fc = a.cutoff - 1.0 - (smax - mj[q]);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                cell[e * WM + j] =
+                                    nopass ? 0u : (uint32_t)rint((fmax(tj[q][e], fc) - fc) * scale);
+                        }
+                    }
+                } else if constexpr (EK == 4) {
                     // column j's clamp floor Fc_j = cutOff - 1 - (Smax - cmax_j), kept in
                     // place of cmax_j for the table build
 #pragma unroll
@@ -1279,14 +1351,15 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                     fv.hiU = nopass || !(x < 4294967290.0) ? 0xffffffffu : (uint32_t)floor(x) + 1u;
                     fv.loU = nopass ? 0xffffffffu : (y <= 1.0 ? 0u : (uint32_t)ceil(y) - 1u);
                 }
-                wave_sync();
+                if constexpr (!kColCells) wave_sync();
                 TLF(tl_w, 3);
                 if constexpr (EK == 4) {
-                    // ---- the 4 W fixed-point terms t[e][j] once (as the generic path's lt
-                    // below: clamped at the column's floor Fc_j, the own segment's cell
-                    // substituted), to the group's cells; then the pair table from them ----
+                    // ---- (not kColCells) the 4 W fixed-point terms t[e][j] once (as the
+                    // generic path's lt below: clamped at the column's floor Fc_j, the own
+                    // segment's cell substituted), to the group's cells; then the pair table
+                    // from them ----
                     uint32_t *const cell = (uint32_t *)(gsl + L4.g_cell);  // [4][WM]
-                    if (fast) {
+                    if (!kColCells && fast) {
                         constexpr int NC = (4 * WM + GL - 1) / GL;
 #pragma unroll
                         for (int q = 0; q < NC; ++q) {
@@ -1551,7 +1624,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             if (pwms_on && kind >= 0) {
                 for (int j = li; j < W; j += GL) {
                     const int e = sym(sseq[pk + j]);
-                    const double pe_e = pcv[e];
+                    const double pe_e = kPcvLate ? pcv[e] / sbg : pcv[e];
                     const bool own = (p >= 0) & (sym(sseq[pp + j]) == e);
                     const double pm = (own ? ppmM : ppmG)[(e < A ? e : 0) * W + j];
                     wfac[j] = make_double2(e < A ? pm / pe_e : 0.0, pe_e);
@@ -1613,6 +1686,9 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 uint8_t *sx = (uint8_t *)(gx + g_seq + (EK ? (gg & 1) * 64 : 0));
                 const double *pcvx = (const double *)(gx + g_pcv);
                 const int ppx = px >= 0 ? px : 0;
+                // (kPcvLate) the group's PCV denominator, as its hold-one-out block formed
+                // it: the same integer total (no symbol outside the alphabet) plus A pc
+                const double sbgx = kPcvLate ? (double)(sumT + (px >= 0 ? W : Lx)) + a.apc : 1.0;
                 if constexpr (H == 2) {
                     // the binary64 folds read symbols: the group's pair codes become
                     // their residues in place (every later reader takes sym() of them)
@@ -1621,7 +1697,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 }
                 for (int c = lane; c < E * W; c += 64) {
                     const int e = magic_div((uint32_t)c, (uint32_t)W, magicW), j = c - e * W;
-                    const double pe_e = pcvx[e];
+                    const double pe_e = kPcvLate ? pcvx[e] / sbgx : pcvx[e];
                     const bool own = (px >= 0) & (sx[ppx + j] == e);
                     const double pm = (own ? ppmM : ppmG)[(e < A ? e : 0) * W + j];
                     *(double2 *)(tab + (e * WS + j) * 16) = make_double2(e < A ? pm / pe_e : 0.0, pe_e);
