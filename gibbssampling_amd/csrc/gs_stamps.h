@@ -33,7 +33,28 @@
 #define TLF(gw, i) \
     do {           \
     } while (0)
-#define TLP(gw, i) TL_MARK_(gw, i)
+// (marks 0 and 1 are kept in registers and stored with mark 2: a store waits for a.stamps,
+// a scalar load of the argument struct, and the interval from the wavefront's start to its
+// first vector loads' issue is what these marks are there to show)
+#undef STAMP_DECL
+#define STAMP_DECL unsigned long long tlp_t_[2] = {0, 0};
+#define TL_STORE_(gw, i, t)                                                           \
+    do {                                                                              \
+        if ((threadIdx.x & 63) == 0 && a.stamps && (gw) < kTlWaves)                   \
+            a.stamps[kStampSlots + (long long)(gw) * kTlMarks + (i)] = (t);           \
+    } while (0)
+#define TLP(gw, i)                                                 \
+    do {                                                           \
+        if constexpr ((i) < 2) {                                   \
+            tlp_t_[(i) & 1] = __builtin_amdgcn_s_memrealtime();    \
+        } else {                                                   \
+            if constexpr ((i) == 2) {                              \
+                TL_STORE_(gw, 0, tlp_t_[0]);                       \
+                TL_STORE_(gw, 1, tlp_t_[1]);                       \
+            }                                                      \
+            TL_MARK_(gw, i);                                       \
+        }                                                          \
+    } while (0)
 #else
 #define TLF(gw, i) TL_MARK_(gw, i)
 #endif

@@ -39,6 +39,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
+#include <type_traits>
 
 #include "gs_bgregime.h"
 #include "gs_common.h"
@@ -60,20 +62,48 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // The pointer is laundered through an empty asm at each use so the load cannot be
 // hoisted; it stays in the constant address space, so the load is an s_load.
 typedef const __attribute__((address_space(4))) SweepArgs KSweepArgs;
+// The kernarg segment of gs_sweep_kernel's one-iteration entry: the arguments that the
+// addresses of the prologue's first vector loads need, as leading scalar parameters (the
+// first 14 dwords: with -mllvm -amdgpu-kernarg-preload-count they are in SGPRs when the
+// wavefront starts, no scalar load in front of those vector loads), then the whole
+// SweepArgs as every other entry has it, at the start of a 64-byte line as there.  The
+// host builds its launch parameters from the same fields (gs_sweep_launch).
+struct SweepOneKargs {
+    const int64_t *agg_in;
+    const uint8_t *pseq;
+    const int32_t *pos_in;
+    const int32_t *comp;
+    int32_t stride;
+    int32_t grid;        // gridDim.x: a hidden argument otherwise, far behind the struct
+    int32_t wr;
+    int32_t wq_waves;    // wq (at most 64 / gl here) | wavefronts a workgroup << 16
+    int32_t seq_stride;  // (a wavefront's sequence is at most 1,024 symbols: it fits)
+    int32_t Lmax;
+    int32_t *err_code;   // (past the preloaded dwords: the same line's scalar load)
+    SweepArgs a;
+};
+constexpr int kOneLeadDwords = 14;
+constexpr int kOneArgsOff = (int)offsetof(SweepOneKargs, a);
+static_assert(offsetof(SweepOneKargs, Lmax) + 4 == 4 * kOneLeadDwords && kOneArgsOff == 64,
+              "the leading parameters: 14 dwords, then err_code, then SweepArgs on its own line");
+// KOFF: the byte offset of the SweepArgs in the kernel's segment (0, or kOneArgsOff: the
+// one-iteration path, where the pointer is not laundered, see kargs_k below)
+template <int KOFF = 0>
 __device__ __forceinline__ KSweepArgs *kargs() {
     uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return (KSweepArgs *)p;
+    if constexpr (KOFF == 0) asm volatile("" : "+s"(p));
+    return (KSweepArgs *)(p + KOFF);
 }
-#define KA(f) (kargs()->f)
+#define KA(f) (kargs<KOFF>()->f)
 // The same inside gs_sweep_kernel: its one-iteration path (ONE) reads the segment
 // pointer as it is.  Straight-line code has no loop to hoist the loads out of (it keeps
 // no SGPR spill without the laundering), and with it the backend fails there ("illegal
 // VGPR to SGPR copy" at the asm).
+// (its SweepArgs lie kOneArgsOff bytes into the segment, behind the leading parameters)
 template <bool LAUNDER>
 __device__ __forceinline__ KSweepArgs *kargs_k() {
-    if constexpr (LAUNDER) return kargs();
-    return (KSweepArgs *)(uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (LAUNDER) return kargs<0>();
+    return (KSweepArgs *)((uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + kOneArgsOff);
 }
 #define KAK(f) (kargs_k<!ONE>()->f)
 
@@ -82,6 +112,7 @@ __device__ __forceinline__ KSweepArgs *kargs_k() {
 // sequences without a motif on the four-symbol path)
 __device__ __noinline__ double log2_ool(double x) { return log2(x); }
 
+template <int KOFF>
 __device__ __forceinline__ void raise_error(const SweepArgs &a, int code, int64_t gidx) {
     (void)a;
     atomicCAS(KA(err_code), 0, code);
@@ -454,7 +485,7 @@ __device__ __forceinline__ void ek4_store_tables(const unsigned char *lds, unsig
 // replica 0 (the others re-zeroed), so that one (A W + A)-cell vector is all a
 // multi-GPU sweep all-reduces.
 // (s_last: the first word of the wavefront slices, dead after the flush)
-template <int WM, int EK>
+template <int WM, int EK, int KOFF>
 __device__ __forceinline__ void sweep_epilogue(const SweepArgs &a, unsigned char *lds, int *s_last,
                                                int tid) {
     unsigned int *const done = KA(done);
@@ -541,12 +572,56 @@ __device__ __attribute__((noinline)) ExactPick rescan_group_h1(KSweepArgs *ka_in
 // not given are drawn once a workgroup, by one wavefront), nothing is prefetched,
 // and the group's first lane stores the result itself (no res[] round trip through LDS).
 // The per-sequence math is the loop's own body, run once.
-template <int WM, int H, int GL, int EK, bool ONE = false>
-__global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
+// ld: what the prologue's first vector loads take their addresses from.  ONE: the entry's
+// leading parameters (SweepOneKargs: in SGPRs at wavefront start), else a's own fields.
+// (the loop path's reads of a's fields stay where they are used)
+struct SweepLeadGiven {
+    const int64_t *agg_in_;
+    const uint8_t *pseq_;
+    const int32_t *pos_in_, *comp_;
+    int32_t stride_, grid_, wr_, wq_waves_, seq_stride_, Lmax_;
+    int32_t *err_code_;
+#define GS_LEAD(T, f) \
+    __device__ __forceinline__ T f() const { return f##_; }
+    GS_LEAD(const int64_t *, agg_in) GS_LEAD(const uint8_t *, pseq) GS_LEAD(const int32_t *, pos_in)
+    GS_LEAD(const int32_t *, comp) GS_LEAD(int32_t, stride) GS_LEAD(unsigned int, grid) GS_LEAD(int32_t, wr)
+    GS_LEAD(int32_t, seq_stride) GS_LEAD(int32_t, Lmax) GS_LEAD(int32_t *, err_code)
+#undef GS_LEAD
+    __device__ __forceinline__ int32_t wq() const { return wq_waves_ & 0xffff; }
+    __device__ __forceinline__ int32_t nthreads() const { return (wq_waves_ >> 16) * 64; }
+};
+struct SweepLeadOfArgs {
+    const SweepArgs &a;
+#define GS_LEAD(T, f) \
+    __device__ __forceinline__ T f() const { return a.f; }
+    GS_LEAD(const int64_t *, agg_in) GS_LEAD(const uint8_t *, pseq) GS_LEAD(const int32_t *, pos_in)
+    GS_LEAD(const int32_t *, comp) GS_LEAD(int32_t, stride) GS_LEAD(int32_t, wq) GS_LEAD(int32_t, wr)
+    GS_LEAD(int64_t, seq_stride) GS_LEAD(int32_t, Lmax) GS_LEAD(int32_t *, err_code)
+#undef GS_LEAD
+    __device__ __forceinline__ unsigned int grid() const { return gridDim.x; }
+    __device__ __forceinline__ int32_t nthreads() const { return blockDim.x; }
+};
+// The one-iteration entry's leading parameter types (SweepOneKargs, member by member)
+#define GS_ONE_LEAD_TYPES                                                                              \
+    const int64_t *, const uint8_t *, const int32_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, \
+        int32_t, int32_t, int32_t *
+// LP: empty, or (ONE) GS_ONE_LEAD_TYPES: one kernel name and one body for both entries.
+// (The body stays in the kernel function itself: moved into a device function that two
+// entries call, the workgroup-size reads of the barrier reduction were no longer folded
+// to the uniform size and the loop path gained SGPR spills.)
+template <int WM, int H, int GL, int EK, bool ONE = false, class... LP>
+__global__ void GS_SWEEP_ATTR gs_sweep_kernel(LP... lp, SweepArgs a) {
+    static_assert(sizeof...(LP) == (ONE ? 11 : 0), "leading parameters: the one-iteration entry's alone");
+    const auto ld = [&] {
+        if constexpr (ONE)
+            return SweepLeadGiven{lp...};
+        else
+            return SweepLeadOfArgs{a};
+    }();
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int G = 64 / GL;
     // sweep_waves(H) wavefronts, fewer when the LDS of that many does not fit
-    const int kWavesPerBlock = blockDim.x >> 6, kSweepThreads = blockDim.x;
+    const int kWavesPerBlock = ld.nthreads() >> 6, kSweepThreads = ld.nthreads();
     constexpr int NG = WM / H, WS = tab_stride(WM), LS = lt_stride(WM), GS = gt_stride(WM);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar loads
@@ -626,7 +701,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     double2 *wfac = (double2 *)(gsl + g_wfac);      // [WM] factors of the picked window
     // EK = 4: the scan reads a second copy of the codes, x 8 (pair_entry), right after
     // the sequence's slot (its span: Lmax + WM + 96 bytes and the odd group's 64)
-    uint8_t *scode8 = EK ? sseq + ((a.Lmax + WM + 96 + 15) & ~15) + 64 : sseq;
+    uint8_t *scode8 = EK ? sseq + ((ld.Lmax() + WM + 96 + 15) & ~15) + 64 : sseq;
     const uint8_t *lcodes = scode8;
     const unsigned char *ltab = H == 2 ? gt : (const unsigned char *)lt;
     // EK = 4 runs the certified sweep only (mode 0, no caller's PCV): the other modes
@@ -644,7 +719,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         else
             return (int)x;
     };
-    const uint8_t *gseq = H == 2 ? a.pseq : a.seq;  // what is staged
+    const uint8_t *gseq = H == 2 ? ld.pseq() : a.seq;  // what is staged
     STAMP_DECL
     const int tl_w = blockIdx.x * kWavesPerBlock + wid;  // (timeline marks: stamps build)
     (void)tl_w;
@@ -657,7 +732,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // sweeps, this wavefront's first 64 descriptors, then each group's first
     // sequence and composition.
     TLP(tl_w, 0);
-    const int err0 = __hip_atomic_load(a.err_code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (ONE: after the loads whose addresses are there at wavefront start; this one's is a
+    // scalar load away)
+    int err0 = 0;
+    if constexpr (!ONE) err0 = __hip_atomic_load(ld.err_code(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // EK = 4: the snapshot's workgroup tables (C, T, PPM, PPM', their logs, the PCV log
     // table: ek4_build_tables) are built by every workgroup from the replicas (default),
     // or come finished (a.ftab_in, gs_set_tuning ftab_mode 1 / 2: a table kernel before
@@ -690,9 +768,15 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // the fourth wavefront's: thread 192 + c loads cell c's replicas too, so that no
     // wavefront takes two binary64 logs and divisions before the prologue's barrier.
     constexpr bool kSplitM = EK == 4 && 4 * WM <= 64;
-    int64_t rc[kRepl], rt[kRepl], rm[kSplitM ? kRepl : 1];
+    // (ONE: the count-minus-one cells' low halves alone, all their sum is read by: a high
+    // half nobody reads gave its register to the next value, which then waited for the load)
+    using RmT = std::conditional_t<ONE, int32_t, int64_t>;
+    int64_t rc[kRepl], rt[kRepl];
+    RmT rm[kSplitM ? kRepl : 1];
     const int nT = 4 * (W + 1), tt = tid - 64;
-    const bool hasC = EK == 4 && tid < a.cells, hasT = EK == 4 && tt >= 0 && tt < nT + 4;
+    // (ONE: the cell count is the template's, A W + A at A = 4 and W = WM: gs_sweep_launch checks)
+    const int cells = ONE ? 4 * WM + 4 : a.cells;
+    const bool hasC = EK == 4 && tid < cells, hasT = EK == 4 && tt >= 0 && tt < nT + 4;
     const bool hasM = kSplitM && tid >= 192 && tid - 192 < AW;
     const int acell = tt < nT ? tt / (W + 1) : tt - nT;
     if constexpr (EK == 4) {
@@ -700,17 +784,18 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         for (int r = 0; r < kRepl; ++r) rc[r] = rt[r] = 0;
 #pragma unroll
         for (int r = 0; r < (kSplitM ? kRepl : 1); ++r) rm[r] = 0;
-        if (!useF && a.agg_in) {
+        if (!useF && ld.agg_in()) {
             if (hasC)
 #pragma unroll
-                for (int r = 0; r < kRepl; ++r) rc[r] = a.agg_in[(int64_t)r * a.stride + tid];
+                for (int r = 0; r < kRepl; ++r) rc[r] = ld.agg_in()[(int64_t)r * ld.stride() + tid];
             if (hasT)
 #pragma unroll
-                for (int r = 0; r < kRepl; ++r) rt[r] = a.agg_in[(int64_t)r * a.stride + AW + acell];
+                for (int r = 0; r < kRepl; ++r) rt[r] = ld.agg_in()[(int64_t)r * ld.stride() + AW + acell];
             if constexpr (kSplitM) {
                 if (hasM)
 #pragma unroll
-                    for (int r = 0; r < kRepl; ++r) rm[r] = a.agg_in[(int64_t)r * a.stride + tid - 192];
+                    for (int r = 0; r < kRepl; ++r)
+                        rm[r] = *(const RmT *)&ld.agg_in()[(int64_t)r * ld.stride() + tid - 192];
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -727,10 +812,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // and the cache lines of their descriptors and compositions — are read by one
     // XCD's L2 instead of by all eight (cfg2 PMC traffic per launch 4.96 -> 3.16 MB).
     constexpr int wstride = 1;
-    const int xcd = blockIdx.x % kRepl, q8 = gridDim.x / kRepl, r8 = gridDim.x % kRepl;
+    const unsigned int ngrid = ld.grid();
+    const int xcd = blockIdx.x % kRepl, q8 = ngrid / kRepl, r8 = ngrid % kRepl;
     const int lblock = xcd * q8 + min(xcd, r8) + (int)(blockIdx.x / kRepl);
-    const int nwaves = gridDim.x * kWavesPerBlock, lwave = lblock * kWavesPerBlock + wid;
-    const int qn = a.wq, rn = a.wr;  // n_local / nwaves and its remainder (host)
+    const int nwaves = ngrid * kWavesPerBlock, lwave = lblock * kWavesPerBlock + wid;
+    const int qn = ld.wq(), rn = ld.wr();  // n_local / nwaves and its remainder (host)
     (void)nwaves;
     const int n0 = lwave * qn + min(lwave, rn);
     const int cnt = qn + (lwave < rn ? 1 : 0);
@@ -803,29 +889,43 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
         // every lane of group gi loads slot gi's own values (one address a group): the
         // descriptor first (equal lengths: none), so that the sequence's load waits for
         // it alone, then the snapshot position and the uniform
+        // (in the order of what their addresses wait for: the entry's leading parameters
+        // alone, then fields of `a`: the given uniform, the sticky error flag, the audit)
         const bool rd = gi < cnt;
         const int nb = n0 + gi;
-        const unsigned long long oob = __ballot(rd && li == 0 && (unsigned)nb >= (unsigned)a.n_local);
-        if (oob && lane == 0)  // audit, gs_stats [13] (as the loop path's descriptors')
-            atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
-                      (unsigned long long)__popcll(oob));
-        if (a.seq_stride > 0) {
-            b_len = a.Lmax;
-            b_off = (int64_t)nb * a.seq_stride;
-        } else if (rd) {
+        // (each of the two cases issues its own loads, the equal-length one first: where the
+        // descriptor's loads came before it in the code, its address arithmetic waited for
+        // every load in flight, the aggregate replicas' among them, as if they had been
+        // issued)
+        auto first_loads = [&] {
+            b_pos = ld.pos_in()[nb];
+            if (b_len <= 16 * GL && li * 16 < b_len) pf = *(const uint4 *)(gseq + b_off + li * 16);
+            if (li < CS) cpf = ld.comp()[(int64_t)nb * CS + li];
+        };
+        const bool eq_len = ld.seq_stride() > 0;
+        if (eq_len) {
+            b_len = ld.Lmax();
+            b_off = (int64_t)nb * ld.seq_stride();
+        }
+        if (eq_len && rd) first_loads();
+        __builtin_amdgcn_sched_barrier(0);
+        if (!eq_len && rd) {
             b_len = a.len[nb];
             b_off = a.doff[nb];
+            first_loads();
         }
         if (rd) {
-            b_pos = a.pos_in[nb];
             if constexpr (kWgU) {
                 if (a.u_in) b_u = a.u_in[nb];
             } else {
                 b_u = a.u_in ? a.u_in[nb] : uniform(a.seed, rng_stream, (uint64_t)(a.global_offset + nb));
             }
-            if (b_len <= 16 * GL && li * 16 < b_len) pf = *(const uint4 *)(gseq + b_off + li * 16);
-            if (li < CS) cpf = a.comp[(int64_t)nb * CS + li];
         }
+        err0 = __hip_atomic_load(ld.err_code(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long oob = __ballot(rd && li == 0 && (unsigned)nb >= (unsigned)a.n_local);
+        if (oob && lane == 0)  // audit, gs_stats [13] (as the loop path's descriptors')
+            atomicAdd(&(KAK(fallbacks) + (blockIdx.x % kRepl) * kStatStride)[13],
+                      (unsigned long long)__popcll(oob));
         // the counter RNG once a workgroup: lane i of one wavefront draws the uniform of
         // the workgroup's sequence wn0 + i (at most 4 G <= 16 of them), for every group to
         // read after the prologue's barrier.  The wavefront is one that takes no binary64
@@ -906,11 +1006,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             if (i * 256 + tid < kFtV) ((uint4 *)lds)[i * 256 + tid] = ftv[i];
         TLP(tl_w, 4);
     }
-    for (int c = EK ? a.cells : tid; c < a.cells; c += kSweepThreads) {
+    for (int c = EK ? cells : tid; c < cells; c += kSweepThreads) {
         int64_t s = 0;
-        if (a.agg_in) {
+        if (ld.agg_in()) {
 #pragma unroll
-            for (int r = 0; r < kRepl; ++r) s += a.agg_in[(int64_t)r * a.stride + c];
+            for (int r = 0; r < kRepl; ++r) s += ld.agg_in()[(int64_t)r * ld.stride() + c];
         }
         if (c < AW)
             cg[c] = (int32_t)s;
@@ -923,7 +1023,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     if (blockIdx.x == 0) {
         int64_t *const agg_zero = KAK(agg_zero);
         if (agg_zero)
-            for (int i = tid; i < kRepl * a.stride; i += kSweepThreads) agg_zero[i] = 0;
+            for (int i = tid; i < kRepl * ld.stride(); i += kSweepThreads) agg_zero[i] = 0;
     }
     if (mode == 0) {
         // normalizePPM (.fs:257-260): PPM = (C + pc)/den, and (C - 1 + pc)/den for the
@@ -936,7 +1036,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 lppmG[tid] = log2(g);
             }
             if (hasM) {
-                int64_t mc = 0;
+                RmT mc = 0;
 #pragma unroll
                 for (int r = 0; r < kRepl; ++r) mc += rm[r];
                 const double m = ((double)((int32_t)mc - 1) + a.pc) / a.den;
@@ -985,7 +1085,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     // an earlier sweep raised an error: its snapshot is void, nothing to do but the
     // done count (the whole workgroup decides together, at the prologue's barrier)
     if (__syncthreads_or(err0 != 0)) {
-        sweep_epilogue<WM, EK>(a, lds, (int *)(lds + o_wave), tid);
+        sweep_epilogue<WM, EK, ONE ? kOneArgsOff : 0>(a, lds, (int *)(lds + o_wave), tid);
         return;
     }
     TLINE(tl_w, 2);
@@ -1155,7 +1255,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             // Σ over the 49 slots: alphabet part + the sequence's own other symbols
             const int64_t tot = sumT + (p >= 0 ? seg_alpha : L - na) + na;
             if (act && !pcv_fixed && tot > 2147483647LL) {  // Checked Array.sum (.fs:117)
-                if (li == 0) raise_error(a, 3, gidx);
+                if (li == 0) raise_error<ONE ? kOneArgsOff : 0>(a, 3, gidx);
                 keep = false;
             }
             // PCV (.fs:119); outside the alphabet the raw count (Q3).  The ...ByPCV
@@ -1672,7 +1772,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
                 const int px = __builtin_amdgcn_readlane(p, src);
                 const double ux = lane_read_f64(u, src);
                 if constexpr (H == 1) {
-                    const ExactPick r = rescan_group_h1<WM>(kargs(), gg, Lx, px, ux);
+                    const ExactPick r = rescan_group_h1<WM>(kargs<0>(), gg, Lx, px, ux);
                     if (gi == gg) {
                         kind = r.kind;
                         pk = r.win;
@@ -1811,7 +1911,7 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
             TLINE(tl_w, 5);
             TLF(tl_w, 6);
             if (keep && kind < 0) {  // every category missed: the list index overruns
-                if (li == 0) raise_error(a, 2, gidx);
+                if (li == 0) raise_error<ONE ? kOneArgsOff : 0>(a, 2, gidx);
                 keep = false;
             }
             newp = kind == 0 ? -1 : pk;
@@ -1889,8 +1989,8 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     __syncthreads();
     STAMP(11);
     STAMP_FLUSH(nseq_done);
-    int64_t *dst = KAK(agg_out) + (int64_t)(blockIdx.x % kRepl) * a.stride;
-    for (int c = tid; c < a.cells; c += kSweepThreads) {
+    int64_t *dst = KAK(agg_out) + (int64_t)(blockIdx.x % kRepl) * ld.stride();
+    for (int c = tid; c < cells; c += kSweepThreads) {
         int64_t v = 0;
 #pragma unroll
         for (int w = 0; w < kWavesPerBlock; ++w) {
@@ -1911,8 +2011,11 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
     }
     TLINE(tl_w, 7);
     TLF(tl_w, 7);
-    sweep_epilogue<WM, EK>(a, lds, (int *)(lds + o_wave), tid);
+    sweep_epilogue<WM, EK, ONE ? kOneArgsOff : 0>(a, lds, (int *)(lds + o_wave), tid);
 }
+
+typedef void (*SweepLoopEntry)(SweepArgs);
+typedef void (*SweepOneEntry)(GS_ONE_LEAD_TYPES, SweepArgs);
 
 #ifndef GS_FOR_EACH_WM  // (a single WM for quick resource checks: -D'GS_FOR_EACH_WM(X)=X(12)')
 #define GS_FOR_EACH_WM(X) X(4) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) X(48) X(56) X(64)
@@ -1925,9 +2028,15 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(SweepArgs a) {
 // the two halves compile in parallel.
 template <int WM, bool ONE>
 static const void *sweep_ek4_for(int gl) {
-    if (gl == 16) return (const void *)&gs_sweep_kernel<WM, 2, 16, 4, ONE>;
-    if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 2, 32, 4, ONE>;
-    if (gl == 64) return (const void *)&gs_sweep_kernel<WM, 2, 64, 4, ONE>;
+    if constexpr (ONE) {
+        if (gl == 16) return (const void *)static_cast<SweepOneEntry>(&gs_sweep_kernel<WM, 2, 16, 4, true, GS_ONE_LEAD_TYPES>);
+        if (gl == 32) return (const void *)static_cast<SweepOneEntry>(&gs_sweep_kernel<WM, 2, 32, 4, true, GS_ONE_LEAD_TYPES>);
+        if (gl == 64) return (const void *)static_cast<SweepOneEntry>(&gs_sweep_kernel<WM, 2, 64, 4, true, GS_ONE_LEAD_TYPES>);
+    } else {
+        if (gl == 16) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 16, 4>);
+        if (gl == 32) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 32, 4>);
+        if (gl == 64) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 64, 4>);
+    }
     return nullptr;
 }
 // The four-symbol sweep's workgroup tables of the snapshot in `rep` (kRepl replicas,
@@ -2062,12 +2171,12 @@ static const void *sweep_kernel_for(int h, int gl, int ek, int one) {
     if (h == 2 && ek == 4) {
         return gs_sweep_ek4_ptr(WM, gl, one);
     } else if (h == 2) {
-        if (gl == 16) return (const void *)&gs_sweep_kernel<WM, 2, 16, 0>;
-        if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 2, 32, 0>;
-        if (gl == 64) return (const void *)&gs_sweep_kernel<WM, 2, 64, 0>;
+        if (gl == 16) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 16, 0>);
+        if (gl == 32) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 32, 0>);
+        if (gl == 64) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 2, 64, 0>);
     } else {  // more than 16 symbols: groups of >= 32 lanes (E + 1 <= GL)
-        if (gl == 32) return (const void *)&gs_sweep_kernel<WM, 1, 32, 0>;
-        if (gl == 64) return (const void *)&gs_sweep_kernel<WM, 1, 64, 0>;
+        if (gl == 32) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 1, 32, 0>);
+        if (gl == 64) return (const void *)static_cast<SweepLoopEntry>(&gs_sweep_kernel<WM, 1, 64, 0>);
     }
     return nullptr;
 }
@@ -2126,7 +2235,18 @@ hipError_t gs_sweep_launch(const SweepArgs &a, int grid, size_t lds_bytes, hipSt
     const int nwaves = grid * a.waves;  // the kernel's slot ranges: n_local split evenly
     args.wq = a.n_local / nwaves;
     args.wr = a.n_local % nwaves;
-    void *params[] = {&args};
+    // the one-iteration entry: its leading parameters (SweepOneKargs), then the struct
+    SweepOneKargs one = {args.agg_in, args.pseq, args.pos_in,           args.comp, args.stride,   grid,
+                         args.wr,     args.wq | (a.waves << 16),        (int32_t)args.seq_stride,
+                         args.Lmax,   args.err_code,                    args};
+    // (what the entry takes for granted: the narrowed fields fit, the cells are A W + A)
+    if (gs_sweep_one(a) && (one.seq_stride != args.seq_stride || args.wq > 0xffff || a.waves > 0x7fff ||
+                            a.cells != 4 * a.W + 4))
+        return hipErrorInvalidValue;
+    void *params_loop[] = {&args};
+    void *params_one[] = {&one.agg_in,   &one.pseq,       &one.pos_in, &one.comp,     &one.stride, &one.grid,
+                          &one.wr,       &one.wq_waves,   &one.seq_stride, &one.Lmax, &one.err_code, &one.a};
+    void **const params = gs_sweep_one(a) ? params_one : params_loop;
     const int threads = 64 * a.waves;
     if (!start && !stop)  // plain launch (also the form a stream capture records)
         return hipLaunchKernel(k, dim3(grid), dim3(threads), params, lds_bytes, stream);

@@ -43,8 +43,11 @@ def main():
                         "-ffp-contract=off", "-DGS_MARKS", only, "--cuda-device-only", "-S",
                         str(SRC / unit), "-o", str(out)], check=True)
         text = out.read_text()
-    name = f"_Z15gs_sweep_kernelILi{wm}ELi{h}ELi{gl}ELi{ek}ELb{one}EEvN2gs9SweepArgsE:"
-    body = text[text.index(name):]
+    # (the entry's leading parameter pack follows the template's values: empty on the loop
+    # path, the one-iteration entry's SweepOneKargs members)
+    m = re.search(rf"^_Z15gs_sweep_kernelILi{wm}ELi{h}ELi{gl}ELi{ek}ELb{one}EJ\w*EEvDpT4_N2gs9SweepArgsE:",
+                  text, re.M)
+    body = text[m.start():]
     body = body[:body.index(".Lfunc_end")]
     seg = "entry"
     counts = collections.OrderedDict()
