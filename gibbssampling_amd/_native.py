@@ -147,6 +147,8 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_motif_sampling": (C.c_int, [vp, i32, f64, f64, u64, i32, i32, vp, vp, P(i32)]),
         "gs_motif_sampling_batch": (C.c_int, [vp, i32, f64, f64, vp, i32, i32, i32, vp, vp, vp,
                                               vp]),
+        "gs_motif_sampling_batch_fixed": (C.c_int, [vp, i32, f64, f64, vp, vp, vp, i32, i32, i32,
+                                                    vp, vp, vp, vp]),
         "gs_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_motif_sweep_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp]),
         "gs_motif_greedy_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, i32, vp, vp, vp,
@@ -155,6 +157,8 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
                                               vp, P(i32)]),
         "gs_motif_sampling_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp]),
+        "gs_motif_sampling_multi_batch_fixed": (C.c_int, [vp, i32, i32, f64, f64, vp, vp, vp, i32,
+                                                          i32, i32, i32, vp, vp, vp, vp, vp]),
         "gs_multi_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_multi_batch_last_info": (C.c_int, [vp, vp]),
         "gs_motif_run_batch": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, vp, vp,
@@ -171,6 +175,8 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_site_refine": (C.c_int, [vp, i32, f64, i32, i32, vp, vp, P(i32)]),
         "gs_site_sampling": (C.c_int, [vp, i32, f64, u64, i32, i32, vp, vp, vp]),
         "gs_site_sampling_batch": (C.c_int, [vp, i32, f64, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "gs_site_sampling_batch_fixed": (C.c_int, [vp, i32, f64, vp, vp, vp, i32, i32, i32, vp, vp,
+                                                   vp, vp]),
         "gs_site_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_counts": (C.c_int, [vp, i32, vp, vp, vp]),
         "gs_random_starts": (C.c_int, [vp, i32, f64, u64, i32, vp, vp]),
@@ -213,6 +219,21 @@ def header_symbols(header: Path = HEADER_PATH) -> list[str]:
 
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def fixed_args(pcv, ppm, W: int):
+    """The pcv= / ppm= keywords of the batched drivers as contiguous float64 arrays (None
+    stays None): 49 CompositeVector slots, 49 slot rows x W columns.  A wrong shape raises
+    ArgumentError before any native call."""
+    if pcv is not None:
+        pcv = np.ascontiguousarray(pcv, np.float64)
+        if pcv.shape != (49,):
+            raise ArgumentError(GS_E_ARG, "pcv needs the 49 CompositeVector slots")
+    if ppm is not None:
+        ppm = np.ascontiguousarray(ppm, np.float64)
+        if ppm.shape != (49, int(W)):
+            raise ArgumentError(GS_E_ARG, "ppm needs 49 slot rows x motifLength columns")
+    return pcv, ppm
 
 
 class Context:
@@ -364,21 +385,31 @@ class Context:
         return pos, pwms, passes.value
 
     def motif_sampling_batch(self, W: int, pc: float, cutoff: float, seeds, init_mode: int = 0,
-                             max_passes: int = 1000):
+                             max_passes: int = 1000, *, pcv=None, ppm=None):
         """R independent doMotifSampling runs in one call, row r exactly
         motif_sampling(W, pc, cutoff, seeds[r], ...): the chains' greedy passes run
         as R concurrent workgroups -> (pos[R, N], pwms[R, N], passes[R], status[R]).
         A chain that raises (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows
-        valid; errors of the call itself raise."""
+        valid; errors of the call itself raise.  pcv (49 slots) / ppm (49 x W): the
+        ByPCV / WithPPM twins (gs_motif_sampling_batch_fixed), row r what motif_sampling
+        gives on a context with set_fixed_pcv(pcv) / set_fixed_ppm(ppm)."""
+        pcv, ppm = fixed_args(pcv, ppm, W)
         seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
         R = len(seeds)
         pos = np.empty((R, self.n_local), np.int32)
         pwms = np.empty((R, self.n_local), np.float64)
         passes = np.zeros(R, np.int32)
         status = np.zeros(R, np.int32)
-        st = self.lib.gs_motif_sampling_batch(self.h, int(W), float(pc), float(cutoff), _ptr(seeds),
-                                              R, int(init_mode), int(max_passes), _ptr(pos),
-                                              _ptr(pwms), _ptr(passes), _ptr(status))
+        if pcv is None and ppm is None:
+            st = self.lib.gs_motif_sampling_batch(self.h, int(W), float(pc), float(cutoff),
+                                                  _ptr(seeds), R, int(init_mode), int(max_passes),
+                                                  _ptr(pos), _ptr(pwms), _ptr(passes),
+                                                  _ptr(status))
+        else:
+            st = self.lib.gs_motif_sampling_batch_fixed(
+                self.h, int(W), float(pc), float(cutoff), _ptr(pcv), _ptr(ppm), _ptr(seeds), R,
+                int(init_mode), int(max_passes), _ptr(pos), _ptr(pwms), _ptr(passes),
+                _ptr(status))
         if st != GS_OK and not status.any():
             self._check(st)
         return pos, pwms, passes, status
@@ -445,13 +476,16 @@ class Context:
 
     def motif_sampling_multi_batch(self, motif_amount: int, W: int, pc: float, cutoff: float,
                                    seeds, init_mode: int = 0, max_passes: int = 1000,
-                                   cap: int | None = None):
+                                   cap: int | None = None, *, pcv=None, ppm=None):
         """R independent doMotifSampling runs with any motifAmount in one call, row r
         exactly motif_sampling_multi(motif_amount, W, pc, cutoff, seeds[r], ...): sweep 0
         over all (chain, target) pairs at once, the chains' greedy passes side by side ->
         (cnt[R, N], pos[R, N, cap], pwms[R, N], passes[R], status[R]).  A chain that
         raises (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows valid; errors
-        of the call itself raise."""
+        of the call itself raise.  pcv (49 slots) / ppm (49 x W): the ByPCV / WithPPM twins
+        (gs_motif_sampling_multi_batch_fixed), row r what motif_sampling_multi gives on a
+        context with set_fixed_pcv(pcv) / set_fixed_ppm(ppm)."""
+        pcv, ppm = fixed_args(pcv, ppm, W)
         cap = int(cap or motif_amount)
         seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
         R = len(seeds)
@@ -460,10 +494,16 @@ class Context:
         pwms = np.zeros((R, self.n_local), np.float64)
         passes = np.zeros(R, np.int32)
         status = np.zeros(R, np.int32)
-        st = self.lib.gs_motif_sampling_multi_batch(
-            self.h, int(motif_amount), int(W), float(pc), float(cutoff), _ptr(seeds), R,
-            int(init_mode), int(max_passes), cap, _ptr(cnt), _ptr(pos), _ptr(pwms), _ptr(passes),
-            _ptr(status))
+        if pcv is None and ppm is None:
+            st = self.lib.gs_motif_sampling_multi_batch(
+                self.h, int(motif_amount), int(W), float(pc), float(cutoff), _ptr(seeds), R,
+                int(init_mode), int(max_passes), cap, _ptr(cnt), _ptr(pos), _ptr(pwms),
+                _ptr(passes), _ptr(status))
+        else:
+            st = self.lib.gs_motif_sampling_multi_batch_fixed(
+                self.h, int(motif_amount), int(W), float(pc), float(cutoff), _ptr(pcv), _ptr(ppm),
+                _ptr(seeds), R, int(init_mode), int(max_passes), cap, _ptr(cnt), _ptr(pos),
+                _ptr(pwms), _ptr(passes), _ptr(status))
         if st != GS_OK and not status.any():
             self._check(st)
         return cnt, pos, pwms, passes, status
@@ -654,22 +694,30 @@ class Context:
         return pos, score, passes
 
     def site_sampling_batch(self, W: int, pc: float, seeds, init_mode: int = 0,
-                            max_passes: int = 1000):
+                            max_passes: int = 1000, *, pcv=None, ppm=None):
         """R independent doSiteSampling runs in one call, row r exactly
         site_sampling(W, pc, seeds[r], ...): the chains' Gauss–Seidel passes run as R
         concurrent workgroups, their shifted passes side by side ->
         (pos[R, N], score[R, N], passes[R, 3], status[R]).  A chain that raises
         (status[r] != 0, e.g. GS_E_OVERFLOW) leaves the other rows valid; errors of the
-        call itself raise."""
+        call itself raise.  pcv (49 slots) / ppm (49 x W): the WithBPV / WithPPM twins
+        (gs_site_sampling_batch_fixed), row r what site_sampling gives on a context with
+        set_fixed_pcv(pcv) / set_fixed_ppm(ppm)."""
+        pcv, ppm = fixed_args(pcv, ppm, W)
         seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
         R = len(seeds)
         pos = np.empty((R, self.n_local), np.int32)
         score = np.empty((R, self.n_local), np.float64)
         passes = np.zeros((R, 3), np.int32)
         status = np.zeros(R, np.int32)
-        st = self.lib.gs_site_sampling_batch(self.h, int(W), float(pc), _ptr(seeds), R,
-                                             int(init_mode), int(max_passes), _ptr(pos),
-                                             _ptr(score), _ptr(passes), _ptr(status))
+        if pcv is None and ppm is None:
+            st = self.lib.gs_site_sampling_batch(self.h, int(W), float(pc), _ptr(seeds), R,
+                                                 int(init_mode), int(max_passes), _ptr(pos),
+                                                 _ptr(score), _ptr(passes), _ptr(status))
+        else:
+            st = self.lib.gs_site_sampling_batch_fixed(
+                self.h, int(W), float(pc), _ptr(pcv), _ptr(ppm), _ptr(seeds), R, int(init_mode),
+                int(max_passes), _ptr(pos), _ptr(score), _ptr(passes), _ptr(status))
         if st != GS_OK and not status.any():
             self._check(st)
         return pos, score, passes, status

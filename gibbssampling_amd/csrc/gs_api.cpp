@@ -98,6 +98,75 @@ static int batch_entry_checks(gs_ctx *c, const char *name, int32_t W, const char
     return GS_OK;
 }
 
+// The slot mapping of the caller's fixed values (gs_set_fixed_pcv / gs_set_fixed_ppm and
+// the *_batch_fixed entry points).  The PCV by encoded symbol, [64]: the caller's value at
+// each symbol's CompositeVector slot, symbols outside the alphabet included.
+static std::vector<double> encode_pcv(const gs_ctx *c, const double *pcv49) {
+    std::vector<double> h(64, 0.0);
+    for (int s = 0; s < kSlots; ++s)
+        if (c->enc[s] != 0xff) h[c->enc[s]] = pcv49[s];
+    return h;
+}
+// The PPM in alphabet order, [A][W], as the initialiser's PPM table.
+static std::vector<double> encode_ppm(const gs_ctx *c, const double *ppm49, int32_t W) {
+    std::vector<double> h((size_t)c->A * W);
+    for (int a = 0; a < c->A; ++a)
+        for (int j = 0; j < W; ++j) h[(size_t)a * W + j] = ppm49[(c->alphabet[a] - kSlot0) * W + j];
+    return h;
+}
+
+// The caller's PCV / PPM of one *_batch_fixed call in the context's fixed slots, which the
+// drivers and the single-chain stages they reuse read; the context's own (use_pcv, use_ppm,
+// d_pcv_fixed, d_ppm_fixed, ppm_W) are back on scope exit.  Set after the entry's checks
+// (W valid, the context's own flags clear) and after takeover_reset; nothing a later
+// sweep selects is kept from under it (scratch_used, gs_batch.cpp; captured graphs are
+// neither replayed nor captured by a batch).
+struct FixedScope {
+    gs_ctx *c;
+    const bool use_pcv, use_ppm;
+    double *const d_pcv, *const d_ppm;
+    const int32_t ppm_W;
+    double *mine_pcv = nullptr, *mine_ppm = nullptr;
+    explicit FixedScope(gs_ctx *ctx)
+        : c(ctx), use_pcv(ctx->use_pcv), use_ppm(ctx->use_ppm), d_pcv(ctx->d_pcv_fixed),
+          d_ppm(ctx->d_ppm_fixed), ppm_W(ctx->ppm_W) {}
+    FixedScope(const FixedScope &) = delete;
+    FixedScope &operator=(const FixedScope &) = delete;
+    int set(const double *pcv49, const double *ppm49, int32_t W) {
+        if (pcv49) {
+            const std::vector<double> h = encode_pcv(c, pcv49);
+            HIP_TRY(c, hipMalloc(&mine_pcv, h.size() * sizeof(double)));
+            HIP_TRY(c, hipMemcpy(mine_pcv, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+            c->d_pcv_fixed = mine_pcv;
+            c->use_pcv = true;
+        }
+        if (ppm49) {
+            const std::vector<double> h = encode_ppm(c, ppm49, W);
+            HIP_TRY(c, hipMalloc(&mine_ppm, h.size() * sizeof(double)));
+            HIP_TRY(c, hipMemcpy(mine_ppm, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+            c->d_ppm_fixed = mine_ppm;
+            c->ppm_W = W;
+            c->use_ppm = true;
+        }
+        return GS_OK;
+    }
+    ~FixedScope() {
+        c->use_pcv = use_pcv;
+        c->use_ppm = use_ppm;
+        c->d_pcv_fixed = d_pcv;
+        c->d_ppm_fixed = d_ppm;
+        c->ppm_W = ppm_W;
+        // (nothing in flight may read them: the drivers end synchronised on every path)
+        if (mine_pcv || mine_ppm) (void)hipStreamSynchronize(c->stream);
+        dfree(mine_pcv);
+        dfree(mine_ppm);
+    }
+};
+// (the refusal of the *_batch_fixed entry points while the context holds its own values)
+static const char *const kFixedTwiceText =
+    "the context holds a fixed PCV / PPM of its own: clear it (gs_set_fixed_pcv / "
+    "gs_set_fixed_ppm with null) and pass the values as arguments";
+
 extern "C" {
 
 const char *gs_version(void) { return kVersion; }
@@ -396,10 +465,7 @@ int gs_set_fixed_pcv(gs_ctx *c, const double *pcv49) {
         drop_graphs(c);
         return GS_OK;
     }
-    // by encoded symbol: the caller's value at each symbol's CompositeVector slot
-    std::vector<double> h(64, 0.0);
-    for (int s = 0; s < kSlots; ++s)
-        if (c->enc[s] != 0xff) h[c->enc[s]] = pcv49[s];
+    const std::vector<double> h = encode_pcv(c, pcv49);
     if (!c->d_pcv_fixed) HIP_TRY(c, hipMalloc(&c->d_pcv_fixed, 64 * sizeof(double)));
     HIP_TRY(c, hipMemcpy(c->d_pcv_fixed, h.data(), 64 * sizeof(double), hipMemcpyHostToDevice));
     c->use_pcv = true;
@@ -418,10 +484,7 @@ int gs_set_fixed_ppm(gs_ctx *c, const double *ppm49, int32_t W) {
         return GS_OK;
     }
     if (W < 1 || W > 64) return fail(c, GS_E_ARG, "motifLength must be in [1, 64]");
-    // alphabet order, as the initialiser's PPM table
-    std::vector<double> h((size_t)c->A * W);
-    for (int a = 0; a < c->A; ++a)
-        for (int j = 0; j < W; ++j) h[(size_t)a * W + j] = ppm49[(c->alphabet[a] - kSlot0) * W + j];
+    const std::vector<double> h = encode_ppm(c, ppm49, W);
     dfree(c->d_ppm_fixed);
     HIP_TRY(c, hipMalloc(&c->d_ppm_fixed, h.size() * sizeof(double)));
     HIP_TRY(c, hipMemcpy(c->d_ppm_fixed, h.data(), h.size() * sizeof(double),
@@ -682,10 +745,13 @@ int gs_motif_sampling(gs_ctx *c, int32_t W, double pc, double cutoff, uint64_t s
     return gs_state_get(c, pos_out, pwms_out);
 }
 
-int gs_motif_sampling_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds,
-                            int32_t n_chains, int32_t init_mode, int32_t max_passes,
-                            int32_t *pos_out, double *pwms_out, int32_t *passes_out,
-                            int32_t *status_out) {
+// gs_motif_sampling_batch (pcv49 and ppm49 null) and gs_motif_sampling_batch_fixed.
+static int motif_sampling_batch_entry(gs_ctx *c, int32_t W, double pc, double cutoff,
+                                      const double *pcv49, const double *ppm49,
+                                      const uint64_t *seeds, int32_t n_chains, int32_t init_mode,
+                                      int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                                      int32_t *passes_out, int32_t *status_out) {
+    const bool fixed = pcv49 || ppm49;
     if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
         return GS_E_ARG;
     if (n_chains == 0) return GS_OK;
@@ -693,15 +759,37 @@ int gs_motif_sampling_batch(gs_ctx *c, int32_t W, double pc, double cutoff, cons
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
     if ((rc = batch_entry_checks(
-             c, "gs_motif_sampling_batch", W,
+             c, fixed ? "gs_motif_sampling_batch_fixed" : "gs_motif_sampling_batch", W,
              "every chain walks all targets in order (.fs:885-929): it needs all sequences on "
              "one device and no communicator",
-             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
-             "gs_motif_sampling)")))
+             fixed ? kFixedTwiceText
+                   : "a fixed PCV / PPM on the context is not batched (clear it and pass the "
+                     "values to gs_motif_sampling_batch_fixed, or loop "
+                     "gs_motif_sampling)")))
         return rc;
     takeover_reset(c);
+    FixedScope fx(c);
+    if ((rc = fx.set(pcv49, ppm49, W))) return rc;
     return motif_batch(c, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, pos_out,
                        pwms_out, passes_out, status_out);
+}
+
+int gs_motif_sampling_batch(gs_ctx *c, int32_t W, double pc, double cutoff, const uint64_t *seeds,
+                            int32_t n_chains, int32_t init_mode, int32_t max_passes,
+                            int32_t *pos_out, double *pwms_out, int32_t *passes_out,
+                            int32_t *status_out) {
+    return motif_sampling_batch_entry(c, W, pc, cutoff, nullptr, nullptr, seeds, n_chains,
+                                      init_mode, max_passes, pos_out, pwms_out, passes_out,
+                                      status_out);
+}
+
+int gs_motif_sampling_batch_fixed(gs_ctx *c, int32_t W, double pc, double cutoff,
+                                  const double *pcv49, const double *ppm49, const uint64_t *seeds,
+                                  int32_t n_chains, int32_t init_mode, int32_t max_passes,
+                                  int32_t *pos_out, double *pwms_out, int32_t *passes_out,
+                                  int32_t *status_out) {
+    return motif_sampling_batch_entry(c, W, pc, cutoff, pcv49, ppm49, seeds, n_chains, init_mode,
+                                      max_passes, pos_out, pwms_out, passes_out, status_out);
 }
 
 int gs_batch_last_ms(const gs_ctx *c, double out[2]) {
@@ -962,9 +1050,12 @@ int gs_site_sampling(gs_ctx *c, int32_t W, double pc, uint64_t seed, int32_t ini
     return site_download(c, pos_out, score_out);
 }
 
-int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t n_chains,
-                           int32_t init_mode, int32_t max_passes, int32_t *pos_out,
-                           double *score_out, int32_t *passes_out, int32_t *status_out) {
+// gs_site_sampling_batch (pcv49 and ppm49 null) and gs_site_sampling_batch_fixed.
+static int site_sampling_batch_entry(gs_ctx *c, int32_t W, double pc, const double *pcv49,
+                                     const double *ppm49, const uint64_t *seeds, int32_t n_chains,
+                                     int32_t init_mode, int32_t max_passes, int32_t *pos_out,
+                                     double *score_out, int32_t *passes_out, int32_t *status_out) {
+    const bool fixed = pcv49 || ppm49;
     if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
         return GS_E_ARG;
     if (n_chains == 0) return GS_OK;
@@ -972,15 +1063,34 @@ int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seed
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
     if ((rc = batch_entry_checks(
-             c, "gs_site_sampling_batch", W,
+             c, fixed ? "gs_site_sampling_batch_fixed" : "gs_site_sampling_batch", W,
              "getBestPWMSsWithStartPositions walks every target in order (.fs:554-585): it "
              "needs all sequences on one device and no communicator",
-             "the WithBPV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
-             "gs_site_sampling)")))
+             fixed ? kFixedTwiceText
+                   : "a fixed PCV / PPM on the context is not batched (clear it and pass the "
+                     "values to gs_site_sampling_batch_fixed, or loop "
+                     "gs_site_sampling)")))
         return rc;
     takeover_reset(c);
+    FixedScope fx(c);
+    if ((rc = fx.set(pcv49, ppm49, W))) return rc;
     return site_batch(c, W, pc, seeds, n_chains, init_mode, max_passes, pos_out, score_out,
                       passes_out, status_out);
+}
+
+int gs_site_sampling_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t n_chains,
+                           int32_t init_mode, int32_t max_passes, int32_t *pos_out,
+                           double *score_out, int32_t *passes_out, int32_t *status_out) {
+    return site_sampling_batch_entry(c, W, pc, nullptr, nullptr, seeds, n_chains, init_mode,
+                                     max_passes, pos_out, score_out, passes_out, status_out);
+}
+
+int gs_site_sampling_batch_fixed(gs_ctx *c, int32_t W, double pc, const double *pcv49,
+                                 const double *ppm49, const uint64_t *seeds, int32_t n_chains,
+                                 int32_t init_mode, int32_t max_passes, int32_t *pos_out,
+                                 double *score_out, int32_t *passes_out, int32_t *status_out) {
+    return site_sampling_batch_entry(c, W, pc, pcv49, ppm49, seeds, n_chains, init_mode,
+                                     max_passes, pos_out, score_out, passes_out, status_out);
 }
 
 int gs_site_batch_last_ms(const gs_ctx *c, double out[3]) {
@@ -989,11 +1099,15 @@ int gs_site_batch_last_ms(const gs_ctx *c, double out[3]) {
     return GS_OK;
 }
 
-int gs_motif_sampling_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
-                                  double cutoff, const uint64_t *seeds, int32_t n_chains,
-                                  int32_t init_mode, int32_t max_passes, int32_t cap,
-                                  int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
-                                  int32_t *passes_out, int32_t *status_out) {
+// gs_motif_sampling_multi_batch (pcv49 and ppm49 null) and gs_motif_sampling_multi_batch_fixed.
+static int motif_sampling_multi_batch_entry(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                            double cutoff, const double *pcv49,
+                                            const double *ppm49, const uint64_t *seeds,
+                                            int32_t n_chains, int32_t init_mode,
+                                            int32_t max_passes, int32_t cap, int32_t *cnt_out,
+                                            int32_t *pos_out, double *pwms_out,
+                                            int32_t *passes_out, int32_t *status_out) {
+    const bool fixed = pcv49 || ppm49;
     if (!c || n_chains < 0 || max_passes < 1 || (init_mode != 0 && init_mode != 1))
         return GS_E_ARG;
     if (motif_amount < 1 || motif_amount > kMultiMaxAmount || cap < motif_amount ||
@@ -1004,15 +1118,40 @@ int gs_motif_sampling_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, do
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     int rc;
     if ((rc = batch_entry_checks(
-             c, "gs_motif_sampling_multi_batch", W,
+             c, fixed ? "gs_motif_sampling_multi_batch_fixed" : "gs_motif_sampling_multi_batch", W,
              "every chain walks all targets in order (.fs:885-929): it needs all sequences on "
              "one device and no communicator",
-             "the ByPCV / OfPPM twins are not batched (clear the fixed PCV / PPM, or loop "
-             "gs_motif_sampling_multi)")))
+             fixed ? kFixedTwiceText
+                   : "a fixed PCV / PPM on the context is not batched (clear it and pass the "
+                     "values to gs_motif_sampling_multi_batch_fixed, or loop "
+                     "gs_motif_sampling_multi)")))
         return rc;
     takeover_reset(c);
+    FixedScope fx(c);
+    if ((rc = fx.set(pcv49, ppm49, W))) return rc;
     return multi_batch(c, motif_amount, W, pc, cutoff, seeds, n_chains, init_mode, max_passes, cap,
                        cnt_out, pos_out, pwms_out, passes_out, status_out);
+}
+
+int gs_motif_sampling_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                  double cutoff, const uint64_t *seeds, int32_t n_chains,
+                                  int32_t init_mode, int32_t max_passes, int32_t cap,
+                                  int32_t *cnt_out, int32_t *pos_out, double *pwms_out,
+                                  int32_t *passes_out, int32_t *status_out) {
+    return motif_sampling_multi_batch_entry(c, motif_amount, W, pc, cutoff, nullptr, nullptr, seeds,
+                                            n_chains, init_mode, max_passes, cap, cnt_out, pos_out,
+                                            pwms_out, passes_out, status_out);
+}
+
+int gs_motif_sampling_multi_batch_fixed(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                        double cutoff, const double *pcv49, const double *ppm49,
+                                        const uint64_t *seeds, int32_t n_chains, int32_t init_mode,
+                                        int32_t max_passes, int32_t cap, int32_t *cnt_out,
+                                        int32_t *pos_out, double *pwms_out, int32_t *passes_out,
+                                        int32_t *status_out) {
+    return motif_sampling_multi_batch_entry(c, motif_amount, W, pc, cutoff, pcv49, ppm49, seeds,
+                                            n_chains, init_mode, max_passes, cap, cnt_out, pos_out,
+                                            pwms_out, passes_out, status_out);
 }
 
 int gs_multi_batch_last_ms(const gs_ctx *c, double out[3]) {

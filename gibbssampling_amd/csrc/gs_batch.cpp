@@ -163,7 +163,8 @@ struct BatchStarts {
         R = n_chains;
         mode = init_mode;
         cells = c->A * W + c->A;
-        // (a fixed PCV / PPM applies as in starts_enqueue; the four drivers refuse both)
+        // (a fixed PCV / PPM applies as in starts_enqueue: the context's own for
+        // gs_random_starts_batch, the caller's arguments for the *_batch_fixed drivers)
         GS_TRY(starts_pass(c, mode, W, pc, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                            c->use_ppm ? c->d_ppm_fixed : nullptr, &sa, &lds));
         cpart_chain = mode == 0 ? c->n_global * c->A * W : 0;
@@ -365,6 +366,8 @@ struct StarSlabs {
         a.err_index = erri;
         a.exit_chunk = 0;
         a.exit_out = nullptr;
+        // (as greedy_run after the carve: the caller's PCV of the *_batch_fixed entry points)
+        a.pcv_fixed = c->use_pcv ? c->d_pcv_fixed : nullptr;
         HIP_TRY(c, gs_greedy_batch_launch(a, R, waves, (size_t)lds, c->stream, nullptr, nullptr));
         return GS_OK;
     }

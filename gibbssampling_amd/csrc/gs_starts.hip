@@ -492,8 +492,13 @@ gs_site_batch_agg_kernel(StartsArgs a, SiteBatchArgs b) {
 // `fst tmp > fst acc.[n]` (.fs:509, .fs:544) fused: a target's accept touches only its
 // own acc entry, every other target reads the pass-start aggregates and start vector.
 // a's per-chain pointers (agg, starts, score_out / pos_out = the acc, the error words)
-// name slab 0.
-__global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, SiteBatchArgs b) {
+// name slab 0.  BPV: under the caller's PCV (a.pcv_fixed: getLeft /
+// RightShiftedBestPWMSsWithBPV, .fs:318-378) the scan has no background, no drift and no
+// overflow, and the background prologue (compall, bg0, bsum) that nothing then reads is
+// skipped.  A compile-time choice, a kernel each: the plain batch's kernel keeps the
+// instruction stream it had before there was a branch for the PCV.
+template <bool BPV>
+__device__ __forceinline__ void site_batch_scan(StartsArgs a, SiteBatchArgs b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int64_t r = blockIdx.x / b.blocks;
     const int j0 = blockIdx.x - (int)r * b.blocks;
@@ -514,7 +519,7 @@ __global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, Si
     int32_t *comp = (int32_t *)(lds + a.o_comp);        // [128]
     uint8_t *sseq = (uint8_t *)(lds + a.o_seq);
 
-    for (int c = lane; c < a.cells; c += 64) {
+    for (int c = lane; c < (BPV ? AW : a.cells); c += 64) {
         int64_t s = 0;
 #pragma unroll
         for (int q = 0; q < kRepl; ++q) s += a.agg[(int64_t)q * a.stride + c];
@@ -524,7 +529,7 @@ __global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, Si
             compall[c - AW] = s;
     }
     __syncthreads();
-    if (lane < A) {
+    if (lane < A && !BPV) {
         int64_t s = 0;
         for (int j = 0; j < W; ++j) s += cg[lane * W + j];
         compall[lane] += s;
@@ -542,20 +547,22 @@ __global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, Si
         }
         __syncthreads();
         int64_t bsum = 0;
-        if (lane < A) {
-            int64_t s = 0;
-            for (int j = 0; j < W; ++j) s += cg[AW + lane * W + j];
-            const int64_t v = compall[lane] - comp[lane] - s;
-            bg0[lane] = v;
-            bsum = v;
+        if (!BPV) {
+            if (lane < A) {
+                int64_t s = 0;
+                for (int j = 0; j < W; ++j) s += cg[AW + lane * W + j];
+                const int64_t v = compall[lane] - comp[lane] - s;
+                bg0[lane] = v;
+                bsum = v;
+            }
+            bsum = wave_sum_i64(bsum);
         }
-        bsum = wave_sum_i64(bsum);
         __syncthreads();
         double best;
         int bestk;
         bool overflow;
-        best_pwms_scan(sseq, L, W, A, ppm, bg0, bsum, comp, Dt, a.pc, a.apc, nullptr, lane, best,
-                       bestk, overflow);
+        best_pwms_scan(sseq, L, W, A, ppm, bg0, bsum, comp, Dt, a.pc, a.apc,
+                       BPV ? a.pcv_fixed : nullptr, lane, best, bestk, overflow);
         if (overflow) {  // (.fs:117): this chain's error words, the chain ends alone
             if (lane == 0) {
                 atomicCAS(a.err_code, 0, 3);
@@ -572,6 +579,13 @@ __global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, Si
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(64) gs_site_batch_scan_kernel(StartsArgs a, SiteBatchArgs b) {
+    site_batch_scan<false>(a, b);
+}
+__global__ void __launch_bounds__(64) gs_site_batch_scan_bpv_kernel(StartsArgs a, SiteBatchArgs b) {
+    site_batch_scan<true>(a, b);
 }
 
 hipError_t gs_site_batch_ctl_launch(int32_t n_chains, int32_t pass, int32_t stage,
@@ -608,8 +622,8 @@ hipError_t gs_site_batch_pass_launch(const StartsArgs &a, size_t lds_bytes, int3
     hipLaunchKernelGGL(gs_site_batch_agg_kernel, dim3(n_chains * agg_blocks), dim3(256),
                        (size_t)a.A * (8 + 4 * a.W), s, a, b);
     b.blocks = scan_blocks;
-    hipLaunchKernelGGL(gs_site_batch_scan_kernel, dim3(n_chains * scan_blocks), dim3(64), lds_bytes,
-                       s, a, b);
+    hipLaunchKernelGGL(a.pcv_fixed ? gs_site_batch_scan_bpv_kernel : gs_site_batch_scan_kernel,
+                       dim3(n_chains * scan_blocks), dim3(64), lds_bytes, s, a, b);
     return hipGetLastError();
 }
 

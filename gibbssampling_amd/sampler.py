@@ -295,11 +295,18 @@ class MotifSampler:
                                                           pseudoCount: float, cutOff: float,
                                                           alphabet, sources, pcv,
                                                           seed: int | None = None,
-                                                          device: int = 0) -> list[MotifIndex]:
+                                                          device: int = 0,
+                                                          batch: bool = False) -> list[MotifIndex]:
         """Repetitions of getPWMOfRandomStartsWithBPV |> ByPCV sweep |> ByPCV greedy
-        (.fs:856-881); run r uses seed + r."""
-        ctx = _bind(alphabet, sources, device)
+        (.fs:856-881); run r uses seed + r.  batch=True computes every run
+        r = 0 … numberOfRepetitions in one Context.motif_sampling_batch(pcv=) call
+        (motif_sampling_multi_batch for motifAmount >= 2) and replays the same loop over
+        them: the same result, all runs paid for even when the loop stops early."""
         base = _seed(seed)
+        if batch:
+            return _batched_motif_twin(numberOfRepetitions, motifAmount, motifLength, pseudoCount,
+                                       cutOff, alphabet, sources, base, device, pcv=pcv)
+        ctx = _bind(alphabet, sources, device)
 
         def run(r):
             with _fixed(ctx, pcv=pcv):
@@ -320,15 +327,40 @@ class MotifSampler:
     def getBestPWMSsOfPPM(numberOfRepetitions: int, motifAmount: int, motifLength: int,
                           pseudoCount: float, cutOff: float, alphabet, sources,
                           positionProbabilityMatrix, seed: int | None = None,
-                          device: int = 0) -> list[MotifIndex]:
-        """Repetitions of doMotifSamplingWithPPM (.fs:1001-1026); run r uses seed + r."""
+                          device: int = 0, batch: bool = False) -> list[MotifIndex]:
+        """Repetitions of doMotifSamplingWithPPM (.fs:1001-1026); run r uses seed + r.
+        batch=True computes every run r = 0 … numberOfRepetitions in one
+        Context.motif_sampling_batch(ppm=) call (motif_sampling_multi_batch for
+        motifAmount >= 2) and replays the same loop over them: the same result, all runs
+        paid for even when the loop stops early."""
         base = _seed(seed)
+        if batch:
+            return _batched_motif_twin(numberOfRepetitions, motifAmount, motifLength, pseudoCount,
+                                       cutOff, alphabet, sources, base, device,
+                                       ppm=positionProbabilityMatrix)
         return _best_of_repetitions(
             numberOfRepetitions,
             lambda r: MotifSampler.doMotifSamplingWithPPM(
                 motifAmount, motifLength, pseudoCount, cutOff, alphabet, sources,
                 positionProbabilityMatrix, base + r, device),
             lambda xs: sum(x.PWMS for x in xs), [createMotifIndex(0.0, [])])
+
+
+def _batched_motif_twin(numberOfRepetitions, motifAmount, motifLength, pseudoCount, cutOff,
+                        alphabet, sources, base, device, pcv=None, ppm=None):
+    """The repetition loop of a ByPCV / OfPPM driver over runs 0 … numberOfRepetitions
+    computed by one batch call: Context.motif_sampling_batch for motifAmount = 1,
+    Context.motif_sampling_multi_batch (Positions lists) above."""
+    if not 1 <= motifAmount <= 16:
+        raise _native.ArgumentError(_native.GS_E_ARG, "motifAmount must be in [1, 16]")
+    ctx = _bind(alphabet, sources, device)
+    runs = _batched_runs if motifAmount == 1 else \
+        functools.partial(_batched_list_runs, motifAmount=motifAmount)
+    return _replay_repetitions(
+        numberOfRepetitions,
+        runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength, pseudoCount, cutOff, base, 0,
+             pcv=pcv, ppm=ppm),
+        lambda xs: sum(x.PWMS for x in xs), [createMotifIndex(0.0, [])])
 
 
 class _fixed:
@@ -423,13 +455,24 @@ def _seed(seed: int | None) -> int:
     return int(seed) & (2**64 - 1)
 
 
+def _fixed_kw(pcv, ppm) -> dict:
+    """The pcv= / ppm= keywords of a batch call of the twins (none for the plain drivers)."""
+    kw = {}
+    if pcv is not None:
+        kw["pcv"] = np.asarray(pcv, np.float64)
+    if ppm is not None:
+        kw["ppm"] = np.asarray(ppm, np.float64)
+    return kw
+
+
 def _batched_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
-                  init_mode: int) -> Callable[[int], list]:
+                  init_mode: int, pcv=None, ppm=None) -> Callable[[int], list]:
     """Runs r = 0 … count - 1 of doMotifSampling (seed base + r) by one batch call,
     as a run(r) lookup for _replay_repetitions.  A run that raised raises when the
-    loop asks for it, as the sequential loop would."""
+    loop asks for it, as the sequential loop would.  pcv / ppm: the ByPCV / WithPPM twin."""
     pos, pwms, _, status = ctx.motif_sampling_batch(
-        motifLength, pseudoCount, cutOff, [base + r for r in range(count)], init_mode, UNBOUNDED)
+        motifLength, pseudoCount, cutOff, [base + r for r in range(count)], init_mode, UNBOUNDED,
+        **_fixed_kw(pcv, ppm))
 
     def run(r: int) -> list:
         if status[r] != _native.GS_OK:
@@ -440,12 +483,13 @@ def _batched_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
 
 
 def _batched_list_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: int,
-                       init_mode: int, motifAmount: int) -> Callable[[int], list]:
+                       init_mode: int, motifAmount: int, pcv=None,
+                       ppm=None) -> Callable[[int], list]:
     """_batched_runs with Positions lists (motifAmount >= 2): one
     Context.motif_sampling_multi_batch call."""
     cnt, pos, pwms, _, status = ctx.motif_sampling_multi_batch(
         motifAmount, motifLength, pseudoCount, cutOff, [base + r for r in range(count)],
-        init_mode, UNBOUNDED)
+        init_mode, UNBOUNDED, **_fixed_kw(pcv, ppm))
 
     def run(r: int) -> list:
         if status[r] != _native.GS_OK:
@@ -456,12 +500,13 @@ def _batched_list_runs(ctx, count: int, motifLength, pseudoCount, cutOff, base: 
 
 
 def _batched_site_runs(ctx, count: int, motifLength, pseudoCount, base: int,
-                       init_mode: int) -> Callable[[int], list]:
+                       init_mode: int, pcv=None, ppm=None) -> Callable[[int], list]:
     """Runs r = 0 … count - 1 of doSiteSampling (seed base + r) by one batch call, as a
     run(r) lookup for _replay_repetitions.  A run that raised raises when the loop asks
-    for it, as the sequential loop would."""
+    for it, as the sequential loop would.  pcv / ppm: the WithBPV / WithPPM twin."""
     pos, score, _, status = ctx.site_sampling_batch(
-        motifLength, pseudoCount, [base + r for r in range(count)], init_mode, UNBOUNDED)
+        motifLength, pseudoCount, [base + r for r in range(count)], init_mode, UNBOUNDED,
+        **_fixed_kw(pcv, ppm))
 
     def run(r: int) -> list:
         if status[r] != _native.GS_OK:
@@ -645,9 +690,19 @@ class SiteSampler:
     def getMotifsWithBestInformationContentWithBPV(numberOfRepetitions: int, motifLength: int,
                                                    pseudoCount: float, alphabet, sources, pcv,
                                                    seed: int | None = None, init_mode: int = 0,
-                                                   device: int = 0):
-        """.fs:434-459; run r uses seed + r."""
+                                                   device: int = 0, batch: bool = False):
+        """.fs:434-459; run r uses seed + r.  batch=True computes every run
+        r = 0 … numberOfRepetitions in one Context.site_sampling_batch(pcv=) call and
+        replays the same loop over them: the same result, all runs paid for even when the
+        loop stops early."""
         base = _seed(seed)
+        if batch:
+            ctx = _bind(alphabet, sources, device)
+            return _replay_repetitions(
+                numberOfRepetitions,
+                _batched_site_runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength,
+                                   pseudoCount, base, init_mode, pcv=pcv),
+                lambda xs: sum(s for s, _ in xs), [(0.0, 0)])
         return _best_of_repetitions(
             numberOfRepetitions,
             lambda r: SiteSampler.doSiteSamplingWithBPV(motifLength, pseudoCount, alphabet,
@@ -679,9 +734,19 @@ class SiteSampler:
     def getBestInformationContentOfPPM(numberOfRepetitions: int, motifLength: int,
                                        pseudoCount: float, alphabet, sources,
                                        positionProbabilityMatrix, seed: int | None = None,
-                                       init_mode: int = 0, device: int = 0):
-        """.fs:664-689; run r uses seed + r."""
+                                       init_mode: int = 0, device: int = 0, batch: bool = False):
+        """.fs:664-689; run r uses seed + r.  batch=True computes every run
+        r = 0 … numberOfRepetitions in one Context.site_sampling_batch(ppm=) call and
+        replays the same loop over them: the same result, all runs paid for even when the
+        loop stops early."""
         base = _seed(seed)
+        if batch:
+            ctx = _bind(alphabet, sources, device)
+            return _replay_repetitions(
+                numberOfRepetitions,
+                _batched_site_runs(ctx, max(0, int(numberOfRepetitions)) + 1, motifLength,
+                                   pseudoCount, base, init_mode, ppm=positionProbabilityMatrix),
+                lambda xs: sum(s for s, _ in xs), [(0.0, 0)])
         return _best_of_repetitions(
             numberOfRepetitions,
             lambda r: SiteSampler.doSiteSamplingWithPPM(motifLength, pseudoCount, alphabet,

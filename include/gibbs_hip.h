@@ -351,6 +351,38 @@ int gs_best_pwms(gs_ctx *ctx, int32_t W, double pseudo_count, int32_t target,
  * / doSiteSamplingWithPPM (.fs:703-707). */
 int gs_set_fixed_pcv(gs_ctx *ctx, const double *pcv49);
 int gs_set_fixed_ppm(gs_ctx *ctx, const double *ppm49, int32_t W);
+/* The batched repetition drivers of the twins (findBestInormationContentContainingMotifsWithPCV
+ * .fs:856-881, getBestPWMSsOfPPM .fs:1001-1026, getMotifsWithBestInformationContentWithBPV
+ * .fs:434-459, getBestInformationContentOfPPM .fs:664-689): gs_motif_sampling_batch,
+ * gs_site_sampling_batch and gs_motif_sampling_multi_batch with the caller's pcv49 (49 slots)
+ * and / or ppm49 (49 slot rows x W) as arguments, either nullable.  Chain r is exactly
+ * gs_motif_sampling / gs_site_sampling / gs_motif_sampling_multi with seeds[r] on a context
+ * where gs_set_fixed_pcv(pcv49) and / or gs_set_fixed_ppm(ppm49, W) are set; both null is
+ * exactly the plain batch.  Outputs, per-chain status, return value, n_chains == 0 and the
+ * refusals are the sibling's (gs_batch_last_ms / gs_site_batch_last_ms /
+ * gs_multi_batch_last_ms / gs_multi_batch_last_info report the last call of either kind).
+ * GS_E_UNSUPPORTED also while the context itself holds a fixed PCV or PPM (one source of
+ * the values per call: clear it and pass the values as arguments).  The call leaves the
+ * context's own fixed state untouched: a later call on it computes what it would on a
+ * fresh context. */
+int gs_motif_sampling_batch_fixed(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+                                  const double *pcv49, const double *ppm49,
+                                  const uint64_t *seeds, int32_t n_chains, int32_t init_mode,
+                                  int32_t max_passes, int32_t *pos_out, double *pwms_out,
+                                  int32_t *passes_out, int32_t *status_out);
+int gs_site_sampling_batch_fixed(gs_ctx *ctx, int32_t W, double pseudo_count,
+                                 const double *pcv49, const double *ppm49,
+                                 const uint64_t *seeds, int32_t n_chains, int32_t init_mode,
+                                 int32_t max_passes, int32_t *pos_out, double *score_out,
+                                 int32_t *passes_out /* [n_chains][3], nullable */,
+                                 int32_t *status_out /* [n_chains], nullable */);
+int gs_motif_sampling_multi_batch_fixed(gs_ctx *ctx, int32_t motif_amount, int32_t W,
+                                        double pseudo_count, double cut_off, const double *pcv49,
+                                        const double *ppm49, const uint64_t *seeds,
+                                        int32_t n_chains, int32_t init_mode, int32_t max_passes,
+                                        int32_t cap, int32_t *cnt_out, int32_t *pos_out,
+                                        double *pwms_out, int32_t *passes_out,
+                                        int32_t *status_out);
 
 /* --- site sampler --------------------------------- */
 /* Site-sampler positions are (float*int)[] (.fs:589): a start in [0, L-W] and
