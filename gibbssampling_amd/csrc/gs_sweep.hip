@@ -680,6 +680,10 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(LP... lp, SweepArgs a) {
     // the one-iteration path stores its results itself)
     double *const wg_u = (double *)(lds + o_wave + w_res);
     (void)wg_u;
+    // ONE: the wavefronts' sticky-error words of the prologue's vote, [<= 4], after the
+    // uniforms' 16 slots
+    int32_t *const wg_vote = (int32_t *)(lds + o_wave + w_res + 128);
+    (void)wg_vote;
     int32_t *misc = (int32_t *)(wl + w_misc);
     // this lane's group slice
     unsigned char *gsl = wl + w_group + gi * a.group_bytes;
@@ -1084,7 +1088,22 @@ __global__ void GS_SWEEP_ATTR gs_sweep_kernel(LP... lp, SweepArgs a) {
     TLP(tl_w, 5);
     // an earlier sweep raised an error: its snapshot is void, nothing to do but the
     // done count (the whole workgroup decides together, at the prologue's barrier)
-    if (__syncthreads_or(err0 != 0)) {
+    // (ONE: the vote through the one barrier that publishes the workgroup tables, where the
+    // barrier reduction takes three and three LDS round trips.  err0 is wave-uniform, one
+    // address by one instruction: a lane of each wavefront stores it to the wavefront's own
+    // word of wg_vote, which nothing else writes from kernel start until every wavefront
+    // has read it (the finished tables' image ends at o_wave, before it).  Every wavefront
+    // derives the decision from the same LDS words, read after the same barrier: all take
+    // the same branch, and the error exit keeps its barrier count.)
+    bool void_snapshot;
+    if constexpr (ONE) {
+        if (lane == 0) wg_vote[wid] = err0;
+        __syncthreads();
+        void_snapshot = __ballot(lane < kWavesPerBlock && wg_vote[lane] != 0) != 0ull;
+    } else {
+        void_snapshot = __syncthreads_or(err0 != 0);
+    }
+    if (void_snapshot) {
         sweep_epilogue<WM, EK, ONE ? kOneArgsOff : 0>(a, lds, (int *)(lds + o_wave), tid);
         return;
     }
