@@ -7,11 +7,11 @@ hand-written HIP kernels behind the C ABI in include/gibbs_hip.h.
 from . import bioarray
 from ._native import (ArgumentError, ChecksumOverflowError, Context, DeviceError, GibbsError,
                       RouletteOverrunError, load_library)
-from .sampler import MotifIndex, MotifSampler, SiteSampler, createMotifIndex
+from .sampler import ChainStats, MotifIndex, MotifSampler, SiteSampler, createMotifIndex
 
 __all__ = [
-    "bioarray", "Context", "load_library", "MotifIndex", "MotifSampler", "SiteSampler",
-    "createMotifIndex", "GibbsError", "ArgumentError", "RouletteOverrunError",
+    "bioarray", "Context", "load_library", "ChainStats", "MotifIndex", "MotifSampler",
+    "SiteSampler", "createMotifIndex", "GibbsError", "ArgumentError", "RouletteOverrunError",
     "ChecksumOverflowError", "DeviceError",
 ]
 __version__ = "0.1.0"

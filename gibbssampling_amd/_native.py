@@ -164,6 +164,10 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_motif_run_batch": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, vp, vp,
                                          vp]),
         "gs_run_batch_last_ms": (C.c_int, [vp, vp]),
+        "gs_occupancy_size": (i64, [vp, i32]),
+        "gs_occupancy_offsets": (C.c_int, [vp, i32, vp]),
+        "gs_motif_run_batch_stats": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, i32,
+                                               i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
                                                vp, vp, vp, vp, vp]),
         "gs_motif_run_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, u64, i64, i32, vp, vp, vp]),
@@ -559,9 +563,74 @@ class Context:
             self._check(st)
         return pos, pwms, status
 
+    def occupancy_offsets(self, W: int) -> np.ndarray:
+        """Bins of one chain's occupancy histogram for motif length W, off[N + 1]: sequence
+        n owns off[n] .. off[n + 1] - 1, bin off[n] counts Positions [], bin off[n] + 1 + k
+        start k; off[N] is the histogram's length H."""
+        if int(self.lib.gs_occupancy_size(self.h, int(W))) < 0:
+            raise ArgumentError(GS_E_ARG, "occupancy_offsets: a bad motifLength, or no sequences")
+        off = np.zeros(self.n_local + 1, np.int64)
+        self._check(self.lib.gs_occupancy_offsets(self.h, int(W), _ptr(off)))
+        return off
+
+    def motif_run_batch_stats(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds,
+                              pos=None, init_mode: int = 0, first_sweep: int = 0, u=None,
+                              burn_in: int = 0, thin: int = 1, occupancy: bool = True,
+                              ic: bool = True, best: bool = True, strict: bool = False):
+        """motif_run_batch with statistics of the chains' sweeps, gathered on the device
+        with no host wait -> (pos[R, N], pwms[R, N], status[R], stats).  Sweep t counts when
+        t >= burn_in and (t - burn_in) % thin == 0.  stats is a dict of the parts asked for:
+        "occupancy"[R, H] (the counted sweeps whose state has its sequence at that bin,
+        occupancy_offsets) with "offsets"[N + 1]; "ic"[R, n_counted], the sum of the PWMS of
+        each counted sweep in the fixed order of sampler.informationContent; "best_sweep"[R]
+        (first_sweep + t of the first largest ic, -1: none), "best_pos"[R, N] and
+        "best_pwms"[R, N].  A chain that raises in sweep t contributes nothing from t on
+        (its ic entries are NaN).  With no part asked for this is motif_run_batch."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R, T = len(seeds), int(n_sweeps)
+        if pos is not None:
+            init_mode = -1
+            pos = np.array(pos, dtype=np.int32, copy=True)
+            if pos.shape != (R, self.n_local):
+                raise ArgumentError(GS_E_ARG, "pos needs one row per seed, one entry per sequence")
+        else:
+            if init_mode not in (0, 1):
+                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
+            pos = np.full((R, self.n_local), -1, np.int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (R, max(T, 0), self.n_local):
+                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        burn_in, thin = int(burn_in), int(thin)
+        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
+        ok = 0 <= burn_in <= T and thin >= 1
+        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        stats = {}
+        if occupancy:
+            H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
+        if ic:
+            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(R, -1, np.int64)
+            stats["best_pos"] = np.full((R, self.n_local), -1, np.int32)
+            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        st = self.lib.gs_motif_run_batch_stats(
+            self.h, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
+            int(init_mode), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms), _ptr(status),
+            _ptr(stats.get("occupancy")), _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        return pos, pwms, status, stats
+
     def run_batch_last_ms(self):
-        """Device milliseconds of the last motif_run_batch: (starts and their aggregates,
-        sweeps)."""
+        """Device milliseconds of the last motif_run_batch or motif_run_batch_stats: (starts
+        and their aggregates, sweeps with the statistics launches)."""
         out = np.zeros(2, np.float64)
         self._check(self.lib.gs_run_batch_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])

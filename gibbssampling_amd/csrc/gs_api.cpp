@@ -50,6 +50,8 @@ const gs_tuning_field kTuningFields[] = {
     GS_TUNING_FIELD(multi_batch_fill, v >= 1 && v <= 4096),
     GS_TUNING_FIELD(run_batch_clear, v == 0 || v == 1),
     GS_TUNING_FIELD(run_batch_blocks, v >= 1 && v <= 32),
+    GS_TUNING_FIELD(run_stats_blocks, v >= 0 && v <= 1024),
+    GS_TUNING_FIELD(run_stats_atomic, v == 0 || v == 1),
     GS_TUNING_FIELD(run_multi_arena_max, v >= 2048 && v <= (double)(1 << 28)),
     GS_TUNING_FIELD(batch_starts, v == -1 || v == 0 || v == 1),
     GS_TUNING_FIELD(greedy_switch, v >= 0 && v <= 1e9),
@@ -1166,12 +1168,19 @@ int gs_multi_batch_last_info(const gs_ctx *c, int32_t out[4]) {
     return GS_OK;
 }
 
-int gs_motif_run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
-                       const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
-                       int32_t init_mode, const double *u, int32_t *pos_inout, double *pwms_out,
-                       int32_t *status_out) {
+// gs_motif_run_batch (st null) and gs_motif_run_batch_stats.
+static int motif_run_batch_entry(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                                 const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                                 int32_t init_mode, const double *u, int32_t *pos_inout,
+                                 double *pwms_out, int32_t *status_out, const RunStats *st) {
     if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
         return GS_E_ARG;
+    if (st && (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
+               (st->best_sweep_out != nullptr) != (st->best_pos_out && st->best_pwms_out) ||
+               (!st->best_sweep_out && (st->best_pos_out || st->best_pwms_out))))
+        return fail(c, GS_E_ARG,
+                    "gs_motif_run_batch_stats: burn_in outside [0, n_sweeps], thin < 1, or "
+                    "best_sweep_out without both best rows (or the reverse)");
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
@@ -1188,7 +1197,35 @@ int gs_motif_run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     takeover_reset(c);
     return run_batch(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep, init_mode, u,
-                     pos_inout, pwms_out, status_out);
+                     pos_inout, pwms_out, status_out, st);
+}
+
+int gs_motif_run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                       const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                       int32_t init_mode, const double *u, int32_t *pos_inout, double *pwms_out,
+                       int32_t *status_out) {
+    return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
+                                 init_mode, u, pos_inout, pwms_out, status_out, nullptr);
+}
+
+int64_t gs_occupancy_size(const gs_ctx *c, int32_t W) {
+    return c ? occupancy_offsets(c, W, nullptr) : -1;
+}
+
+int gs_occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off) {
+    if (!c || !off) return GS_E_ARG;
+    return occupancy_offsets(c, W, off) < 0 ? GS_E_ARG : GS_OK;
+}
+
+int gs_motif_run_batch_stats(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                             const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                             int32_t init_mode, const double *u, int32_t burn_in, int32_t thin,
+                             int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+                             int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
+                             int32_t *best_pos_out, double *best_pwms_out) {
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
+    return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
+                                 init_mode, u, pos_inout, pwms_out, status_out, &st);
 }
 
 int gs_run_batch_last_ms(const gs_ctx *c, double out[2]) {

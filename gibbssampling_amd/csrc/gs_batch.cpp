@@ -1,6 +1,7 @@
 // gs_batch.cpp — the host drivers of the batched entry points:
 // motif_batch (gs_motif_sampling_batch), site_batch (gs_site_sampling_batch), multi_batch
-// (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch), run_multi_batch
+// (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch and, with the chains'
+// statistics, gs_motif_run_batch_stats, §9.25), run_multi_batch
 // (gs_motif_run_multi_batch) and starts_batch (gs_random_starts_batch), over one copy of the
 // stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
 // (set_snapshot_dev, starts_enqueue, starts_pass, greedy_carve, one_sweep) are in
@@ -863,13 +864,33 @@ int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const
 // rows rotating over three buffers (the next one zeroed by a memset before the sweep that
 // fills it, or by the sweep before: tune.run_batch_clear).  One synchronisation, one
 // download.  The caller validated the arguments.
+//
+// With statistics (gs_motif_run_batch_stats) every counted sweep writes its
+// PWMS as the last one does and is followed on the stream by one launch of
+// gs_run_batch_stats_kernel, which reads the rows and skip words that sweep left; the
+// chains' histograms, traces and best states come down with the rows.
 int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
               int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
-              double *pwms_out, int32_t *status_out) {
+              double *pwms_out, int32_t *status_out, const RunStats *stats) {
     const int64_t n = c->n_local;
     c->run_batch_ms[0] = c->run_batch_ms[1] = 0.0;
     if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
-    if (n == 0) return GS_OK;
+    if (stats && !stats->any()) stats = nullptr;
+    const auto counted = [&](int32_t t) {
+        return stats && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
+    };
+    const int64_t n_counted =
+        stats && stats->burn_in < T ? ((int64_t)T - stats->burn_in + stats->thin - 1) / stats->thin : 0;
+    if (n == 0) {  // no sequences: no bins, and no counted sweep completes
+        if (stats && stats->ic_out)
+            std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
+        if (stats && stats->best_sweep_out)
+            std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
+        return GS_OK;
+    }
+    const int64_t H = stats ? occupancy_offsets(c, W, nullptr) : 0;
+    const bool st_occ = stats && stats->occ_out, st_ic = stats && stats->ic_out,
+               st_best = stats && stats->best_sweep_out;
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
     GS_TRY(multi_lds_check(c, lds));
@@ -888,7 +909,10 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         c, "gs_motif_run_batch",
         (int64_t)R * (n * (8 + 8 + (mode == 1 ? 4 : 0)) + 3 * 8 * ((int64_t)cells + 1) + 8 + 8 +
                       (int64_t)sizeof(SpecCtl)) +
-            n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax));
+            n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax +
+            // the statistics: bins and their offsets, the trace, the running best and its rows
+            (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) + (st_ic ? R * n_counted * 8 : 0) +
+            (st_best ? (int64_t)R * (16 + n * 12) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     GS_TRY(multi_scratch(c, a, grid, 0));
     // the slabs (row r = chain r)
@@ -914,6 +938,45 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     }
     HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
     for (auto &q : b_agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
+    // the statistics' slabs: zero bins, no best yet (-1); every counted sweep's launch
+    // writes its own trace entry of every chain
+    DevBuf<int32_t> s_occ, s_bpos;
+    DevBuf<int64_t> s_off, s_bsweep;
+    DevBuf<double> s_ic, s_bic, s_bpwms;
+    std::vector<int64_t> h_off;  // alive for the upload
+    RunStatsArgs sa{};
+    sa.n_chains = R;
+    sa.n_local = (int32_t)n;
+    sa.atomic = c->tune.run_stats_atomic;
+    sa.H = H;
+    sa.ic_stride = n_counted;
+    if (st_occ) {
+        h_off.resize((size_t)n + 1);
+        occupancy_offsets(c, W, h_off.data());
+        GS_TRY(s_off.alloc(c, n + 1));
+        GS_TRY(s_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
+        HIP_TRY(c, hipMemcpyAsync(s_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_occ, 0, (size_t)R * H * 4, c->stream));
+        sa.off = s_off;
+        sa.occ = s_occ;
+    }
+    if (st_ic && n_counted > 0) GS_TRY(s_ic.alloc(c, R * n_counted));
+    if (st_best) {
+        GS_TRY(s_bsweep.alloc(c, R));
+        GS_TRY(s_bic.alloc(c, R));
+        GS_TRY(s_bpos.alloc(c, rows));
+        GS_TRY(s_bpwms.alloc(c, rows));
+        HIP_TRY(c, hipMemsetAsync(s_bsweep, 0xff, (size_t)R * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bic, 0, (size_t)R * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bpos, 0, (size_t)rows * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bpwms, 0, (size_t)rows * 8, c->stream));
+        sa.best_sweep = s_bsweep;
+        sa.best_ic = s_bic;
+        sa.best_pos = s_bpos;
+        sa.best_pwms = s_bpwms;
+    }
+    const int sblocks = c->tune.run_stats_blocks > 0 ? c->tune.run_stats_blocks : agg_blocks(c, n, R);
     RunBatchArgs ba{};
     ba.n_chains = R;
     ba.cells = cells;
@@ -970,13 +1033,22 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
                 HIP_TRY(c, hipMemsetAsync(b_agg[nxt], 0, (size_t)agg_elems * 8, c->stream));
             ba.pos_in = b_pos[t & 1];
             ba.pos_out = b_pos[(t + 1) & 1];
-            ba.pwms_out = t == T - 1 ? b_pwms.p : nullptr;
+            const bool count = counted(t);
+            ba.pwms_out = t == T - 1 || (count && (st_ic || st_best)) ? b_pwms.p : nullptr;
             ba.agg_in = b_agg[cur];
             ba.agg_out = b_agg[nxt];
             ba.agg_clear = clear_in_kernel && t >= 1 ? b_agg[aft].p : nullptr;
             ba.u = b_u ? b_u + (int64_t)t * n : nullptr;
             a.stream = stream_sweep((uint64_t)(first_sweep + t));
             HIP_TRY(c, gs_run_batch_sweep_launch(a, ba, (int)grid, (size_t)lds, c->stream));
+            if (count) {  // the consumer of this sweep's state, before the next sweep's launch
+                sa.skip = b_agg[nxt] + (int64_t)R * cells;
+                sa.pos = b_pos[(t + 1) & 1];
+                sa.pwms = b_pwms;
+                sa.ic = s_ic ? s_ic + (t - stats->burn_in) / stats->thin : nullptr;
+                sa.sweep = first_sweep + t;
+                HIP_TRY(c, gs_run_batch_stats_launch(sa, sblocks, c->stream));
+            }
         }
         HIP_TRY(c, ev.mark());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -997,8 +1069,32 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
                                   c->stream));
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    const auto down = [&](void *dst, const void *src, int64_t bytes) -> hipError_t {
+        return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
+                         : hipSuccess;
+    };
+    if (st_occ) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
+    if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
+    if (st_best) {
+        HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
+        HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * 4));
+        HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
+    }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return report_chain_errors(c, herr, status_out, nullptr);
+}
+
+// Bins of one chain's occupancy histogram (gs_occupancy_offsets): off[n + 1] = off[n] + 1 +
+// (L_n - W + 1), off nullable.  The total H, or -1 for a bad W or no sequences.
+int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off) {
+    if (!c->d_seq || c->n_local <= 0 || W < 1 || W > 64 || c->Lmin < W) return -1;
+    int64_t h = 0;
+    for (int64_t i = 0; i < c->n_local; ++i) {
+        if (off) off[i] = h;
+        h += 1 + (c->h_len[(size_t)i] - W + 1);
+    }
+    if (off) off[c->n_local] = h;
+    return h;
 }
 
 // R independent chains of T synchronous sweeps with Positions lists (any motifAmount),

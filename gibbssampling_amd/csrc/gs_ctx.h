@@ -53,6 +53,8 @@ struct gs_tuning {
     int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
     int32_t run_batch_clear = 1;  // chain batch: the next aggregate rows zeroed by a memset before each sweep (0) or a third row cleared in-kernel (1: 1 - 3 % faster at 200 and 2 000 sequences)
     int32_t run_batch_blocks = 32;  // chain batch: cap on the one-wavefront workgroups per CU of its sweep launches (8 / 16 / 32, i.e. what fits: 18.1 / 12.6 / 11.3 ms for 64 chains x 200 sweeps x 200 sequences)
+    int32_t run_stats_blocks = 0;  // chain statistics (gs_motif_run_batch_stats): workgroups per chain of a counted sweep's launch, 0 = 256 targets each while the GPU is four deep over all chains (10 000 sequences x 8 chains x 200 sweeps: one workgroup a chain 135.6 - 145.8 against 130.7 ms of sweeps); the results do not depend on it
+    int32_t run_stats_atomic = 1;  // ... and its bins by non-returning atomic adds (1) or plain read-modify-write (0): both race-free, no difference measured; the results do not depend on it
     int32_t run_multi_arena_max = 1 << 28;  // list chain batch (gs_motif_run_multi_batch): the categories a target's levels 1 .. M - 1 may take (kArenaMax) before its chain is given up with GS_E_UNSUPPORTED; tests lower it to reach that branch with small arenas.  The one field a chain's status can depend on
     int32_t batch_starts = -1;  // batch drivers: the chains' starts chain after chain on the single-chain state (0), all chains in the launches of gs_random_starts_batch (1), or -1: the latter while a chain has fewer targets than a launch has workgroups (8 a CU), the size range where it measured faster; the results do not depend on it
     int32_t greedy_switch = 16;  // star greedy -> speculative passes once a pass moves < N / it targets (0 never)
@@ -185,6 +187,27 @@ hipError_t gs_run_batch_agg_launch(const MultiArgs &a, const RunBatchArgs &b, in
 hipError_t gs_run_batch_sweep_launch(const MultiArgs &a, const RunBatchArgs &b, int grid, size_t lds,
                                      hipStream_t s);
 hipError_t gs_run_batch_occupancy(int *blocks_per_cu, size_t lds);
+// One counted sweep of gs_motif_run_batch_stats for gs_run_batch_stats_kernel
+// (gs_chainstats.hip): the rows and skip words that sweep's launch left,
+// the chains' histograms, this sweep's column of the trace, the running best.
+struct RunStatsArgs {
+    int32_t n_chains, n_local;
+    int32_t atomic;              // bins by non-returning atomic adds (1) or read-modify-write (0)
+    const int64_t *skip;         // [R]: the skip words of the sweep's agg_out
+    const int32_t *pos;          // [R][n_local]: the snapshot the sweep wrote
+    const double *pwms;          // [R][n_local]: its PWMS (read only with ic or best_sweep)
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets
+    int64_t H;                   // off[n_local]
+    int32_t *occ;                // [R][H], or null
+    double *ic;                  // the sweep's entry of chain 0's trace, or null
+    int64_t ic_stride;           // n_counted
+    int64_t sweep;               // first_sweep + t
+    double *best_ic;             // [R]
+    int64_t *best_sweep;         // [R]: -1 until a counted sweep completed; null: no best state
+    int32_t *best_pos;           // [R][n_local]
+    double *best_pwms;           // [R][n_local]
+};
+hipError_t gs_run_batch_stats_launch(const RunStatsArgs &a, int blocks_per_chain, hipStream_t s);
 // What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
 // of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
 // names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
@@ -548,9 +571,22 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
 int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const uint64_t *seeds,
                 int32_t R, int32_t mode, int32_t max_passes, int32_t cap, int32_t *cnt_out,
                 int32_t *pos_out, double *pwms_out, int32_t *passes_out, int32_t *status_out);
+// The caller's side of gs_motif_run_batch_stats: which sweeps count and where the chains'
+// statistics go (each nullable; the best rows go with best_sweep_out).
+struct RunStats {
+    int32_t burn_in, thin;
+    int32_t *occ_out;
+    double *ic_out;
+    int64_t *best_sweep_out;
+    int32_t *best_pos_out;
+    double *best_pwms_out;
+    bool any() const { return occ_out || ic_out || best_sweep_out; }
+};
+// (stats null, or with no output: gs_motif_run_batch)
 int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
               int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
-              double *pwms_out, int32_t *status_out);
+              double *pwms_out, int32_t *status_out, const RunStats *stats = nullptr);
+int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off);
 int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
                  double *score_out, int32_t *pos_out, int32_t *status_out);
 int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,

@@ -100,6 +100,78 @@ def _single_positions(motifMem: Sequence[MotifIndex]) -> np.ndarray:
     return pos
 
 
+def informationContent(pwms) -> float:
+    """The sum of a state's PWMS (the reference's quality of a run, .fs:981-989) in the
+    fixed binary64 order of the device's trace (gs_motif_run_batch_stats): 64 partial sums
+    v[l] from +0.0, v[l] adding the entries n = l, l + 64, ... in increasing n; then for
+    s = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + s] for l < s; the result is v[0]."""
+    x = np.ascontiguousarray(pwms, np.float64).ravel()
+    # (padded with +0.0: a partial sum that started from +0.0 is never -0.0, so adding
+    # +0.0 changes no bit)
+    pad = np.zeros((-len(x)) % 64, np.float64)
+    v = np.zeros(64, np.float64)
+    for row in np.concatenate([x, pad]).reshape(-1, 64):
+        v = v + row
+    s = 32
+    while s >= 1:
+        v[:s] = v[:s] + v[s:2 * s]
+        s //= 2
+    return float(v[0])
+
+
+@dataclass
+class ChainStats:
+    """What MotifSampler.runSweepsBatchedStats gathered over the counted sweeps of R chains.
+    occupancy[R, H]: the counted sweeps whose state has its sequence at that bin; sequence n
+    owns the bins offsets[n] .. offsets[n + 1] - 1, the first one counting Positions [], bin
+    offsets[n] + 1 + k start k.  ic[R, n_counted]: informationContent of every counted
+    sweep (NaN from the sweep in which a chain raised).  best_sweep[R] and best[R]: the
+    sweep of each chain's first largest ic (-1: none) and its state."""
+    occupancy: np.ndarray
+    offsets: np.ndarray
+    ic: np.ndarray
+    best_sweep: np.ndarray
+    best: list
+
+    def finished(self) -> np.ndarray:
+        """[R] bool: the chains every counted sweep of which was counted (a chain that
+        raised stops counting in that sweep)."""
+        off = self.offsets
+        if len(off) < 2:
+            return np.ones(len(self.occupancy), bool)
+        return self.occupancy[:, off[0]:off[1]].sum(axis=1) == self.ic.shape[1]
+
+    def marginals(self, pool: bool = True) -> list:
+        """Per sequence the occupancy of its bins divided by the counted sweeps: pooled
+        over the finished chains (one array of 1 + L_n - W + 1 frequencies a sequence), or
+        with pool=False chain by chain ([R, bins] a sequence, each chain over its own
+        counted sweeps).  Without any counted state the frequencies are 0."""
+        occ = np.asarray(self.occupancy, np.float64)
+        off = self.offsets
+        if pool:
+            keep = self.finished()
+            total = occ[keep].sum(axis=0)
+            den = float(keep.sum() * self.ic.shape[1])
+            total = total / den if den > 0 else np.zeros_like(total)
+            return [total[off[n]:off[n + 1]] for n in range(len(off) - 1)]
+        out = []
+        for n in range(len(off) - 1):
+            part = occ[:, off[n]:off[n + 1]]
+            den = part.sum(axis=1, keepdims=True)
+            out.append(np.divide(part, den, out=np.zeros_like(part), where=den > 0))
+        return out
+
+    def mode(self) -> list[MotifIndex]:
+        """Each sequence's most frequent pooled bin, the first one among equals (the
+        .fsx's countBy |> sortByDescending |> head, per site), as a MotifIndex whose PWMS
+        field carries that bin's pooled frequency."""
+        out = []
+        for m in self.marginals(pool=True):
+            k = int(np.argmax(m))  # the first maximum
+            out.append(createMotifIndex(m[k], [] if k == 0 else [k - 1]))
+        return out
+
+
 class MotifSampler:
     """MotifSampler module (.fs:709-1038): the hot-path entry points."""
 
@@ -174,6 +246,44 @@ class MotifSampler:
                                                 pos, init_mode, first_sweep)
         _raise_failed_chain(status)
         return [_motif_indices(pos[r], pwms[r]) for r in range(len(seeds))]
+
+    @staticmethod
+    def runSweepsBatchedStats(motifLength: int, pseudoCount: float, cutOff: float, alphabet,
+                              sources, sweeps: int, seeds, motifMems=None, init_mode: int = 0,
+                              first_sweep: int = 0, burn_in: int = 0, thin: int = 1,
+                              device: int = 0, motifAmount: int = 1):
+        """runSweepsBatched with the statistics a chain is run for, gathered on the device
+        in the same single call (Context.motif_run_batch_stats) -> (chains, ChainStats):
+        the occupancy of every motif start over the counted sweeps (t >= burn_in, every
+        thin-th), the trace of informationContent, and the best state each chain visited.
+        motifAmount 1 with single positions only."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if motifAmount != 1:
+            raise _native.ArgumentError(_native.GS_E_ARG,
+                                        "the chain statistics need motifAmount = 1")
+        pos = None
+        if motifMems is not None:
+            if len(motifMems) != len(seeds):
+                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+            if any(len(m) != len(sources) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "a motifMem and sources differ in length")
+            if not all(_is_single(1, m) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "the chain statistics need single positions")
+            pos = np.array([_single_positions(m) for m in motifMems],
+                           np.int32).reshape(len(seeds), len(sources))
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, status, st = ctx.motif_run_batch_stats(
+            motifLength, pseudoCount, cutOff, sweeps, seeds, pos, init_mode, first_sweep,
+            burn_in=burn_in, thin=thin)
+        _raise_failed_chain(status)
+        R = len(seeds)
+        best = [_motif_indices(st["best_pos"][r], st["best_pwms"][r]) if st["best_sweep"][r] >= 0
+                else [] for r in range(R)]
+        stats = ChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)), st["ic"],
+                           st["best_sweep"], best)
+        return [_motif_indices(pos[r], pwms[r]) for r in range(R)], stats
 
     @staticmethod
     def findBestMotifIndicesWithStartPositions(motifAmount: int, motifLength: int,

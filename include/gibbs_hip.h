@@ -238,8 +238,50 @@ int gs_motif_run_batch(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_o
                        int32_t *pos_inout,   /* [n_chains][n_local], -1 = Positions []   */
                        double *pwms_out,     /* [n_chains][n_local]                      */
                        int32_t *status_out   /* [n_chains], nullable                     */);
-/* Device times of the last gs_motif_run_batch, ms: starts (and first aggregates), sweeps. */
+/* Device times of the last gs_motif_run_batch or gs_motif_run_batch_stats, ms: starts (and
+ * first aggregates), sweeps (the statistics launches included). */
 int gs_run_batch_last_ms(const gs_ctx *ctx, double out[2]);
+
+/* Bins of one chain's occupancy histogram for motif length W: sequence n owns
+ * off[n] .. off[n+1]-1 with off[0] = 0, off[n+1] = off[n] + 1 + (L_n - W + 1);
+ * bin off[n] counts Positions [], bin off[n] + 1 + k counts start k. */
+int64_t gs_occupancy_size(const gs_ctx *ctx, int32_t W);              /* H, -1 on a bad W / no sequences */
+int gs_occupancy_offsets(const gs_ctx *ctx, int32_t W, int64_t *off); /* [n_local + 1] */
+
+/* gs_motif_run_batch with statistics of the chains' sweeps, gathered on the device with no
+ * host wait (no reference counterpart; the .fsx tallies whole runs on the host, .fsx:384-388).
+ * The chains, pos_inout, pwms_out, status_out, the return value, n_chains == 0, n_sweeps == 0
+ * and every refusal are exactly those of gs_motif_run_batch with the same leading arguments;
+ * with all three statistics null the call is that call, bit for bit.  Sweep t, 0 <= t <
+ * n_sweeps, is counted when t >= burn_in and (t - burn_in) % thin == 0; n_counted is their
+ * number; the state of a counted sweep is the snapshot that sweep wrote (the starts are never
+ * counted).  occ_out[r][b]: the number of counted sweeps whose state has its sequence at bin b
+ * (gs_occupancy_offsets); for a chain that finishes every sequence's bins sum to n_counted.
+ * ic_out[r][i]: the sum over the sequences of the PWMS of the i-th counted sweep (the
+ * reference's quality of a run, .fs:981-989), in binary64 in one fixed order: 64 partial sums
+ * v[l], each from +0.0, v[l] adding the PWMS of n = l, l + 64, ... in increasing n; then for
+ * s = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + s] for l < s; the result is v[0].  best_*: the
+ * counted sweep with the largest ic, a later one replacing it only when strictly larger
+ * (.fs:989); the first counted sweep is always taken and a NaN never replaces anything.
+ * best_sweep_out[r] is the absolute sweep number first_sweep + t, or -1 when no counted sweep
+ * completed (the two rows are then unspecified); the rows are that sweep's positions and PWMS,
+ * bit for bit.  A chain that raises in sweep t contributes nothing from sweep t on: its bins
+ * hold the counted sweeps before t, its ic entries from t on are quiet NaN, its best is the
+ * best before t; the other chains are untouched.  The outputs are written, not accumulated: a
+ * continued call (init_mode -1, first_sweep advanced) yields its own counts and the caller
+ * adds them.  GS_E_ARG before any launch, besides gs_motif_run_batch's: burn_in outside [0,
+ * n_sweeps], thin < 1, best_sweep_out without both best rows or the reverse.  The bins (n_chains
+ * x H x 4 bytes), the trace and the best rows count toward the 4 GiB of chain slabs. */
+int gs_motif_run_batch_stats(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+        int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+        int32_t init_mode, const double *u,
+        int32_t burn_in, int32_t thin,
+        int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+        int32_t *occ_out,        /* [n_chains][H], nullable            */
+        double  *ic_out,         /* [n_chains][n_counted], nullable    */
+        int64_t *best_sweep_out, /* [n_chains], nullable               */
+        int32_t *best_pos_out,   /* [n_chains][n_local]                */
+        double  *best_pwms_out   /* [n_chains][n_local]                */);
 
 /* R independent chains of n_sweeps synchronous sweeps each with Positions lists (any
  * motifAmount) in one call: chain r is exactly n_sweeps calls of gs_motif_sweep_multi(ctx,
@@ -512,6 +554,9 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * greedy_exit_ratio, greedy_waves, multi_greedy_threads, multi_spec_slots, multi_batch_fill,
  * run_batch_clear (gs_motif_run_batch: 0 a memset of the next aggregate rows before each
  * sweep, 1 a third row cleared in-kernel), run_batch_blocks (its workgroups per CU),
+ * run_stats_blocks (gs_motif_run_batch_stats: workgroups per chain of a counted sweep's
+ * statistics launch, 0 automatic), run_stats_atomic (its bins by atomic adds, 1, or plain
+ * read-modify-write, 0),
  * run_multi_arena_max (gs_motif_run_multi_batch: the combinations of up to motif_amount - 1
  * windows a target may have before its chain gets GS_E_UNSUPPORTED, 2048 .. 2^28, default
  * 2^28; for tests of that status, and the one field a chain's status depends on),
