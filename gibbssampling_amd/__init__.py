@@ -7,10 +7,12 @@ hand-written HIP kernels behind the C ABI in include/gibbs_hip.h.
 from . import bioarray
 from ._native import (ArgumentError, ChecksumOverflowError, Context, DeviceError, GibbsError,
                       RouletteOverrunError, load_library)
-from .sampler import ChainStats, MotifIndex, MotifSampler, SiteSampler, createMotifIndex
+from .sampler import (ChainStats, ListChainStats, MotifIndex, MotifSampler, SiteSampler,
+                      createMotifIndex)
 
 __all__ = [
-    "bioarray", "Context", "load_library", "ChainStats", "MotifIndex", "MotifSampler",
+    "bioarray", "Context", "load_library", "ChainStats", "ListChainStats", "MotifIndex",
+    "MotifSampler",
     "SiteSampler", "createMotifIndex", "GibbsError", "ArgumentError", "RouletteOverrunError",
     "ChecksumOverflowError", "DeviceError",
 ]

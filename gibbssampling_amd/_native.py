@@ -170,6 +170,9 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
                                                i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
                                                vp, vp, vp, vp, vp]),
+        "gs_motif_run_multi_batch_stats": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32,
+                                                     i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp, vp, vp]),
         "gs_motif_run_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, u64, i64, i32, vp, vp, vp]),
         "gs_run_multi_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_run_multi_batch_last_info": (C.c_int, [vp, vp]),
@@ -635,18 +638,9 @@ class Context:
         self._check(self.lib.gs_run_batch_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
 
-    def motif_run_multi_batch(self, motif_amount: int, W: int, pc: float, cutoff: float,
-                              n_sweeps: int, seeds, cnt=None, pos=None, init_mode: int = 0,
-                              first_sweep: int = 0, cap: int | None = None, u=None,
-                              strict: bool = False):
-        """R independent chains of n_sweeps sweeps with Positions lists (any motifAmount) in
-        one call, row r exactly n_sweeps motif_sweep_multi calls, each fed the previous
-        output, with the counter RNG's uniforms of seeds[r] -> (cnt[R, N], pos[R, N, cap],
-        pwms[R, N], status[R]).  The starts are the lists (cnt[R, N], pos[R, N, cap]; implies
-        init_mode -1) or those of random_starts(W, pc, seeds[r], init_mode) as one-position
-        lists.  u[R, n_sweeps, N] replaces the uniforms.  pwms is unspecified for n_sweeps =
-        0.  A chain that raises (status[r] != 0) leaves the other rows valid; errors of the
-        call itself raise, and with strict=True so does a chain's."""
+    def _run_multi_batch_args(self, motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u):
+        """The chains' seeds, lists and uniforms as the library takes them (motif_run_multi_batch
+        and motif_run_multi_batch_stats) -> (seeds, cnt, pos, init_mode, cap, u)."""
         cap = int(cap or motif_amount)
         seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
         R = len(seeds)
@@ -668,6 +662,23 @@ class Context:
             u = np.ascontiguousarray(u, dtype=np.float64)
             if u.shape != (R, max(int(n_sweeps), 0), self.n_local):
                 raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        return seeds, cnt, pos, init_mode, cap, u
+
+    def motif_run_multi_batch(self, motif_amount: int, W: int, pc: float, cutoff: float,
+                              n_sweeps: int, seeds, cnt=None, pos=None, init_mode: int = 0,
+                              first_sweep: int = 0, cap: int | None = None, u=None,
+                              strict: bool = False):
+        """R independent chains of n_sweeps sweeps with Positions lists (any motifAmount) in
+        one call, row r exactly n_sweeps motif_sweep_multi calls, each fed the previous
+        output, with the counter RNG's uniforms of seeds[r] -> (cnt[R, N], pos[R, N, cap],
+        pwms[R, N], status[R]).  The starts are the lists (cnt[R, N], pos[R, N, cap]; implies
+        init_mode -1) or those of random_starts(W, pc, seeds[r], init_mode) as one-position
+        lists.  u[R, n_sweeps, N] replaces the uniforms.  pwms is unspecified for n_sweeps =
+        0.  A chain that raises (status[r] != 0) leaves the other rows valid; errors of the
+        call itself raise, and with strict=True so does a chain's."""
+        seeds, cnt, pos, init_mode, cap, u = self._run_multi_batch_args(
+            motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u)
+        R = len(seeds)
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
         st = self.lib.gs_motif_run_multi_batch(
@@ -677,6 +688,57 @@ class Context:
         if st != GS_OK and (strict or not status.any()):
             self._check(st)
         return cnt, pos, pwms, status
+
+    def motif_run_multi_batch_stats(self, motif_amount: int, W: int, pc: float, cutoff: float,
+                                    n_sweeps: int, seeds, cnt=None, pos=None, init_mode: int = 0,
+                                    first_sweep: int = 0, cap: int | None = None, u=None,
+                                    burn_in: int = 0, thin: int = 1, occupancy: bool = True,
+                                    sites: bool = True, ic: bool = True, best: bool = True,
+                                    strict: bool = False):
+        """motif_run_multi_batch with statistics of the chains' sweeps, gathered on the device
+        with no host wait between sweeps -> (cnt[R, N], pos[R, N, cap], pwms[R, N], status[R],
+        stats).  Sweep t counts when t >= burn_in and (t - burn_in) % thin == 0.  stats is a
+        dict of the parts asked for: "occupancy"[R, H] with "offsets"[N + 1] (bin off[n]: the
+        counted sweeps whose list of sequence n is empty, bin off[n] + 1 + k: those whose list
+        contains start k); "sites"[R, N, motif_amount + 1] (the counted sweeps whose list of
+        sequence n has that length); "ic"[R, n_counted], the sum of the PWMS of each counted
+        sweep in the fixed order of sampler.informationContent; "best_sweep"[R] (first_sweep +
+        t of the first largest ic, -1: none), "best_cnt"[R, N], "best_pos"[R, N, cap] and
+        "best_pwms"[R, N].  A chain that raises in sweep t contributes nothing from t on (its
+        ic entries are NaN).  With no part asked for this is motif_run_multi_batch."""
+        seeds, cnt, pos, init_mode, cap, u = self._run_multi_batch_args(
+            motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u)
+        R, T, M = len(seeds), int(n_sweeps), int(motif_amount)
+        burn_in, thin = int(burn_in), int(thin)
+        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
+        ok = 0 <= burn_in <= T and thin >= 1
+        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        stats = {}
+        if occupancy:
+            H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
+        if sites:
+            stats["sites"] = np.zeros((R, self.n_local, max(M, 0) + 1), np.int32)
+        if ic:
+            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(R, -1, np.int64)
+            stats["best_cnt"] = np.zeros((R, self.n_local), np.int32)
+            stats["best_pos"] = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
+            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        st = self.lib.gs_motif_run_multi_batch_stats(
+            self.h, M, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
+            int(init_mode), cap, _ptr(u), burn_in, thin, _ptr(cnt), _ptr(pos), _ptr(pwms),
+            _ptr(status), _ptr(stats.get("occupancy")), _ptr(stats.get("sites")),
+            _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")), _ptr(stats.get("best_cnt")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        return cnt, pos, pwms, status, stats
 
     def motif_run_multi(self, motif_amount: int, W: int, pc: float, cutoff: float, n_sweeps: int,
                         seed: int, cnt, pos, first_sweep: int = 0, cap: int | None = None):
@@ -692,14 +754,15 @@ class Context:
         return cnt, pos, pwms
 
     def run_multi_batch_last_ms(self):
-        """Device milliseconds of the last motif_run_multi_batch: (starts and their
-        aggregates, sweeps)."""
+        """Device milliseconds of the last motif_run_multi_batch or
+        motif_run_multi_batch_stats: (starts and their aggregates, sweeps with the statistics
+        launches)."""
         out = np.zeros(2, np.float64)
         self._check(self.lib.gs_run_multi_batch_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
 
     def run_multi_batch_last_info(self) -> dict:
-        """Overflow handling of the last motif_run_multi_batch: pairs rescored by overflow
+        """Overflow handling of the last motif_run_multi_batch(_stats): pairs rescored by overflow
         launches, chains parked, resume rounds, the first arena's capacity."""
         out = np.zeros(4, np.int32)
         self._check(self.lib.gs_run_multi_batch_last_info(self.h, _ptr(out)))

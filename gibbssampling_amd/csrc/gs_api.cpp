@@ -1235,16 +1235,27 @@ int gs_run_batch_last_ms(const gs_ctx *c, double out[2]) {
     return GS_OK;
 }
 
-int gs_motif_run_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,
-                             int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains,
-                             int64_t first_sweep, int32_t init_mode, int32_t cap, const double *u,
-                             int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
-                             int32_t *status_out) {
+// gs_motif_run_multi_batch (st null) and gs_motif_run_multi_batch_stats.
+static int motif_run_multi_batch_entry(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                       double cutoff, int32_t n_sweeps, const uint64_t *seeds,
+                                       int32_t n_chains, int64_t first_sweep, int32_t init_mode,
+                                       int32_t cap, const double *u, int32_t *cnt_inout,
+                                       int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+                                       const RunMultiStats *st) {
     if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
         return GS_E_ARG;
     if (motif_amount < 1 || motif_amount > kMultiMaxAmount || cap < motif_amount ||
         cap > kMultiMaxAmount)
         return fail(c, GS_E_ARG, "motifAmount / list capacity out of range");
+    if (st) {
+        const bool rows = st->best_cnt_out && st->best_pos_out && st->best_pwms_out;
+        const bool any_row = st->best_cnt_out || st->best_pos_out || st->best_pwms_out;
+        if (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
+            (st->best_sweep_out != nullptr) != rows || (!st->best_sweep_out && any_row))
+            return fail(c, GS_E_ARG,
+                        "gs_motif_run_multi_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
+                        "or best_sweep_out without all three best rows (or the reverse)");
+    }
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!cnt_inout || !pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
@@ -1263,7 +1274,32 @@ int gs_motif_run_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double 
     drop_ftab(c);  // (the sweep chain's handed-over tables: gs_ctx.h d_ftab)
     takeover_reset(c);
     return run_multi_batch(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
-                           init_mode, cap, u, cnt_inout, pos_inout, pwms_out, status_out);
+                           init_mode, cap, u, cnt_inout, pos_inout, pwms_out, status_out, st);
+}
+
+int gs_motif_run_multi_batch(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,
+                             int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains,
+                             int64_t first_sweep, int32_t init_mode, int32_t cap, const double *u,
+                             int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
+                             int32_t *status_out) {
+    return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
+                                       first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
+                                       pwms_out, status_out, nullptr);
+}
+
+int gs_motif_run_multi_batch_stats(gs_ctx *c, int32_t motif_amount, int32_t W, double pc,
+                                   double cutoff, int32_t n_sweeps, const uint64_t *seeds,
+                                   int32_t n_chains, int64_t first_sweep, int32_t init_mode,
+                                   int32_t cap, const double *u, int32_t burn_in, int32_t thin,
+                                   int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
+                                   int32_t *status_out, int32_t *occ_out, int32_t *sites_out,
+                                   double *ic_out, int64_t *best_sweep_out, int32_t *best_cnt_out,
+                                   int32_t *best_pos_out, double *best_pwms_out) {
+    const RunMultiStats st{burn_in,        thin,         occ_out,      sites_out,    ic_out,
+                           best_sweep_out, best_cnt_out, best_pos_out, best_pwms_out};
+    return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
+                                       first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
+                                       pwms_out, status_out, &st);
 }
 
 int gs_motif_run_multi(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,

@@ -2,7 +2,8 @@
 // motif_batch (gs_motif_sampling_batch), site_batch (gs_site_sampling_batch), multi_batch
 // (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch and, with the chains'
 // statistics, gs_motif_run_batch_stats, §9.25), run_multi_batch
-// (gs_motif_run_multi_batch) and starts_batch (gs_random_starts_batch), over one copy of the
+// (gs_motif_run_multi_batch and, with statistics, gs_motif_run_multi_batch_stats, §9.26) and
+// starts_batch (gs_random_starts_batch), over one copy of the
 // stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
 // (set_snapshot_dev, starts_enqueue, starts_pass, greedy_carve, one_sweep) are in
 // gs_engine.cpp.
@@ -1107,15 +1108,37 @@ int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off) {
 // overflowed the larger arena as well and parked its chain at sweep t, a further round runs
 // the chains parked at t from their intact snapshot of sweep t with the next arena size up,
 // their aggregates rebuilt from the lists.  One download.  The caller validated the arguments.
+//
+// With statistics (gs_motif_run_multi_batch_stats) every counted sweep's
+// launches write their PWMS as the last sweep's do, and one launch of
+// gs_run_multi_batch_stats_kernel over the round's chains follows them on the stream; the
+// bins, site counts, trace and running best live for the whole call, so a parked chain's
+// counted sweeps before t come from the round that parked it and those from t on from the
+// round that resumes it.
 int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
                     const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
                     const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
-                    int32_t *status_out) {
+                    int32_t *status_out, const RunMultiStats *stats) {
     const int64_t n = c->n_local;
     c->run_multi_batch_ms[0] = c->run_multi_batch_ms[1] = 0.0;
     for (int i = 0; i < 4; ++i) c->run_multi_batch_info[i] = 0;
     if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
-    if (n == 0) return GS_OK;
+    if (stats && !stats->any()) stats = nullptr;
+    const auto counted = [&](int32_t t) {
+        return stats && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
+    };
+    const int64_t n_counted =
+        stats && stats->burn_in < T ? ((int64_t)T - stats->burn_in + stats->thin - 1) / stats->thin : 0;
+    if (n == 0) {  // no sequences: no bins, and no counted sweep completes
+        if (stats && stats->ic_out)
+            std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
+        if (stats && stats->best_sweep_out)
+            std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
+        return GS_OK;
+    }
+    const bool st_occ = stats && stats->occ_out, st_sites = stats && stats->sites_out,
+               st_ic = stats && stats->ic_out, st_best = stats && stats->best_sweep_out;
+    const int64_t H = st_occ ? occupancy_offsets(c, W, nullptr) : 0;
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, false);
     // (the kernel stages its pick in static LDS beside the carve: both have to fit)
@@ -1162,7 +1185,12 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         (int64_t)R * (n * (2 * (4 + 4 * (int64_t)cap) + 8 + (mode == 1 ? 4 : 0)) +
                       3 * 8 * ((int64_t)cells + 1) + 8 + 4 + 8 + (int64_t)sizeof(SpecCtl) + 4) +
             (ovf_elems + novf_elems) * 4 + u_elems * 8 + cpart_bytes +
-            scratch_bytes(rows, arena0)));
+            scratch_bytes(rows, arena0) +
+            // the statistics: bins and their offsets, site counts, the trace, the running
+            // best and its rows
+            (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) +
+            (st_sites ? rows * ((int64_t)M + 1) * 4 : 0) + (st_ic ? R * n_counted * 8 : 0) +
+            (st_best ? (int64_t)R * 16 + rows * (4 + 4 * (int64_t)cap + 8) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     {  // the first round's arenas, so that no sweep waits for an allocation
         MultiArgs sized = a;
@@ -1197,6 +1225,53 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
     }
     HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(b_park, 0xff, (size_t)R * 4, c->stream));
+    // the statistics' slabs, cleared here once for all rounds: zero bins and site counts, no
+    // best yet (-1, empty lists); the first round's launches write every chain's trace entries
+    DevBuf<int32_t> s_occ, s_sites, s_bcnt, s_bpos;
+    DevBuf<int64_t> s_off, s_bsweep;
+    DevBuf<double> s_ic, s_bic, s_bpwms;
+    std::vector<int64_t> h_off;  // alive for the upload
+    RunMultiStatsArgs sa{};
+    sa.n_local = (int32_t)n;
+    sa.cap = cap;
+    sa.M = M;
+    sa.atomic = c->tune.run_stats_atomic;
+    sa.H = H;
+    sa.ic_stride = n_counted;
+    if (st_occ) {
+        h_off.resize((size_t)n + 1);
+        occupancy_offsets(c, W, h_off.data());
+        GS_TRY(s_off.alloc(c, n + 1));
+        GS_TRY(s_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
+        HIP_TRY(c, hipMemcpyAsync(s_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_occ, 0, (size_t)R * H * 4, c->stream));
+        sa.off = s_off;
+        sa.occ = s_occ;
+    }
+    if (st_sites) {
+        GS_TRY(s_sites.alloc(c, rows * (M + 1)));
+        HIP_TRY(c, hipMemsetAsync(s_sites, 0, (size_t)(rows * (M + 1)) * 4, c->stream));
+        sa.sites = s_sites;
+    }
+    if (st_ic && n_counted > 0) GS_TRY(s_ic.alloc(c, R * n_counted));
+    if (st_best) {
+        GS_TRY(s_bsweep.alloc(c, R));
+        GS_TRY(s_bic.alloc(c, R));
+        GS_TRY(s_bcnt.alloc(c, rows));
+        GS_TRY(s_bpos.alloc(c, rows * cap));
+        GS_TRY(s_bpwms.alloc(c, rows));
+        HIP_TRY(c, hipMemsetAsync(s_bsweep, 0xff, (size_t)R * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bic, 0, (size_t)R * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bcnt, 0, (size_t)rows * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bpos, 0xff, (size_t)(rows * cap) * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(s_bpwms, 0, (size_t)rows * 8, c->stream));
+        sa.best_sweep = s_bsweep;
+        sa.best_ic = s_bic;
+        sa.best_cnt = s_bcnt;
+        sa.best_pos = s_bpos;
+        sa.best_pwms = s_bpwms;
+    }
     RunMultiBatchArgs ba{};
     ba.cells = cells;
     ba.n_all = R;
@@ -1258,7 +1333,7 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
                 m->pos_in = b_pos[t & 1];
                 m->cnt_out = b_cnt[(t + 1) & 1];
                 m->pos_out = b_pos[(t + 1) & 1];
-                m->pwms_out = t == T - 1 ? b_pwms.p : nullptr;
+                m->pwms_out = t == T - 1 || (counted(t) && (st_ic || st_best)) ? b_pwms.p : nullptr;
                 m->stream = stream_sweep((uint64_t)(first_sweep + t));
             }
             ba.sweep = t;
@@ -1281,6 +1356,20 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
                 bo.ovf_list = bo.ovf_count = nullptr;
                 HIP_TRY(c, gs_run_multi_batch_sweep_launch(ao, bo, (int)ogrid, (size_t)lds,
                                                            c->stream));
+            }
+            if (counted(t)) {  // the consumer of this sweep's state, before the next sweep's launch
+                sa.n_chains = nc;
+                sa.chains = ba.chains;
+                sa.skip = b_agg[nxt] + (int64_t)R * cells;
+                sa.cnt = b_cnt[(t + 1) & 1];
+                sa.pos = b_pos[(t + 1) & 1];
+                sa.pwms = b_pwms;
+                sa.ic = s_ic ? s_ic + (t - stats->burn_in) / stats->thin : nullptr;
+                sa.sweep = first_sweep + t;
+                const int sblocks = c->tune.run_stats_blocks > 0
+                                        ? c->tune.run_stats_blocks
+                                        : agg_blocks(c, n * cap, nc);
+                HIP_TRY(c, gs_run_multi_batch_stats_launch(sa, sblocks, c->stream));
             }
         }
         return GS_OK;
@@ -1383,6 +1472,19 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
                                   c->stream));
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    const auto down = [&](void *dst, const void *src, int64_t bytes) -> hipError_t {
+        return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
+                         : hipSuccess;
+    };
+    if (st_occ) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
+    if (st_sites) HIP_TRY(c, down(stats->sites_out, s_sites, rows * (M + 1) * 4));
+    if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
+    if (st_best) {
+        HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
+        HIP_TRY(c, down(stats->best_cnt_out, s_bcnt, rows * 4));
+        HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * cap * 4));
+        HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
+    }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int32_t r = 0; r < R; ++r)
         if (given_up[(size_t)r])

@@ -1,25 +1,77 @@
-// gs_chainstats.hip — the device-side consumer of a chain batch's sweeps
-// (gs_motif_run_batch_stats): per counted sweep one launch, stream-ordered
-// right after that sweep's gs_run_batch_sweep_kernel, which left the chains' positions and
-// PWMS rows and their skip words.
+// gs_chainstats.hip — the device-side consumers of a chain batch's sweeps
+// (gs_motif_run_batch_stats, DESIGN.md §9.25, and gs_motif_run_multi_batch_stats, §9.26): per
+// counted sweep one launch, stream-ordered right after that sweep's launches, which left the
+// chains' positions (or Positions lists) and PWMS rows and their skip words.
 #include "gs_ctx.h"
 #include "gs_wave.h"
 
+namespace {
+
+constexpr int kSumChunk = 2048;  // doubles of LDS a workgroup stages a PWMS row through
+
+// Workgroup 0 of a running chain, all 256 threads: the ordered sum of the chain's PWMS row
+// (the contract of both entry points' traces: 64 lane-strided serial sums from +0.0, lane l
+// adding n = l, l + 64, .. in increasing n, then the halving tree v[l] += v[l + s],
+// s = 32 .. 1), its trace entry, and the decision against the running best (the first counted
+// sweep is taken; later ones only when strictly larger, .fs:989; a NaN never wins).  Whether
+// this sweep became the chain's best, workgroup-uniform.
+__device__ __forceinline__ bool chain_sum_best(const double *pwms_row, int n_local, double *ic_entry,
+                                               int64_t *best_sweep, double *best_ic, int64_t sweep,
+                                               double *buf, int *win) {
+    const int tid = threadIdx.x;
+    if (tid == 0) *win = 0;
+    // the row through LDS, kSumChunk entries at a time (a multiple of 64: lane l keeps
+    // n = l mod 64): the whole workgroup's loads are in flight at once, and the
+    // serial adds of wavefront 0 wait on LDS only (10 000 targets: a launch measured
+    // 15 us against 40 with wavefront 0 reading global memory)
+    double v = 0.0;
+    for (int base = 0; base < n_local; base += kSumChunk) {
+        const int m = min(kSumChunk, n_local - base);
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) buf[i] = pwms_row[base + i];
+        __syncthreads();
+        if (tid < 64)
+            for (int i = tid; i < m; i += 64) v = v + buf[i];
+    }
+    if (tid < 64) {
+        for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
+        if (tid == 0) {
+            if (ic_entry) *ic_entry = v;
+            if (best_sweep && (*best_sweep < 0 || v > *best_ic)) {
+                *best_sweep = sweep;
+                *best_ic = v;
+                *win = 1;
+            }
+        }
+    }
+    __syncthreads();
+    return *win != 0;
+}
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// One to a bin that no other thread of the launch touches.
+__device__ __forceinline__ void bump(int32_t *bin, int atomic) {
+    if (atomic)
+        atomicAdd(bin, 1);
+    else
+        *bin += 1;
+}
+
+}  // namespace
+
 // gridDim.x / n_chains workgroups a chain.  A chain whose skip word is set contributes
 // nothing (its trace entry is a quiet NaN).  Workgroup 0 of a chain: wavefront 0 forms the
-// ordered sum of the PWMS row, which the workgroup stages through LDS (64 lane-strided serial
-// sums from +0.0, then the halving tree
-// v[l] += v[l + s], s = 32 .. 1), writes the trace entry and decides against the running
-// best (the first counted sweep is taken; later ones only when strictly larger, .fs:989; a
-// NaN never wins); on a win the whole workgroup copies the two rows into the best slabs.
+// ordered sum of the PWMS row, which the workgroup stages through LDS, writes the trace entry
+// and decides against the running best (chain_sum_best); on a win the whole workgroup copies
+// the two rows into the best slabs.
 // All workgroups: one to bin off[n] + 1 + pos[n] of the chain's histogram for their share
 // of the targets.  A chain's bins of one sweep are distinct and launches are stream-ordered,
 // so the plain read-modify-write (a.atomic == 0) and the non-returning atomic add race with
 // nothing; a position outside [-1, L - W] is not counted.
 extern "C" __global__ void __launch_bounds__(256)
 gs_run_batch_stats_kernel(RunStatsArgs a) {
-    constexpr int kChunk = 2048;
-    __shared__ double buf[kChunk];
+    __shared__ double buf[kSumChunk];
     __shared__ int win;
     const int tid = threadIdx.x;
     const int bpc = gridDim.x / a.n_chains;
@@ -28,51 +80,22 @@ gs_run_batch_stats_kernel(RunStatsArgs a) {
     const int64_t row = (int64_t)r * a.n_local;
     const bool sums = a.ic || a.best_sweep;
     if (blk == 0 && sums && skipped && tid == 0 && a.ic)
-        a.ic[(int64_t)r * a.ic_stride] = __longlong_as_double(0x7ff8000000000000ll);
+        a.ic[(int64_t)r * a.ic_stride] = quiet_nan();
     if (skipped) return;
-    if (blk == 0 && sums) {
-        if (tid == 0) win = 0;
-        // the row through LDS, kChunk entries at a time (a multiple of 64: lane l keeps
-        // n = l mod 64): the whole workgroup's loads are in flight at once, and the
-        // serial adds of wavefront 0 wait on LDS only (10 000 targets: a launch measured
-        // 15 us against 40 with wavefront 0 reading global memory)
-        double v = 0.0;
-        for (int base = 0; base < a.n_local; base += kChunk) {
-            const int m = min(kChunk, a.n_local - base);
-            __syncthreads();
-            for (int i = tid; i < m; i += 256) buf[i] = a.pwms[row + base + i];
-            __syncthreads();
-            if (tid < 64)
-                for (int i = tid; i < m; i += 64) v = v + buf[i];
+    if (blk == 0 && sums &&
+        chain_sum_best(a.pwms + row, a.n_local, a.ic ? a.ic + (int64_t)r * a.ic_stride : nullptr,
+                       a.best_sweep ? a.best_sweep + r : nullptr, a.best_ic + r, a.sweep, buf, &win))
+        for (int n = tid; n < a.n_local; n += 256) {
+            a.best_pos[row + n] = a.pos[row + n];
+            a.best_pwms[row + n] = a.pwms[row + n];
         }
-        if (tid < 64) {
-            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
-            if (tid == 0) {
-                if (a.ic) a.ic[(int64_t)r * a.ic_stride] = v;
-                if (a.best_sweep && (a.best_sweep[r] < 0 || v > a.best_ic[r])) {
-                    a.best_sweep[r] = a.sweep;
-                    a.best_ic[r] = v;
-                    win = 1;
-                }
-            }
-        }
-        __syncthreads();
-        if (win)
-            for (int n = tid; n < a.n_local; n += 256) {
-                a.best_pos[row + n] = a.pos[row + n];
-                a.best_pwms[row + n] = a.pwms[row + n];
-            }
-    }
     if (!a.occ) return;
     int32_t *occ = a.occ + (int64_t)r * a.H;
     for (int n = blk * 256 + tid; n < a.n_local; n += bpc * 256) {
         const int64_t o = a.off[n];
         const int64_t k = (int64_t)a.pos[row + n] + 1;
         if (k < 0 || k >= a.off[n + 1] - o) continue;
-        if (a.atomic)
-            atomicAdd(&occ[o + k], 1);
-        else
-            occ[o + k] += 1;
+        bump(&occ[o + k], a.atomic);
     }
 }
 
@@ -80,5 +103,64 @@ hipError_t gs_run_batch_stats_launch(const RunStatsArgs &a, int blocks_per_chain
     if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
     hipLaunchKernelGGL(gs_run_batch_stats_kernel, dim3(a.n_chains * blocks_per_chain), dim3(256), 0,
                        s, a);
+    return hipGetLastError();
+}
+
+// The same over Positions lists (gs_motif_run_multi_batch_stats), for the
+// chains of one round: gridDim.x / n_chains workgroups a launch index c, chain r = chains[c].
+// A chain whose skip word is set (it raised, or was parked, in this sweep or before)
+// contributes nothing; its trace entry is a quiet NaN, which the round that resumes a parked
+// chain overwrites.  Workgroup 0 of a chain: chain_sum_best, and on a win the cnt row, the
+// pos rows (flat over n_local * cap) and the PWMS row into the best slabs.  All workgroups,
+// one thread a (target, slot) pair of the flat list slab, so that a wavefront's reads of pos
+// are one coalesced load deep: slot 0 adds one to sites[n][cnt] and, for an empty list, to
+// bin off[n]; slot i < cnt one to bin off[n] + 1 + pos[i].  A sweep's list holds pairwise
+// distinct starts (.fs:727-742), so the bins one launch touches in one chain are distinct
+// and launches are stream-ordered: both kinds of add race with nothing.  A length outside
+// [0, M] and a start outside [0, L - W] are not counted: no store leaves the chain's slab.
+extern "C" __global__ void __launch_bounds__(256)
+gs_run_multi_batch_stats_kernel(RunMultiStatsArgs a) {
+    __shared__ double buf[kSumChunk];
+    __shared__ int win;
+    const int tid = threadIdx.x;
+    const int bpc = gridDim.x / a.n_chains;
+    const int c = blockIdx.x / bpc, blk = blockIdx.x - c * bpc;
+    const int r = a.chains ? a.chains[c] : c;
+    const int64_t row = (int64_t)r * a.n_local;
+    const int cap = a.cap, flat = a.n_local * cap;  // (the slabs' 4 GiB bound: < 2^30)
+    if (a.skip[r] != 0) {  // workgroup-uniform
+        if (blk == 0 && tid == 0 && a.ic) a.ic[(int64_t)r * a.ic_stride] = quiet_nan();
+        return;
+    }
+    if (blk == 0 && (a.ic || a.best_sweep) &&
+        chain_sum_best(a.pwms + row, a.n_local, a.ic ? a.ic + (int64_t)r * a.ic_stride : nullptr,
+                       a.best_sweep ? a.best_sweep + r : nullptr, a.best_ic + r, a.sweep, buf,
+                       &win)) {
+        for (int n = tid; n < a.n_local; n += 256) {
+            a.best_cnt[row + n] = a.cnt[row + n];
+            a.best_pwms[row + n] = a.pwms[row + n];
+        }
+        for (int x = tid; x < flat; x += 256) a.best_pos[row * cap + x] = a.pos[row * cap + x];
+    }
+    if (!a.occ && !a.sites) return;
+    int32_t *occ = a.occ ? a.occ + (int64_t)r * a.H : nullptr;
+    for (int x = blk * 256 + tid; x < flat; x += bpc * 256) {
+        const int n = x / cap, i = x - n * cap;
+        const int cnt = a.cnt[row + n];
+        if (cnt < 0 || cnt > a.M) continue;
+        if (i == 0 && a.sites) bump(&a.sites[(row + n) * (a.M + 1) + cnt], a.atomic);
+        if (!occ || (i > 0 && i >= cnt)) continue;
+        const int64_t o = a.off[n];
+        const int64_t k = cnt == 0 ? 0 : (int64_t)a.pos[row * cap + x] + 1;
+        if (k < (cnt == 0 ? 0 : 1) || k >= a.off[n + 1] - o) continue;
+        bump(&occ[o + k], a.atomic);
+    }
+}
+
+hipError_t gs_run_multi_batch_stats_launch(const RunMultiStatsArgs &a, int blocks_per_chain,
+                                           hipStream_t s) {
+    if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gs_run_multi_batch_stats_kernel, dim3(a.n_chains * blocks_per_chain),
+                       dim3(256), 0, s, a);
     return hipGetLastError();
 }

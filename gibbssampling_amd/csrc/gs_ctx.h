@@ -208,6 +208,34 @@ struct RunStatsArgs {
     double *best_pwms;           // [R][n_local]
 };
 hipError_t gs_run_batch_stats_launch(const RunStatsArgs &a, int blocks_per_chain, hipStream_t s);
+// The same for one counted sweep of gs_motif_run_multi_batch_stats
+// (gs_run_multi_batch_stats_kernel): the list slabs, PWMS rows and skip
+// words the sweep's launches left.  A launch runs over its `chains` only (a resumed round's:
+// the other chains' skip words are not theirs then); everything else is indexed by the chain.
+struct RunMultiStatsArgs {
+    int32_t n_chains, n_local;   // chains of this launch (entries of `chains`)
+    int32_t cap, M;              // the lists' capacity, motifAmount
+    int32_t atomic;              // as RunStatsArgs
+    const int32_t *chains;       // [n_chains]: the chain of every launch index, or null: itself
+    const int64_t *skip;         // [R]: the skip words of the sweep's agg_out
+    const int32_t *cnt;          // [R][n_local]: the snapshot the sweep wrote
+    const int32_t *pos;          // [R][n_local][cap]
+    const double *pwms;          // [R][n_local]: its PWMS (read only with ic or best_sweep)
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets (read only with occ)
+    int64_t H;                   // off[n_local]
+    int32_t *occ;                // [R][H], or null
+    int32_t *sites;              // [R][n_local][M + 1], or null
+    double *ic;                  // the sweep's entry of chain 0's trace, or null
+    int64_t ic_stride;           // n_counted
+    int64_t sweep;               // first_sweep + t
+    double *best_ic;             // [R]
+    int64_t *best_sweep;         // [R]: -1 until a counted sweep completed; null: no best state
+    int32_t *best_cnt;           // [R][n_local]
+    int32_t *best_pos;           // [R][n_local][cap]
+    double *best_pwms;           // [R][n_local]
+};
+hipError_t gs_run_multi_batch_stats_launch(const RunMultiStatsArgs &a, int blocks_per_chain,
+                                           hipStream_t s);
 // What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
 // of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
 // names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
@@ -589,9 +617,21 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
 int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off);
 int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
                  double *score_out, int32_t *pos_out, int32_t *status_out);
+// The caller's side of gs_motif_run_multi_batch_stats (each statistic nullable; the three
+// best rows go with best_sweep_out).
+struct RunMultiStats {
+    int32_t burn_in, thin;
+    int32_t *occ_out, *sites_out;
+    double *ic_out;
+    int64_t *best_sweep_out;
+    int32_t *best_cnt_out, *best_pos_out;
+    double *best_pwms_out;
+    bool any() const { return occ_out || sites_out || ic_out || best_sweep_out; }
+};
+// (stats null, or with no output: gs_motif_run_multi_batch)
 int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
                     const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
                     const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
-                    int32_t *status_out);
+                    int32_t *status_out, const RunMultiStats *stats = nullptr);
 
 }  // namespace gs_host

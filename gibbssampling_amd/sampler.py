@@ -172,6 +172,73 @@ class ChainStats:
         return out
 
 
+@dataclass
+class ListChainStats(ChainStats):
+    """What MotifSampler.runSweepsBatchedListStats gathered over the counted sweeps of R
+    chains of Positions lists: ChainStats, where bin offsets[n] counts the counted sweeps
+    whose list of sequence n is empty and bin offsets[n] + 1 + k those whose list contains
+    start k, and best[r] holds lists; sites[R, N, M + 1]: the counted sweeps whose list of
+    sequence n has 0 .. M positions.  motifLength is the W the chains ran with."""
+    sites: np.ndarray
+    motifLength: int
+
+    def finished(self) -> np.ndarray:
+        """[R] bool: the chains every counted sweep of which was counted: every sequence's
+        site counts sum to the number of counted sweeps (a chain that raised stops counting
+        in that sweep)."""
+        return (self.sites.sum(axis=2) == self.ic.shape[1]).all(axis=1)
+
+    def marginals(self, pool: bool = True) -> list:
+        """Per sequence its bins divided by the counted sweeps: pooled over the finished
+        chains (one array of 1 + L_n - W + 1 frequencies a sequence), or with pool=False
+        chain by chain ([R, bins] a sequence, each chain over the sweeps it counted).  A list
+        holds up to M starts, so bins 1.. sum to the mean number of sites of the sequence,
+        not to 1 minus the empty share.  Without any counted state the frequencies are 0."""
+        occ = np.asarray(self.occupancy, np.float64)
+        off = self.offsets
+        if pool:
+            return ChainStats.marginals(self, pool=True)
+        den = self.sites.sum(axis=2).astype(np.float64)  # [R, N]: the sweeps a chain counted
+        out = []
+        for n in range(len(off) - 1):
+            part, d = occ[:, off[n]:off[n + 1]], den[:, n:n + 1]
+            out.append(np.divide(part, d, out=np.zeros_like(part), where=d > 0))
+        return out
+
+    def siteCounts(self, pool: bool = True) -> list:
+        """Per sequence the frequencies of 0 .. M sites over the counted sweeps: pooled over
+        the finished chains (one array of M + 1 a sequence), or with pool=False chain by
+        chain ([R, M + 1] a sequence, each chain over the sweeps it counted)."""
+        sites = np.asarray(self.sites, np.float64)
+        if pool:
+            keep = self.finished()
+            total = sites[keep].sum(axis=0)
+            den = float(keep.sum() * self.ic.shape[1])
+            total = total / den if den > 0 else np.zeros_like(total)
+            return [total[n] for n in range(sites.shape[1])]
+        den = sites.sum(axis=2, keepdims=True)
+        freq = np.divide(sites, den, out=np.zeros_like(sites), where=den > 0)
+        return [freq[:, n] for n in range(sites.shape[1])]
+
+    def mode(self) -> list[MotifIndex]:
+        """Per sequence a MotifIndex list: the most frequent pooled site count c (the first
+        maximum), then the c most occupied pooled starts that are pairwise more than
+        motifLength apart (.fs:129-140), chosen greedily by descending frequency, the first
+        among equals; fewer when no further start is far enough from those taken.  Positions
+        are in ascending order; the PWMS field carries the pooled frequency of c sites."""
+        out = []
+        for m, s in zip(self.marginals(pool=True), self.siteCounts(pool=True)):
+            c = int(np.argmax(s))  # the first maximum
+            taken: list[int] = []
+            for k in np.argsort(-m[1:], kind="stable"):
+                if len(taken) == c:
+                    break
+                if all(abs(int(k) - q) > self.motifLength for q in taken):
+                    taken.append(int(k))
+            out.append(createMotifIndex(s[c], sorted(taken)))
+        return out
+
+
 class MotifSampler:
     """MotifSampler module (.fs:709-1038): the hot-path entry points."""
 
@@ -284,6 +351,36 @@ class MotifSampler:
         stats = ChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)), st["ic"],
                            st["best_sweep"], best)
         return [_motif_indices(pos[r], pwms[r]) for r in range(R)], stats
+
+    @staticmethod
+    def runSweepsBatchedListStats(motifLength: int, pseudoCount: float, cutOff: float, alphabet,
+                                  sources, sweeps: int, seeds, motifMems=None, init_mode: int = 0,
+                                  first_sweep: int = 0, burn_in: int = 0, thin: int = 1,
+                                  device: int = 0, motifAmount: int = 1):
+        """runSweepsBatchedStats for chains of Positions lists (any motifAmount), in one
+        Context.motif_run_multi_batch_stats call -> (chains, ListChainStats): the occupancy
+        of every motif start and the number of sites of every sequence over the counted
+        sweeps (t >= burn_in, every thin-th), the trace of informationContent, and the best
+        state each chain visited."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if motifMems is not None:
+            if len(motifMems) != len(seeds):
+                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+            if any(len(m) != len(sources) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "a motifMem and sources differ in length")
+        cap, cnt, pos = _chain_lists(motifAmount, motifMems, len(sources))
+        ctx = _bind(alphabet, sources, device)
+        cnt, pos, pwms, status, st = ctx.motif_run_multi_batch_stats(
+            motifAmount, motifLength, pseudoCount, cutOff, sweeps, seeds, cnt, pos, init_mode,
+            first_sweep, cap, burn_in=burn_in, thin=thin)
+        _raise_failed_chain(status)
+        R = len(seeds)
+        best = [_motif_lists(st["best_cnt"][r], st["best_pos"][r], st["best_pwms"][r])
+                if st["best_sweep"][r] >= 0 else [] for r in range(R)]
+        stats = ListChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)),
+                               st["ic"], st["best_sweep"], best, st["sites"], int(motifLength))
+        return [_motif_lists(cnt[r], pos[r], pwms[r]) for r in range(R)], stats
 
     @staticmethod
     def findBestMotifIndicesWithStartPositions(motifAmount: int, motifLength: int,
@@ -530,19 +627,25 @@ def _raise_failed_chain(status) -> None:
                 int(st), f"chain {r} of the batch failed")
 
 
+def _chain_lists(motifAmount, motifMems, n_sources):
+    """The chains' lists at one capacity (the longest list's, at least motifAmount) ->
+    (cap, cnt[R, N], pos[R, N, cap]); without motifMems (cap, None, None)."""
+    if motifMems is None:
+        return motifAmount, None, None
+    cap = max([motifAmount] + [_lists(motifAmount, m)[0] for m in motifMems])
+    cnt = np.zeros((len(motifMems), n_sources), np.int32)
+    pos = np.full((len(motifMems), n_sources, cap), -1, np.int32)
+    for r, mem in enumerate(motifMems):
+        c1, cnt[r], p1 = _lists(motifAmount, mem)
+        pos[r, :, :c1] = p1
+    return cap, cnt, pos
+
+
 def _run_lists_batched(motifAmount, motifLength, pseudoCount, cutOff, alphabet, sources, sweeps,
                        seeds, motifMems, init_mode, first_sweep, device):
     """runSweepsBatched on the Positions-list path: one Context.motif_run_multi_batch call,
     the chains' lists at one capacity (the longest list's, at least motifAmount)."""
-    cnt = pos = None
-    cap = motifAmount
-    if motifMems is not None:
-        cap = max([motifAmount] + [_lists(motifAmount, m)[0] for m in motifMems])
-        cnt = np.zeros((len(seeds), len(sources)), np.int32)
-        pos = np.full((len(seeds), len(sources), cap), -1, np.int32)
-        for r, mem in enumerate(motifMems):
-            c1, cnt[r], p1 = _lists(motifAmount, mem)
-            pos[r, :, :c1] = p1
+    cap, cnt, pos = _chain_lists(motifAmount, motifMems, len(sources))
     ctx = _bind(alphabet, sources, device)
     cnt, pos, pwms, status = ctx.motif_run_multi_batch(motifAmount, motifLength, pseudoCount,
                                                        cutOff, sweeps, seeds, cnt, pos, init_mode,

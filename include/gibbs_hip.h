@@ -321,8 +321,53 @@ int gs_motif_run_multi_batch(gs_ctx *ctx, int32_t motif_amount, int32_t W, doubl
 int gs_motif_run_multi(gs_ctx *ctx, int32_t motif_amount, int32_t W, double pseudo_count,
                        double cut_off, int32_t n_sweeps, uint64_t seed, int64_t first_sweep,
                        int32_t cap, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out);
-/* Device times of the last gs_motif_run_multi_batch, ms: starts (and first aggregates),
- * sweeps (resumed chains included). */
+/* gs_motif_run_multi_batch with statistics of the chains' sweeps, gathered on the device with
+ * no host wait between sweeps: gs_motif_run_batch_stats for Positions lists.  The chains, the
+ * lists, pwms_out, status_out, the return value, n_chains == 0, n_sweeps == 0 and every
+ * refusal are exactly those of gs_motif_run_multi_batch with the same leading arguments; with
+ * all four statistics null the call is that call, bit for bit.  Counting is
+ * gs_motif_run_batch_stats': sweep t counts when t >= burn_in and (t - burn_in) % thin == 0,
+ * the state of a counted sweep is the list snapshot that sweep wrote, the starts never count,
+ * and the outputs are written, not accumulated.
+ * occ_out[r][b], bins of gs_occupancy_offsets: bin off[n] counts the counted sweeps whose list
+ * of sequence n is empty, bin off[n] + 1 + k those whose list contains start k (a sweep's list
+ * holds pairwise distinct starts, .fs:727-742; a start outside [0, L - W] is not counted).
+ * sites_out[r][n][c], 0 <= c <= motif_amount: the counted sweeps whose list of sequence n has
+ * length c (a sweep never writes a longer list; a length outside that range is not counted).
+ * For a chain that finishes, with occ = occ_out[r] and s = sites_out[r][n]:
+ *   (1) s[0] + s[1] + ... + s[motif_amount] == n_counted;
+ *   (2) s[0] == occ[off[n]];
+ *   (3) 1 s[1] + 2 s[2] + ... + motif_amount s[motif_amount]
+ *         == occ[off[n] + 1] + ... + occ[off[n + 1] - 1].
+ * ic_out[r][i]: the sum over the sequences of the PWMS of the i-th counted sweep, in the fixed
+ * 64-lane order of gs_motif_run_batch_stats (the same contract).  best_*: the first counted
+ * sweep with the largest sum (a later one replaces it only when strictly larger, .fs:989; the
+ * first counted sweep is always taken; a NaN never wins).  best_sweep_out[r] is the absolute
+ * sweep number first_sweep + t, or -1 when no counted sweep completed (the three rows are then
+ * unspecified); the rows are that sweep's lists and PWMS, bit for bit.  A chain that raises in
+ * sweep t contributes nothing from t on: its bins and site counts hold the counted sweeps
+ * before t, its ic entries from t on are quiet NaN, its best is the best before t; the other
+ * chains are untouched.  A chain that is run again with larger arenas from the sweep it
+ * stopped in contributes every counted sweep exactly once; one given up there
+ * (GS_E_UNSUPPORTED in its status) keeps the statistics of the sweeps before that one.
+ * GS_E_ARG before any launch, besides gs_motif_run_multi_batch's: burn_in outside [0,
+ * n_sweeps], thin < 1, best_sweep_out without all three best rows or the reverse.  The bins,
+ * the site counts, the trace and the best rows count toward the 4 GiB of chain slabs. */
+int gs_motif_run_multi_batch_stats(gs_ctx *ctx, int32_t motif_amount, int32_t W,
+        double pseudo_count, double cut_off, int32_t n_sweeps, const uint64_t *seeds,
+        int32_t n_chains, int64_t first_sweep, int32_t init_mode, int32_t cap, const double *u,
+        int32_t burn_in, int32_t thin,
+        int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+        int32_t *occ_out,        /* [n_chains][H], nullable                          */
+        int32_t *sites_out,      /* [n_chains][n_local][motif_amount + 1], nullable  */
+        double  *ic_out,         /* [n_chains][n_counted], nullable                  */
+        int64_t *best_sweep_out, /* [n_chains], nullable                             */
+        int32_t *best_cnt_out,   /* [n_chains][n_local]                              */
+        int32_t *best_pos_out,   /* [n_chains][n_local][cap], F# list order, -1 past cnt */
+        double  *best_pwms_out   /* [n_chains][n_local]                              */);
+/* Device times of the last gs_motif_run_multi_batch or gs_motif_run_multi_batch_stats, ms:
+ * starts (and first aggregates), sweeps (resumed chains and the statistics launches
+ * included). */
 int gs_run_multi_batch_last_ms(const gs_ctx *ctx, double out[2]);
 /* Its overflow handling: out[0] pairs rescored by overflow launches, out[1] chains parked,
  * out[2] resume rounds, out[3] the first arena's capacity. */
