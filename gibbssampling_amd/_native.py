@@ -168,6 +168,12 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_occupancy_offsets": (C.c_int, [vp, i32, vp]),
         "gs_motif_run_batch_stats": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, i32,
                                                i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_run_sweeps_stats": (C.c_int, [vp, f64, f64, i32, u64, i64, vp, i32, i32, vp, vp, vp, vp,
+                                          vp]),
+        "gs_motif_run_stats": (C.c_int, [vp, i32, f64, f64, i32, u64, i64, vp, i32, i32, vp, vp, vp,
+                                         vp, vp, vp, vp]),
+        "gs_run_stats_last_ms": (C.c_int, [vp, vp]),
+        "gs_state_motif_length": (i32, [vp]),
         "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
                                                vp, vp, vp, vp, vp]),
         "gs_motif_run_multi_batch_stats": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32,
@@ -636,6 +642,90 @@ class Context:
         and their aggregates, sweeps with the statistics launches)."""
         out = np.zeros(2, np.float64)
         self._check(self.lib.gs_run_batch_last_ms(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def _chain_stats_outputs(self, W, n_sweeps, u, burn_in, thin, occupancy, ic, best):
+        """The uniforms and the output arrays of run_sweeps_stats / motif_run_stats (W: the
+        motif length the bins are for, None: none can be sized) -> (u, burn_in, thin, stats)."""
+        T = int(n_sweeps)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (max(T, 0), self.n_local):
+                raise ArgumentError(GS_E_ARG, "u needs the shape [sweeps, sequences]")
+        burn_in, thin = int(burn_in), int(thin)
+        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
+        ok = 0 <= burn_in <= T and thin >= 1
+        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        stats = {}
+        if occupancy:
+            H = int(self.lib.gs_occupancy_size(self.h, int(W))) if W is not None else -1
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros(max(H, 0), np.int32)
+        if ic:
+            stats["ic"] = np.full(n_counted, np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(1, -1, np.int64)
+            stats["best_pos"] = np.full(self.n_local, -1, np.int32)
+            stats["best_pwms"] = np.zeros(self.n_local, np.float64)
+        return u, burn_in, thin, stats
+
+    def run_sweeps_stats(self, pc: float, cutoff: float, n_sweeps: int, seed: int,
+                         first_sweep: int = 0, u=None, burn_in: int = 0, thin: int = 1,
+                         occupancy: bool = True, ic: bool = True, best: bool = True,
+                         strict: bool = True):
+        """run_sweeps with statistics of the chain's sweeps, gathered on the device with no
+        host wait between sweeps (gs_run_sweeps_stats) -> stats.  The chain starts from the
+        resident snapshot (set_positions, a previous chain), whose motif length sizes the bins;
+        without one the call raises with status GS_E_STATE.  Sweep t counts when t >= burn_in and
+        (t - burn_in) % thin == 0.  stats is a dict of the parts asked for: "occupancy"[H]
+        (the counted sweeps whose state has its sequence at that bin) with "offsets"[N + 1];
+        "ic"[n_counted], the sum of the PWMS of each counted sweep in the fixed order of
+        sampler.informationContent; "best_sweep"[1] (first_sweep + t of the first largest ic,
+        -1: none), "best_pos"[N] and "best_pwms"[N]; and "status", the call's gs_status.  u[n_sweeps,
+        N] replaces the counter RNG's uniforms.  The snapshot stays on the context (get_state).
+        A chain that raises in sweep t counts nothing from t on (its ic entries are NaN) and
+        raises here; with strict=False the status is returned in stats instead."""
+        W = int(self.lib.gs_state_motif_length(self.h))
+        if W <= 0:
+            raise DeviceError(GS_E_STATE, "no snapshot: call set_positions")
+        u, burn_in, thin, stats = self._chain_stats_outputs(W, n_sweeps, u, burn_in, thin,
+                                                            occupancy, ic, best)
+        st = self.lib.gs_run_sweeps_stats(
+            self.h, float(pc), float(cutoff), int(n_sweeps), int(seed) & (2**64 - 1),
+            int(first_sweep), _ptr(u), burn_in, thin, _ptr(stats.get("occupancy")),
+            _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")), _ptr(stats.get("best_pos")),
+            _ptr(stats.get("best_pwms")))
+        if st != GS_OK and (strict or st not in (GS_E_ROULETTE_OVERRUN, GS_E_OVERFLOW)):
+            self._check(st)
+        stats["status"] = int(st)
+        return stats
+
+    def motif_run_stats(self, W: int, pc: float, cutoff: float, n_sweeps: int, seed: int, pos,
+                        first_sweep: int = 0, u=None, burn_in: int = 0, thin: int = 1,
+                        occupancy: bool = True, ic: bool = True, best: bool = True):
+        """motif_run with the statistics of run_sweeps_stats in one call (gs_motif_run_stats)
+        -> (pos, pwms, stats)."""
+        pos = np.array(pos, dtype=np.int32, copy=True)
+        if pos.shape != (self.n_local,):
+            raise ArgumentError(GS_E_ARG, "pos needs one entry per sequence")
+        pwms = np.zeros(self.n_local, np.float64)
+        u, burn_in, thin, stats = self._chain_stats_outputs(W, n_sweeps, u, burn_in, thin,
+                                                            occupancy, ic, best)
+        self._check(self.lib.gs_motif_run_stats(
+            self.h, int(W), float(pc), float(cutoff), int(n_sweeps), int(seed) & (2**64 - 1),
+            int(first_sweep), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms),
+            _ptr(stats.get("occupancy")), _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms"))))
+        stats["status"] = GS_OK
+        return pos, pwms, stats
+
+    def run_stats_last_ms(self):
+        """Device milliseconds of the last run_sweeps_stats: (the chain of launches, the
+        statistics launches); the second is measured only with the profile on, and is then
+        taken out of the first."""
+        out = np.zeros(2, np.float64)
+        self._check(self.lib.gs_run_stats_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
 
     def _run_multi_batch_args(self, motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u):

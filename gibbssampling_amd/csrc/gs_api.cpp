@@ -609,32 +609,60 @@ int gs_run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_
     int rc;
     if ((rc = check_dev(c))) return rc;
     if (!c->have_state) return fail(c, GS_E_STATE, "no snapshot: call gs_state_set_positions");
-    if ((rc = bg_resolve(c))) return rc;
-    int32_t t = 0;
-    if (use_dna(c)) {
-        // the DNA sweep reads its sweep index from the device counter and the last
-        // workgroup of each sweep advances it
-        if ((rc = need_vec(c))) return rc;
-        HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, (unsigned long long)first_sweep,
-                                         c->d_done_ctr, c->stream));
-    }
-    if (graphs_wanted(c) && n_sweeps >= kGraphSweeps) {
-        if ((rc = graph_buffers(c))) return rc;
-        if (hipGraphExec_t g = sweep_graph(c, pc, cutoff, seed)) {
-            HIP_TRY(c, gs_set_counter_launch(c->d_sweep_ctr, (unsigned long long)first_sweep,
-                                             c->d_done_ctr, c->stream));
-            for (; t + kGraphSweeps <= n_sweeps; t += kGraphSweeps)
-                HIP_TRY(c, hipGraphLaunch(g, c->stream));
-        }
-    }
-    // PWMS after a chain are those of its last sweep: every sweep overwrites them and
-    // nothing reads them in between, so only the last direct launch computes them
-    for (; t < n_sweeps; ++t)
-        if ((rc = one_sweep(c, pc, cutoff, nullptr, seed,
-                            stream_sweep((uint64_t)(first_sweep + t)), t == n_sweeps - 1)))
-            return rc;
-    // the rest of the chain by the all-background kernel once a sweep saw the state
-    return n_sweeps > 0 ? bg_check_note(c, pc, cutoff) : GS_OK;
+    return run_sweeps(c, pc, cutoff, n_sweeps, seed, first_sweep);
+}
+
+// What gs_run_sweeps_stats and gs_motif_run_stats refuse before any launch, beyond a missing
+// snapshot (W: the snapshot's, or the one about to be set).
+static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_sweeps,
+                            int64_t first_sweep, const double *u, const RunStats &st) {
+    if (n_sweeps < 0 || first_sweep < 0 || st.burn_in < 0 || st.burn_in > n_sweeps || st.thin < 1 ||
+        (st.best_sweep_out != nullptr) != (st.best_pos_out && st.best_pwms_out) ||
+        (!st.best_sweep_out && (st.best_pos_out || st.best_pwms_out)))
+        return fail(c, GS_E_ARG,
+                    std::string(entry) +
+                        ": n_sweeps < 0, first_sweep < 0, burn_in outside [0, n_sweeps], thin < 1, "
+                        "or best_sweep_out without both best rows (or the reverse)");
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    std::string(entry) +
+                        ": the trace sums the PWMS of every sequence: it needs all sequences on "
+                        "one device and no communicator");
+    // the bins, the trace, the running best and its rows, and the explicit uniforms
+    const int64_t n = c->n_local;
+    const int64_t H = st.occ_out ? std::max<int64_t>(0, occupancy_offsets(c, W, nullptr)) : 0;
+    const int64_t n_counted =
+        st.burn_in < n_sweeps ? ((int64_t)n_sweeps - st.burn_in + st.thin - 1) / st.thin : 0;
+    const int64_t bytes = (st.occ_out ? H * 4 + (n + 1) * 8 : 0) + (st.ic_out ? n_counted * 8 : 0) +
+                          (st.best_sweep_out ? 16 + n * 12 : 0) + (u ? (int64_t)n_sweeps * n * 8 : 0);
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    std::string(entry) + ": the statistics take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a call may hold: ask for fewer of them, or split the sweeps over "
+                        "several calls");
+    return GS_OK;
+}
+
+int gs_run_sweeps_stats(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t seed,
+                        int64_t first_sweep, const double *u, int32_t burn_in, int32_t thin,
+                        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
+                        int32_t *best_pos_out, double *best_pwms_out) {
+    if (!c) return GS_E_ARG;
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if (!c->have_state) return fail(c, GS_E_STATE, "no snapshot: call gs_state_set_positions");
+    if ((rc = run_stats_checks(c, "gs_run_sweeps_stats", c->W, n_sweeps, first_sweep, u, st)))
+        return rc;
+    return run_sweeps(c, pc, cutoff, n_sweeps, seed, first_sweep, u, &st);
+}
+
+int gs_run_stats_last_ms(const gs_ctx *c, double out[2]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->run_stats_ms[0];
+    out[1] = c->run_stats_ms[1];
+    return GS_OK;
 }
 
 int gs_prepare_sweeps(gs_ctx *c, double pc, double cutoff, uint64_t seed) {
@@ -674,6 +702,8 @@ int gs_state_get(gs_ctx *c, int32_t *pos_out, double *pwms_out) {
     return GS_OK;
 }
 
+int32_t gs_state_motif_length(const gs_ctx *c) { return c && c->have_state ? c->W : 0; }
+
 int gs_motif_sweep(gs_ctx *c, int32_t W, double pc, double cutoff, const int32_t *pos_in,
                    const double *u, int32_t *pos_out, double *pwms_out) {
     if (!c || (c->n_local > 0 && (!pos_in || !u || !pos_out || !pwms_out))) return GS_E_ARG;
@@ -698,6 +728,24 @@ int gs_motif_run(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweep
     return gs_state_get(c, pos_inout, pwms_out);
 }
 
+
+int gs_motif_run_stats(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                       uint64_t seed, int64_t first_sweep, const double *u, int32_t burn_in,
+                       int32_t thin, int32_t *pos_inout, double *pwms_out, int32_t *occ_out,
+                       double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+                       double *best_pwms_out) {
+    if (!c || (c->n_local > 0 && !pos_inout)) return GS_E_ARG;
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
+    int rc;
+    // (before the snapshot is replaced: a refused call leaves the context as it was)
+    if ((rc = validate_W(c, W))) return rc;
+    if ((rc = run_stats_checks(c, "gs_motif_run_stats", W, n_sweeps, first_sweep, u, st))) return rc;
+    if ((rc = gs_state_set_positions(c, W, pos_inout))) return rc;
+    if ((rc = gs_run_sweeps_stats(c, pc, cutoff, n_sweeps, seed, first_sweep, u, burn_in, thin,
+                                  occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out)))
+        return rc;
+    return gs_state_get(c, pos_inout, pwms_out);
+}
 
 int gs_run_greedy(gs_ctx *c, double pc, double cutoff, int32_t max_passes, int32_t *passes_out,
                   double *kernel_ms_out) {

@@ -1,7 +1,9 @@
 // gs_chainstats.hip — the device-side consumers of a chain batch's sweeps
 // (gs_motif_run_batch_stats, DESIGN.md §9.25, and gs_motif_run_multi_batch_stats, §9.26): per
 // counted sweep one launch, stream-ordered right after that sweep's launches, which left the
-// chains' positions (or Positions lists) and PWMS rows and their skip words.
+// chains' positions (or Positions lists) and PWMS rows and their skip words.  And the
+// consumer of the single chain's sweeps (gs_run_sweeps_stats, §9.27): one launch after a
+// counted sweep of any of the sweep kernels, which left d_pos, d_pwms and the error word.
 #include "gs_ctx.h"
 #include "gs_wave.h"
 
@@ -162,5 +164,137 @@ hipError_t gs_run_multi_batch_stats_launch(const RunMultiStatsArgs &a, int block
     if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
     hipLaunchKernelGGL(gs_run_multi_batch_stats_kernel, dim3(a.n_chains * blocks_per_chain),
                        dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The consumer of one counted sweep of the single chain (gs_run_sweeps_stats, DESIGN.md
+// §9.27): one long row instead of 64 short ones.  Workgroup 0, when the trace or the best
+// state is asked for: wavefront 0 forms the ordered sum of the contract (64 lane-strided
+// serial sums from +0.0, lane l adding n = l, l + 64, .. in increasing n, then the halving
+// tree) with its entries loaded straight into registers, kStatsDepth coalesced 512-byte
+// wavefront loads a batch and the next batch in flight under the adds of this one; there is
+// no barrier a chunk and no LDS staging.  An entry past the row's end is +0.0: a partial
+// sum that started from +0.0 is never -0.0, so the add changes no bit.  Lane 0 writes the
+// trace entry and decides against the running best (chain_sum_best's rule: the first
+// counted sweep is taken, a later one only when strictly larger, a NaN never); on a win the
+// whole workgroup copies the two rows, behind the one barrier that hands the decision
+// over, or, for a long row (copy_inline == 0), the workgroups of gs_run_stats_best_kernel
+// do, launched behind this kernel.  Every other workgroup (all of them without sums): one to bin off[n] + 1 + pos[n]
+// for its share of the targets, a position outside [-1, L - W] not counted.  The bins one
+// launch touches are distinct and launches are stream-ordered: both kinds of add race with
+// nothing.  No workgroup waits on another.  A set error word (the chain raised in this
+// sweep or before): the trace entry is a quiet NaN and nothing else is written.
+constexpr int kStatsDepth = 24;  // wavefront loads a batch: so many in flight ahead of the adds
+
+extern "C" __global__ void __launch_bounds__(256)
+gs_run_stats_kernel(ChainStatsArgs a) {
+    __shared__ int win;
+    const int tid = threadIdx.x;
+    const bool sums = a.ic || a.best_sweep;
+    if (*a.err != 0) {  // grid-uniform
+        if (blockIdx.x == 0 && tid == 0 && a.ic) *a.ic = quiet_nan();
+        return;
+    }
+    int blk = blockIdx.x, nblk = gridDim.x;
+    if (sums) {
+        if (blk == 0) {
+            if (tid == 0) win = 0;
+            if (tid < 64) {
+                // Two register batches, A and B, filled and drained in turn: the loads of one
+                // are in flight under the adds of the other.  Every load is issued, at an
+                // index clamped into the row, and an entry past the end is replaced where it
+                // is added: a branch around a load, or a copy of a batch, would make the adds
+                // wait for each load in turn.
+                const unsigned n = (unsigned)a.n_local, lane = (unsigned)tid;
+                constexpr unsigned kBatch = 64 * kStatsDepth;
+                const unsigned whole = n / kBatch;  // batches with every entry in the row
+                // batch b of the row; past the last whole one that one again (never added)
+                const auto fill = [&](double (&r)[kStatsDepth], unsigned b) {
+                    const double *p = a.pwms + (size_t)min(b, whole - 1) * kBatch + lane;
+#pragma unroll
+                    for (int k = 0; k < kStatsDepth; ++k) r[k] = p[64 * k];
+                };
+                double v = 0.0;
+                const auto drain = [&](const double (&r)[kStatsDepth]) {
+#pragma unroll
+                    for (int k = 0; k < kStatsDepth; ++k) v = v + r[k];
+                };
+                // the row's tail, short of a batch: loaded first, added last
+                double T[kStatsDepth], A[kStatsDepth], B[kStatsDepth];
+#pragma unroll
+                for (int k = 0; k < kStatsDepth; ++k) {
+                    const unsigned i = whole * kBatch + lane + 64 * k;
+                    const double x = a.pwms[min(i, n - 1)];
+                    T[k] = i < n ? x : 0.0;
+                }
+                if (whole > 0) {  // wavefront-uniform, like every branch below
+                    fill(A, 0);
+                    for (unsigned b = 0; b < whole; b += 2) {
+                        // (the scheduler is held to this order: it would otherwise sink a
+                        // batch's loads below the other's adds, and the two would take turns)
+                        fill(B, b + 1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        drain(A);
+                        __builtin_amdgcn_sched_barrier(0);
+                        fill(A, b + 2);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (b + 1 < whole) drain(B);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                drain(T);
+                for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
+                if (tid == 0) {
+                    if (a.ic) *a.ic = v;
+                    if (a.best_sweep && (*a.best_sweep < 0 || v > *a.best_ic)) {
+                        *a.best_sweep = a.sweep;
+                        *a.best_ic = v;
+                        win = 1;
+                    }
+                }
+            }
+            __syncthreads();
+            if (win && a.copy_inline)
+                for (int n = tid; n < a.n_local; n += 256) {
+                    a.best_pos[n] = a.pos[n];
+                    a.best_pwms[n] = a.pwms[n];
+                }
+            return;
+        }
+        --blk;
+        --nblk;
+    }
+    if (!a.occ) return;
+    for (int n = blk * 256 + tid; n < a.n_local; n += nblk * 256) {
+        const int64_t o = a.off[n];
+        const int64_t k = (int64_t)a.pos[n] + 1;
+        if (k < 0 || k >= a.off[n + 1] - o) continue;
+        bump(&a.occ[o + k], a.atomic);
+    }
+}
+
+// The best rows of a long chain, behind gs_run_stats_kernel on the stream: the running
+// best's sweep number is this sweep's exactly when this sweep won (the numbers of one call
+// are distinct), else every workgroup returns at once.  1 024 targets a workgroup.
+extern "C" __global__ void __launch_bounds__(256)
+gs_run_stats_best_kernel(ChainStatsArgs a) {
+    if (*a.err != 0 || *a.best_sweep != a.sweep) return;  // grid-uniform
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < a.n_local; n += gridDim.x * 256) {
+        a.best_pos[n] = a.pos[n];
+        a.best_pwms[n] = a.pwms[n];
+    }
+}
+
+// bin_blocks workgroups over the targets' bins (none without occ), and one more in front
+// for the sum when the trace or the best state is asked for; then, with copy_inline == 0,
+// the launch that copies the best rows.
+hipError_t gs_run_stats_launch(const ChainStatsArgs &a, int bin_blocks, hipStream_t s) {
+    if (a.n_local <= 0) return hipSuccess;
+    const int grid = (a.ic || a.best_sweep ? 1 : 0) + (a.occ ? bin_blocks : 0);
+    if (grid <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gs_run_stats_kernel, dim3(grid), dim3(256), 0, s, a);
+    if (a.best_sweep && !a.copy_inline)
+        hipLaunchKernelGGL(gs_run_stats_best_kernel, dim3(std::min(1024, (a.n_local + 1023) / 1024)),
+                           dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -53,7 +53,7 @@ struct gs_tuning {
     int32_t multi_batch_fill = 2;  // list batch: scoring workgroups per CU over all chains that the slots per chain start from (1 .. 64 measured)
     int32_t run_batch_clear = 1;  // chain batch: the next aggregate rows zeroed by a memset before each sweep (0) or a third row cleared in-kernel (1: 1 - 3 % faster at 200 and 2 000 sequences)
     int32_t run_batch_blocks = 32;  // chain batch: cap on the one-wavefront workgroups per CU of its sweep launches (8 / 16 / 32, i.e. what fits: 18.1 / 12.6 / 11.3 ms for 64 chains x 200 sweeps x 200 sequences)
-    int32_t run_stats_blocks = 0;  // chain statistics (gs_motif_run_batch_stats): workgroups per chain of a counted sweep's launch, 0 = 256 targets each while the GPU is four deep over all chains (10 000 sequences x 8 chains x 200 sweeps: one workgroup a chain 135.6 - 145.8 against 130.7 ms of sweeps); the results do not depend on it
+    int32_t run_stats_blocks = 0;  // chain statistics (gs_motif_run_batch_stats): workgroups per chain of a counted sweep's launch, 0 = 256 targets each while the GPU is four deep over all chains (10 000 sequences x 8 chains x 200 sweeps: one workgroup a chain 135.6 - 145.8 against 130.7 ms of sweeps); the results do not depend on it; gs_run_sweeps_stats: the workgroups over the bins of a counted sweep's launch, 0 = 256 targets each while the GPU is four deep (§9.27)
     int32_t run_stats_atomic = 1;  // ... and its bins by non-returning atomic adds (1) or plain read-modify-write (0): both race-free, no difference measured; the results do not depend on it
     int32_t run_multi_arena_max = 1 << 28;  // list chain batch (gs_motif_run_multi_batch): the categories a target's levels 1 .. M - 1 may take (kArenaMax) before its chain is given up with GS_E_UNSUPPORTED; tests lower it to reach that branch with small arenas.  The one field a chain's status can depend on
     int32_t batch_starts = -1;  // batch drivers: the chains' starts chain after chain on the single-chain state (0), all chains in the launches of gs_random_starts_batch (1), or -1: the latter while a chain has fewer targets than a launch has workgroups (8 a CU), the size range where it measured faster; the results do not depend on it
@@ -236,6 +236,26 @@ struct RunMultiStatsArgs {
 };
 hipError_t gs_run_multi_batch_stats_launch(const RunMultiStatsArgs &a, int blocks_per_chain,
                                            hipStream_t s);
+// One counted sweep of gs_run_sweeps_stats for gs_run_stats_kernel (gs_chainstats.hip,
+// DESIGN.md §9.27): the single chain's snapshot and PWMS as that sweep left them, its
+// histogram, this sweep's entry of the trace, the running best.
+struct ChainStatsArgs {
+    int32_t n_local;
+    int32_t atomic;              // as RunStatsArgs
+    int32_t copy_inline;         // a win's rows copied by the sum's workgroup (1) or by a launch behind it (0)
+    const int32_t *err;          // the context's sticky error word: nonzero = the chain raised
+    const int32_t *pos;          // [n_local]: the snapshot the sweep wrote
+    const double *pwms;          // [n_local]: its PWMS (read only with ic or best_sweep)
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets (read only with occ)
+    int32_t *occ;                // [H], or null
+    double *ic;                  // the sweep's entry of the trace, or null
+    int64_t sweep;               // first_sweep + t
+    double *best_ic;             // [1]
+    int64_t *best_sweep;         // [1]: -1 until a counted sweep completed; null: no best state
+    int32_t *best_pos;           // [n_local]
+    double *best_pwms;           // [n_local]
+};
+hipError_t gs_run_stats_launch(const ChainStatsArgs &a, int bin_blocks, hipStream_t s);
 // What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
 // of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
 // names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
@@ -407,6 +427,7 @@ struct gs_ctx {
     double site_batch_ms[3] = {0.0, 0.0, 0.0};  // the last site batch: starts, Gauss–Seidel launch, shifted passes
     double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
     double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
+    double run_stats_ms[2] = {0.0, 0.0};  // the last gs_run_sweeps_stats: sweeps, statistics launches
     double starts_batch_ms[2] = {0.0, 0.0};  // the last gs_random_starts_batch: counts / aggregates, scans
     double run_multi_batch_ms[2] = {0.0, 0.0};  // the last list chain batch (gs_motif_run_multi_batch): starts, sweeps
     int32_t run_multi_batch_info[4] = {0, 0, 0, 0};  // ... pairs rescored by overflow launches, chains parked, resume rounds, first arena
@@ -509,6 +530,11 @@ struct MultiBufs {
 constexpr int64_t kArenaBudget = 4ll << 30;     // bytes of category arenas per launch
 constexpr int64_t kArenaMax = 1ll << 28;        // categories per target
 constexpr int64_t kBatchBytesMax = 4ll << 30;   // bytes of chain slabs per batch call
+// gs_run_sweeps_stats: from this many targets on the best rows are copied by a launch of their
+// own behind the statistics kernel (a kernel boundary, ~1.5 us, every counted sweep) instead of
+// by the sum's one workgroup (12 bytes a target at one CU's rate, ~50 GB/s, on a win): the two
+// meet near 32k targets when a sweep in four wins
+constexpr int32_t kStatsCopyLaunch = 32768;
 constexpr int64_t kStartsCpartBudget = 256ll << 20;  // bytes of cpart slabs per group of chains (batched starts, mode 0)
 
 void drop_graphs(gs_ctx *c);
@@ -549,6 +575,10 @@ int set_snapshot_dev(gs_ctx *c, int32_t W, const int32_t *d_src, bool reset_err)
 int one_sweep(gs_ctx *c, double pc, double cutoff, const double *u_dev, uint64_t seed,
               uint64_t stream, bool want_pwms = true);
 bool graphs_wanted(gs_ctx *c);
+struct RunStats;
+// gs_run_sweeps (u and stats null) and gs_run_sweeps_stats (stats non-null, arguments validated)
+int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t seed,
+               int64_t first_sweep, const double *u = nullptr, const RunStats *stats = nullptr);
 int graph_buffers(gs_ctx *c);
 hipGraphExec_t sweep_graph(gs_ctx *c, double pc, double cutoff, uint64_t seed);
 int starts_pass(gs_ctx *c, int mode, int32_t W, double pc, uint64_t seed, const int32_t *d_starts,
@@ -599,8 +629,8 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
 int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const uint64_t *seeds,
                 int32_t R, int32_t mode, int32_t max_passes, int32_t cap, int32_t *cnt_out,
                 int32_t *pos_out, double *pwms_out, int32_t *passes_out, int32_t *status_out);
-// The caller's side of gs_motif_run_batch_stats: which sweeps count and where the chains'
-// statistics go (each nullable; the best rows go with best_sweep_out).
+// The caller's side of gs_motif_run_batch_stats and gs_run_sweeps_stats: which sweeps count and
+// where the chains' statistics go (each nullable; the best rows go with best_sweep_out).
 struct RunStats {
     int32_t burn_in, thin;
     int32_t *occ_out;

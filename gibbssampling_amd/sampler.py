@@ -121,7 +121,8 @@ def informationContent(pwms) -> float:
 
 @dataclass
 class ChainStats:
-    """What MotifSampler.runSweepsBatchedStats gathered over the counted sweeps of R chains.
+    """What MotifSampler.runSweepsBatchedStats gathered over the counted sweeps of R chains
+    (MotifSampler.runSweepsStats: of the single chain, R = 1).
     occupancy[R, H]: the counted sweeps whose state has its sequence at that bin; sequence n
     owns the bins offsets[n] .. offsets[n + 1] - 1, the first one counting Positions [], bin
     offsets[n] + 1 + k start k.  ic[R, n_counted]: informationContent of every counted
@@ -278,6 +279,33 @@ class MotifSampler:
         co, po, pw = ctx.motif_run_multi(motifAmount, motifLength, pseudoCount, cutOff, sweeps,
                                          seed, cnt, pos, first_sweep, cap)
         return _motif_lists(co, po, pw)
+
+    @staticmethod
+    def runSweepsStats(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,
+                       motifMem: Sequence[MotifIndex], sweeps: int, burn_in: int = 0,
+                       thin: int = 1, seed: int = 0, first_sweep: int = 0, device: int = 0):
+        """runSweeps (motifAmount 1, single positions) with the statistics a chain is run
+        for, gathered on the device behind its sweeps in the same single call
+        (Context.motif_run_stats) -> (chain, ChainStats with R = 1): the occupancy of every
+        motif start over the counted sweeps (t >= burn_in, every thin-th), the trace of
+        informationContent, and the best state visited.  The single chain runs on the fast
+        sweep kernels: the way to a posterior from about 2 000 sequences on, where the chain
+        batch (runSweepsBatchedStats) no longer pays.  A chain that raises
+        raises here."""
+        if len(motifMem) != len(sources):
+            raise _native.ArgumentError(_native.GS_E_ARG, "motifMem and sources differ in length")
+        if not _is_single(1, motifMem):
+            raise _native.ArgumentError(_native.GS_E_ARG,
+                                        "the chain statistics need single positions")
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, st = ctx.motif_run_stats(motifLength, pseudoCount, cutOff, sweeps,
+                                            int(seed) & (2**64 - 1), _single_positions(motifMem),
+                                            first_sweep, burn_in=burn_in, thin=thin)
+        best = [_motif_indices(st["best_pos"], st["best_pwms"]) if st["best_sweep"][0] >= 0
+                else []]
+        stats = ChainStats(st["occupancy"][None, :], st.get("offsets", np.zeros(1, np.int64)),
+                           st["ic"][None, :], st["best_sweep"], best)
+        return _motif_indices(pos, pwms), stats
 
     @staticmethod
     def runSweepsBatched(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,

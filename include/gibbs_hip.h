@@ -111,6 +111,9 @@ int gs_state_set_positions(gs_ctx *ctx, int32_t W, const int32_t *pos);
 int gs_run_sweeps(gs_ctx *ctx, double pseudo_count, double cut_off, int32_t n_sweeps,
                   uint64_t seed, int64_t first_sweep);
 int gs_state_get(gs_ctx *ctx, int32_t *pos_out, double *pwms_out);
+/* The motif length of the resident snapshot (what sizes gs_occupancy_size for
+ * gs_run_sweeps_stats), 0 when the context holds none. */
+int32_t gs_state_motif_length(const gs_ctx *ctx);
 /* With a communicator gs_run_sweeps replays chains of 6 sweeps as hipGraphs
  * (captured once per buffer phase and (pseudo_count, cut_off, seed)).  This builds the
  * graph for the current phase ahead of time (no sweep runs); optional. */
@@ -282,6 +285,68 @@ int gs_motif_run_batch_stats(gs_ctx *ctx, int32_t W, double pseudo_count, double
         int64_t *best_sweep_out, /* [n_chains], nullable               */
         int32_t *best_pos_out,   /* [n_chains][n_local]                */
         double  *best_pwms_out   /* [n_chains][n_local]                */);
+
+/* gs_run_sweeps with the same statistics of the single chain's sweeps, gathered on the device
+ * behind each counted sweep of whichever sweep kernel runs it (the general and four-symbol
+ * kernels, the DNA, live-chain, long-sequence and all-background ones), with no host wait
+ * between sweeps: the way to a posterior at the sizes where the chain batch no longer pays.
+ * The chain is exactly the one gs_run_sweeps(ctx, pc, cut_off, n_sweeps, seed, first_sweep)
+ * runs from the same snapshot, or, with u non-null, the one whose sweep t uses u[t][n] as
+ * gs_motif_sweep would.  The snapshot stays on the context: gs_state_get, a further
+ * gs_run_sweeps (first_sweep advanced) and gs_run_greedy work afterwards.  With every
+ * statistic null and u null the positions and PWMS left are those of gs_run_sweeps followed
+ * by gs_synchronize, bit for bit.  The call synchronises once, at its end; its sweeps are
+ * always direct launches (never the captured graphs), an uncounted sweep costs nothing extra.
+ * Sweep t, 0 <= t < n_sweeps, is counted when t >= burn_in and (t - burn_in) % thin == 0;
+ * n_counted is their number; the state of a counted sweep is the snapshot that sweep wrote
+ * (the starts are never counted).  The outputs are written, not accumulated: a continued call
+ * yields its own counts and the caller adds them.
+ * occ_out[b]: the number of counted sweeps whose state has its sequence at bin b, in the bins
+ * of gs_occupancy_offsets (Positions [] goes to bin off[n], start k to bin off[n] + 1 + k); for
+ * a chain that finishes every sequence's bins sum to n_counted.
+ * ic_out[i]: the sum over the sequences of the PWMS of the i-th counted sweep (.fs:981-989), in
+ * binary64 in the fixed order of gs_motif_run_batch_stats: 64 partial sums v[l], each from
+ * +0.0, v[l] adding the PWMS of n = l, l + 64, ... in increasing n; then for s = 32, 16, 8, 4,
+ * 2, 1: v[l] = v[l] + v[l + s] for l < s; the result is v[0].
+ * best_*: the first counted sweep with the largest ic: a later one replaces it only when
+ * strictly larger (.fs:989), the first counted sweep is always taken and a NaN never replaces
+ * anything.  best_sweep_out[0] is the absolute sweep number first_sweep + t, or -1 when no
+ * counted sweep completed (the two rows are then unspecified); the rows are that sweep's
+ * positions and PWMS, bit for bit.
+ * When the sticky device error is raised in sweep t (.fs:752, .fs:117) nothing is counted from
+ * t on: the bins hold the counted sweeps before t, the ic entries from t on are quiet NaN, the
+ * best is the best before t; the call returns that status (the statistics are still written)
+ * and leaves the context as gs_run_sweeps followed by gs_synchronize leaves it after the same
+ * error (no snapshot).
+ * Refused before any launch: GS_E_STATE without a snapshot; GS_E_ARG for n_sweeps < 0,
+ * first_sweep < 0, burn_in outside [0, n_sweeps], thin < 1, best_sweep_out without both best
+ * rows or the reverse; GS_E_UNSUPPORTED for sharded sequences or a communicator (the trace
+ * needs every sequence), or when the bins (H x 4 bytes), the trace, the best rows and the
+ * explicit uniforms together pass 4 GiB.  A fixed PCV is allowed (gs_set_fixed_pcv: the ByPCV
+ * twin): the statistics only read the sweeps' outputs.
+ * gs_motif_run_stats: gs_state_set_positions + gs_run_sweeps_stats + gs_state_get in one call
+ * (gs_motif_run with the statistics); its refusals come before the snapshot is replaced. */
+int gs_run_sweeps_stats(gs_ctx *ctx, double pseudo_count, double cut_off, int32_t n_sweeps,
+        uint64_t seed, int64_t first_sweep,
+        const double *u,         /* nullable: [n_sweeps][n_local], as gs_motif_sweep's */
+        int32_t burn_in, int32_t thin,
+        int32_t *occ_out,        /* [H] of gs_occupancy_offsets, nullable              */
+        double  *ic_out,         /* [n_counted], nullable                              */
+        int64_t *best_sweep_out, /* [1], nullable; goes together with both best rows   */
+        int32_t *best_pos_out,   /* [n_local]                                          */
+        double  *best_pwms_out   /* [n_local]                                          */);
+int gs_motif_run_stats(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+        int32_t n_sweeps, uint64_t seed, int64_t first_sweep, const double *u,
+        int32_t burn_in, int32_t thin,
+        int32_t *pos_inout,      /* [n_local], -1 = Positions []                       */
+        double  *pwms_out,       /* [n_local]                                          */
+        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+        double *best_pwms_out);
+/* Device times of the last gs_run_sweeps_stats, ms: out[0] the chain of launches from the
+ * first sweep to the last statistics launch; with the profile on (gs_profile_enable) out[1]
+ * is the sum over the statistics launches, each between two events of its own, and out[0] the
+ * rest; without it out[1] is 0. */
+int gs_run_stats_last_ms(const gs_ctx *ctx, double out[2]);
 
 /* R independent chains of n_sweeps synchronous sweeps each with Positions lists (any
  * motifAmount) in one call: chain r is exactly n_sweeps calls of gs_motif_sweep_multi(ctx,
@@ -600,8 +665,8 @@ int gs_set_scan_mode(gs_ctx *ctx, int32_t mode);
  * run_batch_clear (gs_motif_run_batch: 0 a memset of the next aggregate rows before each
  * sweep, 1 a third row cleared in-kernel), run_batch_blocks (its workgroups per CU),
  * run_stats_blocks (gs_motif_run_batch_stats: workgroups per chain of a counted sweep's
- * statistics launch, 0 automatic), run_stats_atomic (its bins by atomic adds, 1, or plain
- * read-modify-write, 0),
+ * statistics launch, 0 automatic; gs_run_sweeps_stats: the workgroups over the bins), run_stats_atomic
+ * (their bins by atomic adds, 1, or plain read-modify-write, 0),
  * run_multi_arena_max (gs_motif_run_multi_batch: the combinations of up to motif_amount - 1
  * windows a target may have before its chain gets GS_E_UNSUPPORTED, 2048 .. 2^28, default
  * 2^28; for tests of that status, and the one field a chain's status depends on),
