@@ -173,6 +173,15 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_motif_run_stats": (C.c_int, [vp, i32, f64, f64, i32, u64, i64, vp, i32, i32, vp, vp, vp,
                                          vp, vp, vp, vp]),
         "gs_run_stats_last_ms": (C.c_int, [vp, vp]),
+        "gs_occupancy_summary": (C.c_int, [vp, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_run_sweeps_summary": (C.c_int, [vp, f64, f64, i32, u64, i64, vp, i32, i32, vp, vp, vp,
+                                            vp, vp, vp, vp, vp]),
+        "gs_motif_run_summary": (C.c_int, [vp, i32, f64, f64, i32, u64, i64, vp, i32, i32, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_motif_run_batch_summary": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp, i32,
+                                                 i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                 vp, vp, vp]),
+        "gs_summary_last_ms": (C.c_int, [vp, vp]),
         "gs_state_motif_length": (i32, [vp]),
         "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
                                                vp, vp, vp, vp, vp]),
@@ -727,6 +736,157 @@ class Context:
         out = np.zeros(2, np.float64)
         self._check(self.lib.gs_run_stats_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
+
+    def _summary_outputs(self, W, R, modes, counts, pool):
+        """The output arrays of a chain summary of R chains (R None: the single chain's,
+        without a chain axis) -> dict."""
+        lead = () if R is None else (R,)
+        A = len(getattr(self, "_keep", (None, None, ()))[2])  # the alphabet's length
+        cells = A * int(W) + A if W is not None else 0
+        out = {}
+        if modes:
+            out["mode_pos"] = np.full(lead + (self.n_local,), -1, np.int32)
+            out["mode_count"] = np.zeros(lead + (self.n_local,), np.int32)
+        if counts:
+            out["counts"] = np.zeros(lead + (max(cells, 0),), np.int64)
+        if pool:
+            out["pooled_pos"] = np.full(self.n_local, -1, np.int32)
+            out["pooled_count"] = np.zeros(self.n_local, np.int64)
+            out["pooled_counts"] = np.zeros(max(cells, 0), np.int64)
+            out["n_pooled"] = np.zeros(1, np.int32)
+        return out
+
+    def occupancy_summary(self, W: int, occupancy, n_counted: int, modes: bool = True,
+                          counts: bool = True, pool: bool = True) -> dict:
+        """The reduction of caller-held histograms occupancy[R, H] (occupancy_offsets(W): a
+        statistics call's, or the sums of several) on the device (gs_occupancy_summary) ->
+        dict of the groups asked for: "mode_pos"[R, N] and "mode_count"[R, N], each
+        sequence's first-maximum bin minus one (-1 = Positions []) and its count;
+        "counts"[R, A W + A], the count matrix summed over the counted states in counts()'
+        layout, C then T; and, pooled over the chains whose sequence 0 has n_counted counts,
+        "pooled_pos"[N], "pooled_count"[N] (int64), "pooled_counts"[A W + A] and
+        "n_pooled"[1]."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.int32)
+        H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+        if occ.ndim != 2 or (H >= 0 and occ.shape[1] != H):
+            raise ArgumentError(GS_E_ARG, "occupancy needs the shape [chains, bins]")
+        R = occ.shape[0]
+        out = self._summary_outputs(W if H >= 0 else None, R, modes, counts, pool)
+        self._check(self.lib.gs_occupancy_summary(
+            self.h, int(W), _ptr(occ) if R > 0 else None, R, int(n_counted),
+            _ptr(out.get("mode_pos")), _ptr(out.get("mode_count")), _ptr(out.get("counts")),
+            _ptr(out.get("pooled_pos")), _ptr(out.get("pooled_count")),
+            _ptr(out.get("pooled_counts")), _ptr(out.get("n_pooled"))))
+        return out
+
+    def run_sweeps_summary(self, pc: float, cutoff: float, n_sweeps: int, seed: int,
+                           first_sweep: int = 0, u=None, burn_in: int = 0, thin: int = 1,
+                           occupancy: bool = False, ic: bool = True, best: bool = True,
+                           modes: bool = True, counts: bool = True, strict: bool = True):
+        """run_sweeps_stats with the chain's summary reduced on the device behind the last
+        statistics launch (gs_run_sweeps_summary) -> stats, with "mode_pos"[N],
+        "mode_count"[N] and "counts"[A W + A] as in occupancy_summary.  The bins are
+        downloaded only with occupancy=True."""
+        W = int(self.lib.gs_state_motif_length(self.h))
+        if W <= 0:
+            raise DeviceError(GS_E_STATE, "no snapshot: call set_positions")
+        u, burn_in, thin, stats = self._chain_stats_outputs(W, n_sweeps, u, burn_in, thin,
+                                                            occupancy, ic, best)
+        stats.update(self._summary_outputs(W, None, modes, counts, False))
+        st = self.lib.gs_run_sweeps_summary(
+            self.h, float(pc), float(cutoff), int(n_sweeps), int(seed) & (2**64 - 1),
+            int(first_sweep), _ptr(u), burn_in, thin, _ptr(stats.get("occupancy")),
+            _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")), _ptr(stats.get("best_pos")),
+            _ptr(stats.get("best_pwms")), _ptr(stats.get("mode_pos")),
+            _ptr(stats.get("mode_count")), _ptr(stats.get("counts")))
+        if st != GS_OK and (strict or st not in (GS_E_ROULETTE_OVERRUN, GS_E_OVERFLOW)):
+            self._check(st)
+        stats["status"] = int(st)
+        return stats
+
+    def motif_run_summary(self, W: int, pc: float, cutoff: float, n_sweeps: int, seed: int, pos,
+                          first_sweep: int = 0, u=None, burn_in: int = 0, thin: int = 1,
+                          occupancy: bool = False, ic: bool = True, best: bool = True,
+                          modes: bool = True, counts: bool = True):
+        """motif_run_stats with the summary of run_sweeps_summary in one call
+        (gs_motif_run_summary) -> (pos, pwms, stats)."""
+        pos = np.array(pos, dtype=np.int32, copy=True)
+        if pos.shape != (self.n_local,):
+            raise ArgumentError(GS_E_ARG, "pos needs one entry per sequence")
+        pwms = np.zeros(self.n_local, np.float64)
+        u, burn_in, thin, stats = self._chain_stats_outputs(W, n_sweeps, u, burn_in, thin,
+                                                            occupancy, ic, best)
+        ok = int(self.lib.gs_occupancy_size(self.h, int(W))) >= 0
+        stats.update(self._summary_outputs(W if ok else None, None, modes, counts, False))
+        self._check(self.lib.gs_motif_run_summary(
+            self.h, int(W), float(pc), float(cutoff), int(n_sweeps), int(seed) & (2**64 - 1),
+            int(first_sweep), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms),
+            _ptr(stats.get("occupancy")), _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")),
+            _ptr(stats.get("mode_pos")), _ptr(stats.get("mode_count")), _ptr(stats.get("counts"))))
+        stats["status"] = GS_OK
+        return pos, pwms, stats
+
+    def motif_run_batch_summary(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds,
+                                pos=None, init_mode: int = 0, first_sweep: int = 0, u=None,
+                                burn_in: int = 0, thin: int = 1, occupancy: bool = False,
+                                ic: bool = True, best: bool = True, modes: bool = True,
+                                counts: bool = True, pool: bool = True, strict: bool = False):
+        """motif_run_batch_stats with the chains' summaries and the pooled one reduced on the
+        device (gs_motif_run_batch_summary) -> (pos[R, N], pwms[R, N], status[R], stats), stats
+        with the groups of occupancy_summary besides those of motif_run_batch_stats.  The bins
+        are downloaded only with occupancy=True."""
+        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        R, T = len(seeds), int(n_sweeps)
+        if pos is not None:
+            init_mode = -1
+            pos = np.array(pos, dtype=np.int32, copy=True)
+            if pos.shape != (R, self.n_local):
+                raise ArgumentError(GS_E_ARG, "pos needs one row per seed, one entry per sequence")
+        else:
+            if init_mode not in (0, 1):
+                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
+            pos = np.full((R, self.n_local), -1, np.int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (R, max(T, 0), self.n_local):
+                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        burn_in, thin = int(burn_in), int(thin)
+        ok = 0 <= burn_in <= T and thin >= 1
+        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        stats = {}
+        H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+        if occupancy:
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
+        if ic:
+            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(R, -1, np.int64)
+            stats["best_pos"] = np.full((R, self.n_local), -1, np.int32)
+            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats.update(self._summary_outputs(W if H >= 0 else None, R, modes, counts, pool))
+        st = self.lib.gs_motif_run_batch_summary(
+            self.h, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
+            int(init_mode), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms), _ptr(status),
+            _ptr(stats.get("occupancy")), _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")),
+            _ptr(stats.get("mode_pos")), _ptr(stats.get("mode_count")), _ptr(stats.get("counts")),
+            _ptr(stats.get("pooled_pos")), _ptr(stats.get("pooled_count")),
+            _ptr(stats.get("pooled_counts")), _ptr(stats.get("n_pooled")))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        stats["n_counted"] = n_counted
+        return pos, pwms, status, stats
+
+    def summary_last_ms(self) -> float:
+        """Device milliseconds of the last chain summary's reduction."""
+        out = np.zeros(1, np.float64)
+        self._check(self.lib.gs_summary_last_ms(self.h, _ptr(out)))
+        return float(out[0])
 
     def _run_multi_batch_args(self, motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u):
         """The chains' seeds, lists and uniforms as the library takes them (motif_run_multi_batch

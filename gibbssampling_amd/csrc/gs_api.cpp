@@ -618,11 +618,12 @@ static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_s
                             int64_t first_sweep, const double *u, const RunStats &st) {
     if (n_sweeps < 0 || first_sweep < 0 || st.burn_in < 0 || st.burn_in > n_sweeps || st.thin < 1 ||
         (st.best_sweep_out != nullptr) != (st.best_pos_out && st.best_pwms_out) ||
-        (!st.best_sweep_out && (st.best_pos_out || st.best_pwms_out)))
+        (!st.best_sweep_out && (st.best_pos_out || st.best_pwms_out)) || (st.sum && st.sum->ragged()))
         return fail(c, GS_E_ARG,
                     std::string(entry) +
                         ": n_sweeps < 0, first_sweep < 0, burn_in outside [0, n_sweeps], thin < 1, "
-                        "or best_sweep_out without both best rows (or the reverse)");
+                        "best_sweep_out without both best rows (or the reverse), or half of a "
+                        "summary's output group");
     if ((int64_t)c->n_local != c->n_global || c->comm)
         return fail(c, GS_E_UNSUPPORTED,
                     std::string(entry) +
@@ -630,11 +631,13 @@ static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_s
                         "one device and no communicator");
     // the bins, the trace, the running best and its rows, and the explicit uniforms
     const int64_t n = c->n_local;
-    const int64_t H = st.occ_out ? std::max<int64_t>(0, occupancy_offsets(c, W, nullptr)) : 0;
+    const bool sum = st.sum && st.sum->any(), bins = st.occ_out || sum;
+    const int64_t H = bins ? std::max<int64_t>(0, occupancy_offsets(c, W, nullptr)) : 0;
     const int64_t n_counted =
         st.burn_in < n_sweeps ? ((int64_t)n_sweeps - st.burn_in + st.thin - 1) / st.thin : 0;
-    const int64_t bytes = (st.occ_out ? H * 4 + (n + 1) * 8 : 0) + (st.ic_out ? n_counted * 8 : 0) +
-                          (st.best_sweep_out ? 16 + n * 12 : 0) + (u ? (int64_t)n_sweeps * n * 8 : 0);
+    const int64_t bytes = (bins ? H * 4 + (n + 1) * 8 : 0) + (st.ic_out ? n_counted * 8 : 0) +
+                          (st.best_sweep_out ? 16 + n * 12 : 0) + (u ? (int64_t)n_sweeps * n * 8 : 0) +
+                          (sum ? st.sum->bytes(1, n, (int64_t)c->A * W + c->A) : 0);
     if (bytes > kBatchBytesMax)
         return fail(c, GS_E_UNSUPPORTED,
                     std::string(entry) + ": the statistics take " + std::to_string(bytes) +
@@ -644,18 +647,74 @@ static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_s
     return GS_OK;
 }
 
+// gs_run_sweeps_stats (st.sum null) and gs_run_sweeps_summary.
+static int run_sweeps_stats_entry(gs_ctx *c, const char *entry, double pc, double cutoff,
+                                  int32_t n_sweeps, uint64_t seed, int64_t first_sweep,
+                                  const double *u, const RunStats &st) {
+    if (!c) return GS_E_ARG;
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if (!c->have_state) return fail(c, GS_E_STATE, "no snapshot: call gs_state_set_positions");
+    if ((rc = run_stats_checks(c, entry, c->W, n_sweeps, first_sweep, u, st))) return rc;
+    return run_sweeps(c, pc, cutoff, n_sweeps, seed, first_sweep, u, &st);
+}
+
 int gs_run_sweeps_stats(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t seed,
                         int64_t first_sweep, const double *u, int32_t burn_in, int32_t thin,
                         int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
                         int32_t *best_pos_out, double *best_pwms_out) {
-    if (!c) return GS_E_ARG;
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
+    return run_sweeps_stats_entry(c, "gs_run_sweeps_stats", pc, cutoff, n_sweeps, seed,
+                                  first_sweep, u, st);
+}
+
+int gs_run_sweeps_summary(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t seed,
+                          int64_t first_sweep, const double *u, int32_t burn_in, int32_t thin,
+                          int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
+                          int32_t *best_pos_out, double *best_pwms_out, int32_t *mode_pos_out,
+                          int32_t *mode_count_out, int64_t *counts_out) {
+    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, nullptr, nullptr, nullptr, nullptr};
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
+                      &sum};
+    return run_sweeps_stats_entry(c, "gs_run_sweeps_summary", pc, cutoff, n_sweeps, seed,
+                                  first_sweep, u, st);
+}
+
+int gs_summary_last_ms(const gs_ctx *c, double out[1]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->summary_ms;
+    return GS_OK;
+}
+
+int gs_occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t n_chains,
+                         int64_t n_counted, int32_t *mode_pos_out, int32_t *mode_count_out,
+                         int64_t *counts_out, int32_t *pool_mode_pos_out,
+                         int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+                         int32_t *n_pooled_out) {
+    if (!c) return GS_E_ARG;
+    const SummaryOut out{mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
+                         pool_mode_count_out, pool_counts_out, n_pooled_out};
+    if (n_chains < 0 || n_counted < 0 || (n_chains > 0 && !occ) || out.ragged())
+        return fail(c, GS_E_ARG,
+                    "gs_occupancy_summary: n_chains < 0, n_counted < 0, no bins, or half of an "
+                    "output group");
     int rc;
     if ((rc = check_dev(c))) return rc;
-    if (!c->have_state) return fail(c, GS_E_STATE, "no snapshot: call gs_state_set_positions");
-    if ((rc = run_stats_checks(c, "gs_run_sweeps_stats", c->W, n_sweeps, first_sweep, u, st)))
-        return rc;
-    return run_sweeps(c, pc, cutoff, n_sweeps, seed, first_sweep, u, &st);
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_occupancy_summary: the cells are summed over every sequence: it needs all "
+                    "sequences on one device and no communicator");
+    if (n_chains == 0) return GS_OK;
+    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
+    const int64_t bytes = (int64_t)n_chains * H * 4 + (n + 1) * 8 +
+                          out.bytes(n_chains, n, (int64_t)c->A * W + c->A);
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_occupancy_summary: the bins and the results take " + std::to_string(bytes) +
+                        " B, more than the " + std::to_string(kBatchBytesMax) +
+                        " B a call may hold: split the chains over several calls");
+    return occupancy_summary(c, W, occ, n_chains, n_counted, out);
 }
 
 int gs_run_stats_last_ms(const gs_ctx *c, double out[2]) {
@@ -729,22 +788,43 @@ int gs_motif_run(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweep
 }
 
 
+// gs_motif_run_stats (st.sum null) and gs_motif_run_summary.
+static int motif_run_stats_entry(gs_ctx *c, const char *entry, int32_t W, double pc, double cutoff,
+                                 int32_t n_sweeps, uint64_t seed, int64_t first_sweep,
+                                 const double *u, int32_t *pos_inout, double *pwms_out,
+                                 const RunStats &st) {
+    if (!c || (c->n_local > 0 && !pos_inout)) return GS_E_ARG;
+    int rc;
+    // (before the snapshot is replaced: a refused call leaves the context as it was)
+    if ((rc = validate_W(c, W))) return rc;
+    if ((rc = run_stats_checks(c, entry, W, n_sweeps, first_sweep, u, st))) return rc;
+    if ((rc = gs_state_set_positions(c, W, pos_inout))) return rc;
+    if ((rc = run_sweeps_stats_entry(c, entry, pc, cutoff, n_sweeps, seed, first_sweep, u, st)))
+        return rc;
+    return gs_state_get(c, pos_inout, pwms_out);
+}
+
 int gs_motif_run_stats(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
                        uint64_t seed, int64_t first_sweep, const double *u, int32_t burn_in,
                        int32_t thin, int32_t *pos_inout, double *pwms_out, int32_t *occ_out,
                        double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
                        double *best_pwms_out) {
-    if (!c || (c->n_local > 0 && !pos_inout)) return GS_E_ARG;
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
-    int rc;
-    // (before the snapshot is replaced: a refused call leaves the context as it was)
-    if ((rc = validate_W(c, W))) return rc;
-    if ((rc = run_stats_checks(c, "gs_motif_run_stats", W, n_sweeps, first_sweep, u, st))) return rc;
-    if ((rc = gs_state_set_positions(c, W, pos_inout))) return rc;
-    if ((rc = gs_run_sweeps_stats(c, pc, cutoff, n_sweeps, seed, first_sweep, u, burn_in, thin,
-                                  occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out)))
-        return rc;
-    return gs_state_get(c, pos_inout, pwms_out);
+    return motif_run_stats_entry(c, "gs_motif_run_stats", W, pc, cutoff, n_sweeps, seed,
+                                 first_sweep, u, pos_inout, pwms_out, st);
+}
+
+int gs_motif_run_summary(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                         uint64_t seed, int64_t first_sweep, const double *u, int32_t burn_in,
+                         int32_t thin, int32_t *pos_inout, double *pwms_out, int32_t *occ_out,
+                         double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+                         double *best_pwms_out, int32_t *mode_pos_out, int32_t *mode_count_out,
+                         int64_t *counts_out) {
+    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, nullptr, nullptr, nullptr, nullptr};
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
+                      &sum};
+    return motif_run_stats_entry(c, "gs_motif_run_summary", W, pc, cutoff, n_sweeps, seed,
+                                 first_sweep, u, pos_inout, pwms_out, st);
 }
 
 int gs_run_greedy(gs_ctx *c, double pc, double cutoff, int32_t max_passes, int32_t *passes_out,
@@ -1225,10 +1305,12 @@ static int motif_run_batch_entry(gs_ctx *c, int32_t W, double pc, double cutoff,
         return GS_E_ARG;
     if (st && (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
                (st->best_sweep_out != nullptr) != (st->best_pos_out && st->best_pwms_out) ||
-               (!st->best_sweep_out && (st->best_pos_out || st->best_pwms_out))))
+               (!st->best_sweep_out && (st->best_pos_out || st->best_pwms_out)) ||
+               (st->sum && st->sum->ragged())))
         return fail(c, GS_E_ARG,
-                    "gs_motif_run_batch_stats: burn_in outside [0, n_sweeps], thin < 1, or "
-                    "best_sweep_out without both best rows (or the reverse)");
+                    "gs_motif_run_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
+                    "best_sweep_out without both best rows (or the reverse), or half of a "
+                    "summary's output group");
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
@@ -1272,6 +1354,23 @@ int gs_motif_run_batch_stats(gs_ctx *c, int32_t W, double pc, double cutoff, int
                              int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
                              int32_t *best_pos_out, double *best_pwms_out) {
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out};
+    return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
+                                 init_mode, u, pos_inout, pwms_out, status_out, &st);
+}
+
+int gs_motif_run_batch_summary(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                               const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                               int32_t init_mode, const double *u, int32_t burn_in, int32_t thin,
+                               int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+                               int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
+                               int32_t *best_pos_out, double *best_pwms_out,
+                               int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
+                               int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out,
+                               int64_t *pool_counts_out, int32_t *n_pooled_out) {
+    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
+                         pool_mode_count_out, pool_counts_out, n_pooled_out};
+    const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
+                      &sum};
     return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
                                  init_mode, u, pos_inout, pwms_out, status_out, &st);
 }

@@ -3,7 +3,8 @@
 // (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch and, with the chains'
 // statistics, gs_motif_run_batch_stats, §9.25), run_multi_batch
 // (gs_motif_run_multi_batch and, with statistics, gs_motif_run_multi_batch_stats, §9.26) and
-// starts_batch (gs_random_starts_batch), over one copy of the
+// starts_batch (gs_random_starts_batch), and the chain summary's host side (SummaryRun,
+// occupancy_summary: gs_occupancy_summary and the ..._summary calls, §9.28), over one copy of the
 // stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
 // (set_snapshot_dev, starts_enqueue, starts_pass, greedy_carve, one_sweep) are in
 // gs_engine.cpp.
@@ -887,11 +888,20 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
             std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
         if (stats && stats->best_sweep_out)
             std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
+        if (stats && stats->sum) {
+            SummaryRun none(c);
+            none.R = R;
+            none.cells = (int64_t)c->A * W + c->A;
+            return none.download(*stats->sum);
+        }
         return GS_OK;
     }
     const int64_t H = stats ? occupancy_offsets(c, W, nullptr) : 0;
-    const bool st_occ = stats && stats->occ_out, st_ic = stats && stats->ic_out,
-               st_best = stats && stats->best_sweep_out;
+    // the bins are kept on the device for the caller or for the summary (§9.28), and come
+    // down only for the caller
+    const SummaryOut *sum = stats && stats->sum && stats->sum->any() ? stats->sum : nullptr;
+    const bool st_occ = stats && (stats->occ_out || sum), st_occ_down = stats && stats->occ_out,
+               st_ic = stats && stats->ic_out, st_best = stats && stats->best_sweep_out;
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
     GS_TRY(multi_lds_check(c, lds));
@@ -913,7 +923,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
             n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax +
             // the statistics: bins and their offsets, the trace, the running best and its rows
             (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) + (st_ic ? R * n_counted * 8 : 0) +
-            (st_best ? (int64_t)R * (16 + n * 12) : 0)));
+            (st_best ? (int64_t)R * (16 + n * 12) : 0) + (sum ? sum->bytes(R, n, cells) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     GS_TRY(multi_scratch(c, a, grid, 0));
     // the slabs (row r = chain r)
@@ -945,6 +955,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     DevBuf<int64_t> s_off, s_bsweep;
     DevBuf<double> s_ic, s_bic, s_bpwms;
     std::vector<int64_t> h_off;  // alive for the upload
+    SummaryRun srun(c);
     RunStatsArgs sa{};
     sa.n_chains = R;
     sa.n_local = (int32_t)n;
@@ -1052,6 +1063,8 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
             }
         }
         HIP_TRY(c, ev.mark());
+        // the reduction of the bins as the last statistics launch left them
+        if (sum) GS_TRY(srun.enqueue(W, s_occ, s_off, H, R, n_counted, *sum));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;
     }();
@@ -1074,12 +1087,16 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
                          : hipSuccess;
     };
-    if (st_occ) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
+    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
     if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
     if (st_best) {
         HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
         HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * 4));
         HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
+    }
+    if (sum) {
+        GS_TRY(srun.download(*sum));
+        srun.finish();
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return report_chain_errors(c, herr, status_out, nullptr);
@@ -1096,6 +1113,140 @@ int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off) {
     }
     if (off) off[c->n_local] = h;
     return h;
+}
+
+// The chain summary's device side.  One slab: the cells that start from
+// zero first (the chains' cells, the pooled cells, n_pooled: one memset), then the pooled
+// counts, the modes and the pooled flags.
+SummaryRun::~SummaryRun() {
+    if (slab) (void)hipStreamSynchronize(c->stream);
+    dfree(slab);
+    for (hipEvent_t e : ev)
+        if (e) c->ev_pool.push_back(e);
+}
+
+int SummaryRun::enqueue(int32_t W, const int32_t *d_occ, const int64_t *d_off, int64_t H,
+                        int32_t n_chains, int64_t n_counted, const SummaryOut &out) {
+    R = n_chains;
+    n = c->n_local;
+    cells = (int64_t)c->A * W + c->A;
+    c->summary_ms = 0.0;
+    if (R <= 0 || n <= 0 || !out.any()) return GS_OK;
+    const bool m = out.modes(), k = out.counts != nullptr, p = out.pool();
+    o_counts = 0;
+    o_pcounts = o_counts + (k ? R * cells * 8 : 0);
+    o_np = o_pcounts + (p ? cells * 8 : 0);
+    const int64_t zeroed = o_np + (p ? 8 : 0);
+    o_pcnt = zeroed;
+    o_mpos = o_pcnt + (p ? n * 8 : 0);
+    o_mcnt = o_mpos + (m ? R * n * 4 : 0);
+    o_ppos = o_mcnt + (m ? R * n * 4 : 0);
+    const int64_t o_flags = o_ppos + (p ? n * 4 : 0), bytes = o_flags + (p ? R * 4 : 0);
+    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(bytes, 8)));
+    if (zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)zeroed, c->stream));
+    SummaryArgs a{};
+    a.n_chains = n_chains;
+    a.n_local = c->n_local;
+    a.A = c->A;
+    a.W = W;
+    a.CS = c->E + 1;
+    a.H = H;
+    a.n_counted = n_counted;
+    a.occ = d_occ;
+    a.off = d_off;
+    a.seq = c->d_seq;
+    a.doff = c->d_doff;
+    a.comp = c->d_comp;
+    if (m) {
+        a.mode_pos = (int32_t *)(slab + o_mpos);
+        a.mode_count = (int32_t *)(slab + o_mcnt);
+    }
+    if (k) a.counts = (int64_t *)(slab + o_counts);
+    if (p) {
+        a.flags = (int32_t *)(slab + o_flags);
+        a.n_pooled = (int32_t *)(slab + o_np);
+        a.pool_pos = (int32_t *)(slab + o_ppos);
+        a.pool_count = (int64_t *)(slab + o_pcnt);
+        a.pool_counts = (int64_t *)(slab + o_pcounts);
+    }
+    // a wavefront a row, four a workgroup: eight rows a wavefront (a workgroup's cells cost
+    // up to A W + A atomic adds at its end) while the GPU is eight deep over all views (what
+    // its registers allow: a row is a chain of dependent loads, hidden by other rows only)
+    const int64_t views = R + (p ? 1 : 0);
+    const int blocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 31) / 32, std::max<int64_t>(1, (int64_t)c->n_cu * 8 / views)));
+    for (hipEvent_t &e : ev) e = get_event(c);
+    HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+    HIP_TRY(c, gs_summary_launch(a, blocks, c->stream));
+    HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+    return GS_OK;
+}
+
+int SummaryRun::download(const SummaryOut &out) {
+    if (R <= 0 || !out.any()) return GS_OK;
+    if (n <= 0) {  // no sequences: no modes; every chain's (empty) row sums to anything asked
+        if (out.counts) std::fill(out.counts, out.counts + R * cells, (int64_t)0);
+        if (out.pool()) {
+            std::fill(out.pool_counts, out.pool_counts + cells, (int64_t)0);
+            *out.n_pooled = (int32_t)R;
+        }
+        return GS_OK;
+    }
+    const auto down = [&](void *dst, int64_t o, int64_t bytes) -> hipError_t {
+        return hipMemcpyAsync(dst, slab + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
+    };
+    if (out.modes()) {
+        HIP_TRY(c, down(out.mode_pos, o_mpos, R * n * 4));
+        HIP_TRY(c, down(out.mode_count, o_mcnt, R * n * 4));
+    }
+    if (out.counts) HIP_TRY(c, down(out.counts, o_counts, R * cells * 8));
+    if (out.pool()) {
+        HIP_TRY(c, down(out.pool_pos, o_ppos, n * 4));
+        HIP_TRY(c, down(out.pool_count, o_pcnt, n * 8));
+        HIP_TRY(c, down(out.pool_counts, o_pcounts, cells * 8));
+        HIP_TRY(c, down(out.n_pooled, o_np, 4));
+    }
+    return GS_OK;
+}
+
+void SummaryRun::finish() {
+    float ms = 0.0f;
+    if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->summary_ms = ms;
+}
+
+// gs_occupancy_summary: the caller's bins up, the reduction, the result down (arguments
+// validated).  The context's snapshot and state are not touched.
+int occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
+                      const SummaryOut &out) {
+    const int64_t n = c->n_local;
+    SummaryRun run(c);
+    if (n == 0) {
+        run.R = R;
+        run.cells = (int64_t)c->A * W + c->A;
+        return run.download(out);
+    }
+    const int64_t H = occupancy_offsets(c, W, nullptr);
+    std::vector<int64_t> h_off((size_t)n + 1);
+    occupancy_offsets(c, W, h_off.data());
+    DevBuf<int32_t> d_occ;
+    DevBuf<int64_t> d_off;
+    GS_TRY(d_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
+    GS_TRY(d_off.alloc(c, n + 1));
+    int rc = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_occ, occ, (size_t)R * H * 4, hipMemcpyHostToDevice, c->stream));
+        GS_TRY(run.enqueue(W, d_occ, d_off, H, R, n_counted, out));
+        GS_TRY(run.download(out));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    if (rc) {  // nothing in flight on the slabs when they go
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    run.finish();
+    return GS_OK;
 }
 
 // R independent chains of T synchronous sweeps with Positions lists (any motifAmount),

@@ -4,6 +4,9 @@
 // chains' positions (or Positions lists) and PWMS rows and their skip words.  And the
 // consumer of the single chain's sweeps (gs_run_sweeps_stats, §9.27): one launch after a
 // counted sweep of any of the sweep kernels, which left d_pos, d_pwms and the error word.
+// And the reduction of the bins those launches filled to what a caller keeps of them (the
+// ..._summary calls and gs_occupancy_summary, §9.28): each sequence's first-maximum bin and the
+// count matrix over the counted states.
 #include "gs_ctx.h"
 #include "gs_wave.h"
 
@@ -296,5 +299,212 @@ hipError_t gs_run_stats_launch(const ChainStatsArgs &a, int bin_blocks, hipStrea
     if (a.best_sweep && !a.copy_inline)
         hipLaunchKernelGGL(gs_run_stats_best_kernel, dim3(std::min(1024, (a.n_local + 1023) / 1024)),
                            dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- Chain summaries (gs_occupancy_summary and the ..._summary run calls) ----
+// The reduction of the bins a chain's statistics launches filled (or a caller uploaded) to
+// what a caller keeps: each sequence's first-maximum bin with its count, and the count matrix
+// summed over the counted states.  Two launches at most: gs_summary_pool_kernel decides which
+// chains are pooled (only with the pooled outputs), gs_summary_kernel reads every row once.
+namespace {
+
+constexpr int kSumDepth = 4;  // wavefront loads of a row in flight ahead of the compares
+
+// Whether (c2, i2) comes before (c1, i1): count descending, bin index ascending.
+template <class T>
+__device__ __forceinline__ bool mode_before(T c2, int i2, T c1, int i1) {
+    return c2 > c1 || (c2 == c1 && i2 < i1);
+}
+
+// The first maximum over the 64 lanes' (count, smallest index with it), in every lane.
+template <class T>
+__device__ __forceinline__ void wave_first_max(T &cnt, int &idx) {
+    for (int o = 32; o >= 1; o >>= 1) {
+        const T c2 = __shfl_xor(cnt, o, 64);
+        const int i2 = __shfl_xor(idx, o, 64);
+        if (mode_before(c2, i2, cnt, idx)) {
+            cnt = c2;
+            idx = i2;
+        }
+    }
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The pooled view, one wavefront a sequence: the first maximum of the pooled chains' bins
+// summed in int64.  Lane l takes the bins l, l + 64, .. of the row in increasing order, so a
+// strict comparison keeps its first; no pooled chain leaves every sum 0, i.e. (-1, 0).
+__device__ __forceinline__ void summary_pooled_rows(const SummaryArgs &a, int blk, int nblk) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int n = blk * 4 + w; n < a.n_local; n += nblk * 4) {
+        const int64_t o = a.off[n];
+        const int len = (int)(a.off[n + 1] - o);
+        long long best = LLONG_MIN;
+        int bidx = INT_MAX;
+        for (int base = 0; base < len; base += 64 * kSumDepth) {
+            long long x[kSumDepth];
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) x[k] = 0;
+            for (int r = 0; r < a.n_chains; ++r) {
+                if (!a.flags[r]) continue;  // wavefront-uniform
+                const int32_t *row = a.occ + (int64_t)r * a.H + o;
+#pragma unroll
+                for (int k = 0; k < kSumDepth; ++k) {
+                    const int b = base + lane + 64 * k;
+                    x[k] += b < len ? row[b] : 0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) {
+                const int b = base + lane + 64 * k;
+                if (b < len && x[k] > best) {
+                    best = x[k];
+                    bidx = b;
+                }
+            }
+        }
+        wave_first_max(best, bidx);
+        if (lane == 0) {
+            a.pool_pos[n] = bidx - 1;
+            a.pool_count[n] = best;
+        }
+    }
+}
+
+}  // namespace
+
+// One workgroup a chain: whether the bins of local sequence 0 sum to n_counted
+// (ChainStats.finished), and the number of such chains.
+extern "C" __global__ void __launch_bounds__(256)
+gs_summary_pool_kernel(SummaryArgs a) {
+    __shared__ long long part[4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int64_t o = a.off[0];
+    const int len = (int)(a.off[1] - o);
+    const int32_t *row = a.occ + (int64_t)r * a.H + o;
+    long long s = 0;
+    for (int b = tid; b < len; b += 256) s += row[b];
+    s = wave_sum_i64(s);
+    if ((tid & 63) == 0) part[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        const int f = part[0] + part[1] + part[2] + part[3] == a.n_counted ? 1 : 0;
+        a.flags[r] = f;
+        if (f) atomicAdd(a.n_pooled, 1);
+    }
+}
+
+// gridDim.x / views workgroups a view: view v < n_chains is chain v, view n_chains (only with
+// the pooled outputs) the pooled modes.  A chain's view, one wavefront a
+// (chain, sequence) row, every row read once in coalesced wavefront loads, kSumDepth of them
+// issued ahead of the compares; a bin index is checked against the row's length before its
+// load.  Mode: lane l keeps (maximum, first index) over the bins l, l + 64, ..; the cross-lane
+// step orders by (count descending, index ascending).  Counts (asked for, or the chain is
+// pooled): a non-zero bin 1 + k with count c adds c to the W cells [s[k + j]][j] of the
+// workgroup's LDS copy (64-bit cells: a cell holds at most the sum of a workgroup's bins, each
+// below 2^31, far below 2^63), symbols outside the alphabet skipped as the sweeps' fold skips
+// them; per row S = the sum of its bins 1.., and S comp[n][a] goes to the copy's T cell a.
+// At the end T[a] loses the sum of its row of C (T_n[a] = S_n comp_n[a] - sum_j C_n[a][j]) and
+// every non-zero cell goes to the chain's cells, and for a pooled chain to the pooled ones, by
+// one 64-bit atomic add each.  Integer adds: the result does not depend on their order.  No
+// workgroup waits on another.  Negative bins are the caller's error: nothing is indexed by a
+// bin's value, so no access depends on them.
+extern "C" __global__ void __launch_bounds__(256)
+gs_summary_kernel(SummaryArgs a) {
+    extern __shared__ unsigned long long cell[];  // [A * W] C, then [A] T
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nblk = gridDim.x / (a.n_chains + (a.flags ? 1 : 0));
+    const int v = blockIdx.x / nblk, blk = blockIdx.x - v * nblk;
+    if (v == a.n_chains) {  // workgroup-uniform
+        summary_pooled_rows(a, blk, nblk);
+        return;
+    }
+    const int A = a.A, W = a.W, AW = A * W, cells = AW + A;
+    const bool pooled = a.flags && a.flags[v] != 0;
+    const bool want_cells = a.counts || pooled, want_mode = a.mode_pos != nullptr;
+    if (!want_cells && !want_mode) return;
+    if (want_cells) {
+        for (int i = tid; i < cells; i += 256) cell[i] = 0;
+        __syncthreads();
+    }
+    const int32_t *occ = a.occ + (int64_t)v * a.H;
+    for (int n = blk * 4 + w; n < a.n_local; n += nblk * 4) {
+        const int64_t o = a.off[n];
+        const int len = (int)(a.off[n + 1] - o);  // 1 + (L - W + 1) bins
+        const int32_t *row = occ + o;
+        const uint8_t *s = a.seq + a.doff[n];
+        int best = INT_MIN, bidx = INT_MAX;
+        long long S = 0;
+        for (int base = 0; base < len; base += 64 * kSumDepth) {
+            int32_t x[kSumDepth];
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) {
+                const int b = base + lane + 64 * k;
+                x[k] = b < len ? row[b] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) {
+                const int b = base + lane + 64 * k;
+                if (b >= len) continue;
+                if (x[k] > best) {
+                    best = x[k];
+                    bidx = b;
+                }
+                if (!want_cells || x[k] == 0 || b == 0) continue;
+                // start b - 1 <= L - W: the window stays inside the sequence
+                const unsigned long long c = (unsigned long long)(long long)x[k];
+                S += x[k];
+                // (the window's symbols eight loads at a time, so that the adds wait for a
+                // round trip a chunk and not one a symbol; j < W keeps every load inside it)
+                for (int j0 = 0; j0 < W; j0 += 8) {
+                    int sy[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) sy[i] = j0 + i < W ? s[b - 1 + j0 + i] : A;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        if (sy[i] < A) atomicAdd(&cell[sy[i] * W + j0 + i], c);
+                }
+            }
+        }
+        if (want_mode) {
+            wave_first_max(best, bidx);
+            if (lane == 0) {
+                a.mode_pos[(int64_t)v * a.n_local + n] = bidx - 1;
+                a.mode_count[(int64_t)v * a.n_local + n] = best;
+            }
+        }
+        if (want_cells) {
+            S = wave_sum_i64(S);
+            if (S != 0 && lane < A)
+                atomicAdd(&cell[AW + lane],
+                          (unsigned long long)(S * (long long)a.comp[(int64_t)n * a.CS + lane]));
+        }
+    }
+    if (!want_cells) return;
+    __syncthreads();
+    for (int i = tid; i < cells; i += 256) {
+        unsigned long long val = cell[i];
+        if (i >= AW)
+            for (int j = 0; j < W; ++j) val -= cell[(i - AW) * W + j];
+        if (val == 0) continue;
+        if (a.counts) atomicAdd((unsigned long long *)&a.counts[(int64_t)v * cells + i], val);
+        if (pooled) atomicAdd((unsigned long long *)&a.pool_counts[i], val);
+    }
+}
+
+// The pooled outputs go together (flags, n_pooled, pool_*): first the launch that decides the
+// pool, then blocks workgroups a view over the chains' views and the pooled one.  The cells
+// (counts, pool_counts) and n_pooled are zero at launch.
+hipError_t gs_summary_launch(const SummaryArgs &a, int blocks, hipStream_t s) {
+    if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
+    if (a.flags)
+        hipLaunchKernelGGL(gs_summary_pool_kernel, dim3(a.n_chains), dim3(256), 0, s, a);
+    const size_t lds = (size_t)(a.A * a.W + a.A) * 8;
+    hipLaunchKernelGGL(gs_summary_kernel, dim3(blocks * (a.n_chains + (a.flags ? 1 : 0))),
+                       dim3(256), lds, s, a);
     return hipGetLastError();
 }

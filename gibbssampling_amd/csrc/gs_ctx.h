@@ -256,6 +256,29 @@ struct ChainStatsArgs {
     double *best_pwms;           // [n_local]
 };
 hipError_t gs_run_stats_launch(const ChainStatsArgs &a, int bin_blocks, hipStream_t s);
+// The reduction of n_chains histograms for gs_summary_kernel (gs_chainstats.hip, DESIGN.md
+// §9.28): each sequence's first-maximum bin and the count matrix summed over the counted
+// states, per chain and pooled over the chains whose sequence 0 has n_counted counts.
+struct SummaryArgs {
+    int32_t n_chains, n_local;
+    int32_t A, W, CS;            // alphabet, motif length, entries a row of comp (E + 1)
+    int64_t H;                   // off[n_local]
+    int64_t n_counted;
+    const int32_t *occ;          // [n_chains][H]
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets
+    const uint8_t *seq;          // the encoded sequences (d_seq), sequence n at doff[n]
+    const int64_t *doff;
+    const int32_t *comp;         // [n_local][CS]: the sequences' symbol counts
+    int32_t *mode_pos;           // [n_chains][n_local], or null (goes with mode_count)
+    int32_t *mode_count;
+    int64_t *counts;             // [n_chains][A * W + A], zero at launch, or null
+    int32_t *flags;              // [n_chains]: the chain is pooled; null: no pooled outputs
+    int32_t *n_pooled;           // [1], zero at launch
+    int32_t *pool_pos;           // [n_local]
+    int64_t *pool_count;         // [n_local]
+    int64_t *pool_counts;        // [A * W + A], zero at launch
+};
+hipError_t gs_summary_launch(const SummaryArgs &a, int blocks, hipStream_t s);
 // What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
 // of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
 // names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
@@ -428,6 +451,7 @@ struct gs_ctx {
     double multi_batch_ms[3] = {0.0, 0.0, 0.0};  // the last list batch: starts, sweep, greedy passes
     double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
     double run_stats_ms[2] = {0.0, 0.0};  // the last gs_run_sweeps_stats: sweeps, statistics launches
+    double summary_ms = 0.0;  // the last chain summary's reduction (gs_summary_last_ms)
     double starts_batch_ms[2] = {0.0, 0.0};  // the last gs_random_starts_batch: counts / aggregates, scans
     double run_multi_batch_ms[2] = {0.0, 0.0};  // the last list chain batch (gs_motif_run_multi_batch): starts, sweeps
     int32_t run_multi_batch_info[4] = {0, 0, 0, 0};  // ... pairs rescored by overflow launches, chains parked, resume rounds, first arena
@@ -638,8 +662,58 @@ struct RunStats {
     int64_t *best_sweep_out;
     int32_t *best_pos_out;
     double *best_pwms_out;
-    bool any() const { return occ_out || ic_out || best_sweep_out; }
+    // gs_run_sweeps_summary / gs_motif_run_summary / gs_motif_run_batch_summary: the
+    // reduction of the bins (null: none)
+    const struct SummaryOut *sum = nullptr;
+    bool any() const;
 };
+// Where a chain summary goes, each group nullable as a whole: the chains'
+// modes, the chains' cells, the four pooled outputs.
+struct SummaryOut {
+    int32_t *mode_pos, *mode_count;  // [n_chains][n_local]
+    int64_t *counts;                 // [n_chains][A * W + A]
+    int32_t *pool_pos;               // [n_local]
+    int64_t *pool_count;             // [n_local]
+    int64_t *pool_counts;            // [A * W + A]
+    int32_t *n_pooled;               // [1]
+    bool modes() const { return mode_pos && mode_count; }
+    bool pool() const { return pool_pos && pool_count && pool_counts && n_pooled; }
+    bool any() const { return modes() || counts || pool(); }
+    // half of a group given
+    bool ragged() const {
+        return (mode_pos != nullptr) != (mode_count != nullptr) ||
+               ((pool_pos || pool_count || pool_counts || n_pooled) && !pool());
+    }
+    int64_t bytes(int64_t R, int64_t n, int64_t cells) const {
+        return (modes() ? R * n * 8 : 0) + (counts ? R * cells * 8 : 0) +
+               (pool() ? n * 12 + cells * 8 + R * 4 + 8 : 0);
+    }
+};
+inline bool RunStats::any() const {
+    return occ_out || ic_out || best_sweep_out || (sum && sum->any());
+}
+// The reduction of R histograms resident at d_occ ([R][H], bins of d_off) behind whatever is
+// on the stream: enqueue() allocates the result slab, zeroes its cells and launches between
+// two events; download() enqueues the copies to the caller's arrays; finish(), after the
+// caller's synchronisation, reads the device time into the context.  The slab lives until
+// the object goes, which the caller lets happen only with nothing in flight.
+struct SummaryRun {
+    gs_ctx *c;
+    char *slab = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t o_mpos = 0, o_mcnt = 0, o_counts = 0, o_ppos = 0, o_pcnt = 0, o_pcounts = 0, o_np = 0;
+    int64_t R = 0, n = 0, cells = 0;
+    explicit SummaryRun(gs_ctx *ctx) : c(ctx) {}
+    SummaryRun(const SummaryRun &) = delete;
+    SummaryRun &operator=(const SummaryRun &) = delete;
+    ~SummaryRun();
+    int enqueue(int32_t W, const int32_t *d_occ, const int64_t *d_off, int64_t H, int32_t R,
+                int64_t n_counted, const SummaryOut &out);
+    int download(const SummaryOut &out);
+    void finish();
+};
+int occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
+                      const SummaryOut &out);
 // (stats null, or with no output: gs_motif_run_batch)
 int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
               int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,

@@ -1089,8 +1089,11 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
     if ((rc = bg_resolve(c))) return rc;
     const int64_t n = c->n_local;
     const bool st_any = stats && stats->any() && n > 0;
-    const bool st_occ = st_any && stats->occ_out, st_ic = st_any && stats->ic_out,
-               st_best = st_any && stats->best_sweep_out;
+    // the bins are kept on the device for the caller or for the summary (§9.28), and come
+    // down only for the caller
+    const SummaryOut *sum = st_any && stats->sum && stats->sum->any() ? stats->sum : nullptr;
+    const bool st_occ = st_any && (stats->occ_out || sum), st_occ_down = st_any && stats->occ_out,
+               st_ic = st_any && stats->ic_out, st_best = st_any && stats->best_sweep_out;
     const auto counted = [&](int32_t t) {
         return st_any && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
     };
@@ -1112,6 +1115,7 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
             for (hipEvent_t e : ev) c->ev_pool.push_back(e);
         }
     } m{c};
+    SummaryRun srun(c);
     ChainStatsArgs sa{};
     const int64_t H = st_occ ? occupancy_offsets(c, c->W, nullptr) : 0;
     // (8-byte parts first: every part stays aligned to its element)
@@ -1199,6 +1203,9 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
         if (timed) HIP_TRY(c, mark());
     }
     if (stats) HIP_TRY(c, mark());
+    // the reduction of the bins as the last statistics launch left them
+    if (sum)
+        if ((rc = srun.enqueue(c->W, sa.occ, sa.off, H, 1, n_counted, *sum))) return rc;
     // the rest of the chain by the all-background kernel once a sweep saw the state
     if (n_sweeps > 0 && (rc = bg_check_note(c, pc, cutoff))) return rc;
     if (!stats) return GS_OK;
@@ -1206,7 +1213,9 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
         return bytes > 0 ? hipMemcpyAsync(dst, m.stat + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
                          : hipSuccess;
     };
-    if (st_occ) HIP_TRY(c, down(stats->occ_out, o_occ, H * 4));
+    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, o_occ, H * 4));
+    if (sum)
+        if ((rc = srun.download(*sum))) return rc;
     if (st_ic) HIP_TRY(c, down(stats->ic_out, o_ic, n_counted * 8));
     if (st_best) {
         HIP_TRY(c, down(stats->best_sweep_out, o_best + 8, 8));
@@ -1214,7 +1223,14 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
         HIP_TRY(c, down(stats->best_pwms_out, o_bpwms, n * 8));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (sum) srun.finish();
     if (n == 0) {  // no sequences: no bins, and no counted sweep completes
+        if (stats->sum) {
+            SummaryRun none(c);
+            none.R = 1;
+            none.cells = (int64_t)c->A * c->W + c->A;
+            (void)none.download(*stats->sum);
+        }
         if (stats->ic_out) std::fill(stats->ic_out, stats->ic_out + n_counted, std::nan(""));
         if (stats->best_sweep_out) *stats->best_sweep_out = -1;
     }

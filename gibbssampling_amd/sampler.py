@@ -174,6 +174,55 @@ class ChainStats:
 
 
 @dataclass
+class ChainSummary:
+    """What MotifSampler.runSweepsSummary / runSweepsBatchedSummary reduced on the device from
+    the occupancy of R chains (the single chain: R = 1), without the bins coming down.
+    mode_pos[R, N] / mode_count[R, N]: each chain's most frequent bin of every sequence minus
+    one (-1 = Positions []), the first among equals, and its count.  counts[R, A W + A]: each
+    chain's count matrix summed over its counted states (C[a W + j], then T[a], as
+    Context.counts).  pooled_pos[N], pooled_count[N], pooled_counts[A W + A]: the same over
+    the sum of the n_pooled finished chains' bins.  n_counted: the counted sweeps of a chain.
+    ic, best_sweep, best: as ChainStats.  occupancy / offsets: the bins, only when asked
+    for."""
+    mode_pos: np.ndarray
+    mode_count: np.ndarray
+    counts: np.ndarray
+    pooled_pos: np.ndarray
+    pooled_count: np.ndarray
+    pooled_counts: np.ndarray
+    n_pooled: int
+    n_counted: int
+    ic: np.ndarray
+    best_sweep: np.ndarray
+    best: list
+    motifLength: int
+    alphabetSize: int
+    occupancy: np.ndarray | None = None
+    offsets: np.ndarray | None = None
+
+    def mode(self) -> list[MotifIndex]:
+        """ChainStats.mode() of the same chains: each sequence's most frequent pooled bin, the
+        first among equals, its PWMS field the pooled frequency pooled_count / (n_pooled
+        n_counted), or 0 without a pooled counted state."""
+        den = float(int(self.n_pooled) * int(self.n_counted))
+        out = []
+        for p, k in zip(np.asarray(self.pooled_pos), np.asarray(self.pooled_count)):
+            f = float(np.float64(k) / den) if den > 0 else 0.0
+            out.append(createMotifIndex(f, [] if p < 0 else [int(p)]))
+        return out
+
+    def countMatrix(self, pool: bool = True):
+        """(C[A, W], T[A]) summed over the counted states of the pooled chains, or with
+        pool=False chain by chain: (C[R, A, W], T[R, A])."""
+        A, W = int(self.alphabetSize), int(self.motifLength)
+        if pool:
+            x = np.asarray(self.pooled_counts)
+            return x[:A * W].reshape(A, W), x[A * W:A * W + A]
+        x = np.asarray(self.counts)
+        return x[:, :A * W].reshape(-1, A, W), x[:, A * W:A * W + A]
+
+
+@dataclass
 class ListChainStats(ChainStats):
     """What MotifSampler.runSweepsBatchedListStats gathered over the counted sweeps of R
     chains of Positions lists: ChainStats, where bin offsets[n] counts the counted sweeps
@@ -306,6 +355,80 @@ class MotifSampler:
         stats = ChainStats(st["occupancy"][None, :], st.get("offsets", np.zeros(1, np.int64)),
                            st["ic"][None, :], st["best_sweep"], best)
         return _motif_indices(pos, pwms), stats
+
+    @staticmethod
+    def runSweepsSummary(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,
+                         motifMem: Sequence[MotifIndex], sweeps: int, burn_in: int = 0,
+                         thin: int = 1, seed: int = 0, first_sweep: int = 0, device: int = 0,
+                         occupancy: bool = False):
+        """runSweepsStats with the bins reduced on the device (Context.motif_run_summary) ->
+        (chain, ChainSummary with R = 1): where the motif is in each sequence and how often,
+        and the count matrix over the counted states, without the histogram coming down
+        (DESIGN.md §9.28).  occupancy=True also returns the bins.  A chain that raises raises
+        here."""
+        if len(motifMem) != len(sources):
+            raise _native.ArgumentError(_native.GS_E_ARG, "motifMem and sources differ in length")
+        if not _is_single(1, motifMem):
+            raise _native.ArgumentError(_native.GS_E_ARG,
+                                        "the chain statistics need single positions")
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, st = ctx.motif_run_summary(motifLength, pseudoCount, cutOff, sweeps,
+                                              int(seed) & (2**64 - 1), _single_positions(motifMem),
+                                              first_sweep, burn_in=burn_in, thin=thin,
+                                              occupancy=occupancy)
+        best = [_motif_indices(st["best_pos"], st["best_pwms"]) if st["best_sweep"][0] >= 0
+                else []]
+        n_counted = st["ic"].shape[0]
+        # the single chain finished (a raise raised above): it is the pool
+        summary = ChainSummary(st["mode_pos"][None, :], st["mode_count"][None, :],
+                               st["counts"][None, :], st["mode_pos"],
+                               st["mode_count"].astype(np.int64), st["counts"], 1, n_counted,
+                               st["ic"][None, :], st["best_sweep"], best, int(motifLength),
+                               len(alphabet_codes(alphabet)),
+                               st["occupancy"][None, :] if occupancy else None,
+                               st.get("offsets") if occupancy else None)
+        return _motif_indices(pos, pwms), summary
+
+    @staticmethod
+    def runSweepsBatchedSummary(motifLength: int, pseudoCount: float, cutOff: float, alphabet,
+                                sources, sweeps: int, seeds, motifMems=None, init_mode: int = 0,
+                                first_sweep: int = 0, burn_in: int = 0, thin: int = 1,
+                                device: int = 0, motifAmount: int = 1, occupancy: bool = False):
+        """runSweepsBatchedStats with the bins reduced on the device
+        (Context.motif_run_batch_summary) -> (chains, ChainSummary): every chain's modes and
+        count matrix and those pooled over the finished chains.  occupancy=True also returns
+        the bins.  motifAmount 1 with single positions only."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if motifAmount != 1:
+            raise _native.ArgumentError(_native.GS_E_ARG,
+                                        "the chain statistics need motifAmount = 1")
+        pos = None
+        if motifMems is not None:
+            if len(motifMems) != len(seeds):
+                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+            if any(len(m) != len(sources) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "a motifMem and sources differ in length")
+            if not all(_is_single(1, m) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "the chain statistics need single positions")
+            pos = np.array([_single_positions(m) for m in motifMems],
+                           np.int32).reshape(len(seeds), len(sources))
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, status, st = ctx.motif_run_batch_summary(
+            motifLength, pseudoCount, cutOff, sweeps, seeds, pos, init_mode, first_sweep,
+            burn_in=burn_in, thin=thin, occupancy=occupancy)
+        _raise_failed_chain(status)
+        R = len(seeds)
+        best = [_motif_indices(st["best_pos"][r], st["best_pwms"][r]) if st["best_sweep"][r] >= 0
+                else [] for r in range(R)]
+        summary = ChainSummary(st["mode_pos"], st["mode_count"], st["counts"], st["pooled_pos"],
+                               st["pooled_count"], st["pooled_counts"], int(st["n_pooled"][0]),
+                               st["ic"].shape[1], st["ic"], st["best_sweep"], best,
+                               int(motifLength), len(alphabet_codes(alphabet)),
+                               st["occupancy"] if occupancy else None,
+                               st.get("offsets") if occupancy else None)
+        return [_motif_indices(pos[r], pwms[r]) for r in range(R)], summary
 
     @staticmethod
     def runSweepsBatched(motifLength: int, pseudoCount: float, cutOff: float, alphabet, sources,

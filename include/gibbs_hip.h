@@ -348,6 +348,75 @@ int gs_motif_run_stats(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_o
  * rest; without it out[1] is 0. */
 int gs_run_stats_last_ms(const gs_ctx *ctx, double out[2]);
 
+/* Chain summaries: the reduction of occupancy histograms on the device to what a caller keeps
+ * of them (motifAmount 1, the bins of gs_occupancy_offsets(ctx, W, off); A = the alphabet's
+ * length).  Per chain r and sequence n the mode: b* is the smallest bin index within the
+ * sequence's row whose count is the row's maximum (the first maximum, the .fsx's
+ * countBy |> sortByDescending |> head, .fsx:384-388); mode_pos_out[r][n] = b* - 1 (-1 means
+ * Positions []), mode_count_out[r][n] that count; a row of zeros gives (-1, 0).  Per chain the
+ * mean count matrix times the counted states, counts_out[r][A*W + A] in gs_counts' layout, C
+ * then T: C[a*W + j] = sum over n, k of occ[r][off[n]+1+k] where sequence n has alphabet[a] at
+ * k + j; T[a] = sum over n, k of occ[r][off[n]+1+k] times the number of alphabet[a] in sequence
+ * n outside [k, k+W).  For bins that a chain filled this is exactly the sum of gs_counts over
+ * the counted states; a symbol outside the alphabet counts wherever gs_counts counts it, and
+ * nowhere else.  Pooled: chain r is pooled when the bins of local sequence 0 sum to n_counted
+ * (a chain that raised stopped counting); n_pooled_out[0] is their number,
+ * pool_mode_pos_out[n] / pool_mode_count_out[n] the first maximum of the pooled chains' bins
+ * summed in int64, pool_counts_out the sum of the pooled chains' cells; with no pooled chain
+ * (-1, 0) everywhere and zero cells.  Integer sums only: the results are the same on every run.
+ * Each output group is nullable as a whole: the mode pair, the counts, the pooled four.
+ * gs_occupancy_summary reduces caller-held bins (sums of several calls, of several processes'
+ * chains): it uploads occ, reduces and downloads.  It needs sequences (else GS_E_STATE) but no
+ * snapshot, and leaves the context's snapshot untouched.  GS_E_ARG: a bad W, occ null with
+ * n_chains > 0, n_chains < 0, n_counted < 0, half of a group given.  n_chains == 0 does
+ * nothing.  GS_E_UNSUPPORTED: sharded sequences or a communicator, or bins and results beyond
+ * 4 GiB.  Negative bins are the caller's error: the result is unspecified, without a fault. */
+int gs_occupancy_summary(gs_ctx *ctx, int32_t W,
+        const int32_t *occ,            /* [n_chains][H]                        */
+        int32_t n_chains, int64_t n_counted,
+        int32_t *mode_pos_out,         /* [n_chains][n_local], nullable        */
+        int32_t *mode_count_out,       /* [n_chains][n_local], with the above  */
+        int64_t *counts_out,           /* [n_chains][A*W + A], nullable        */
+        int32_t *pool_mode_pos_out,    /* [n_local], nullable with the next 3  */
+        int64_t *pool_mode_count_out,  /* [n_local]                            */
+        int64_t *pool_counts_out,      /* [A*W + A]                            */
+        int32_t *n_pooled_out          /* [1]                                  */);
+/* gs_run_sweeps_stats / gs_motif_run_stats with the single chain's summary appended
+ * (mode_pos_out[n_local], mode_count_out[n_local], counts_out[A*W + A], nullable as above).
+ * The bins stay on the device whenever occ_out or a summary output is asked for and are
+ * downloaded only when occ_out is non-null; the reduction is one launch behind the last
+ * statistics launch, before the call's single synchronisation.  Everything else is the stats
+ * call's contract: the chain, the other statistics, the refusals (half of a summary group:
+ * GS_E_ARG), the state left on the context, the error rule: after a raise in sweep t the
+ * summary is that of the bins as they stand and the status is returned.  With the three
+ * summary outputs null the call is the stats call, bit for bit. */
+int gs_run_sweeps_summary(gs_ctx *ctx, double pseudo_count, double cut_off, int32_t n_sweeps,
+        uint64_t seed, int64_t first_sweep, const double *u, int32_t burn_in, int32_t thin,
+        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+        double *best_pwms_out,
+        int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out);
+int gs_motif_run_summary(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+        int32_t n_sweeps, uint64_t seed, int64_t first_sweep, const double *u,
+        int32_t burn_in, int32_t thin, int32_t *pos_inout, double *pwms_out,
+        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+        double *best_pwms_out,
+        int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out);
+/* gs_motif_run_batch_stats with the per-chain and the pooled outputs of gs_occupancy_summary
+ * appended; n_counted is the call's own, so a chain that raised is left out of the pool.  The
+ * extra slabs count toward the 4 GiB of chain slabs. */
+int gs_motif_run_batch_summary(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+        int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+        int32_t init_mode, const double *u, int32_t burn_in, int32_t thin,
+        int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+        double *best_pwms_out,
+        int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
+        int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+        int32_t *n_pooled_out);
+/* Device time of the last summary's reduction (any of the four calls above), ms, between two
+ * events around its launches; 0 when nothing was reduced. */
+int gs_summary_last_ms(const gs_ctx *ctx, double out[1]);
+
 /* R independent chains of n_sweeps synchronous sweeps each with Positions lists (any
  * motifAmount) in one call: chain r is exactly n_sweeps calls of gs_motif_sweep_multi(ctx,
  * motif_amount, W, pc, cut_off, cap, ...), each fed the previous output.  init_mode -1:
