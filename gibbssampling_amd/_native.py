@@ -188,6 +188,9 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
         "gs_motif_run_multi_batch_stats": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32,
                                                      i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp, vp, vp]),
+        "gs_list_occupancy_summary": (C.c_int, [vp, i32, i32, vp, vp, i32, i64] + [vp] * 13),
+        "gs_motif_run_multi_batch_summary": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64,
+                                                       i32, i32, vp, i32, i32] + [vp] * 24),
         "gs_motif_run_multi": (C.c_int, [vp, i32, i32, f64, f64, i32, u64, i64, i32, vp, vp, vp]),
         "gs_run_multi_batch_last_ms": (C.c_int, [vp, vp]),
         "gs_run_multi_batch_last_info": (C.c_int, [vp, vp]),
@@ -988,6 +991,113 @@ class Context:
             _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")))
         if st != GS_OK and (strict or not status.any()):
             self._check(st)
+        return cnt, pos, pwms, status, stats
+
+    _LIST_SUMMARY_KEYS = ("mode_sites", "mode_sites_count", "mode_cnt", "mode_pos", "mode_count",
+                          "counts", "pooled_sites", "pooled_sites_count", "pooled_cnt",
+                          "pooled_pos", "pooled_count", "pooled_counts", "n_pooled")
+
+    def _list_summary_outputs(self, W, M, R, modes, counts, pool):
+        """The output arrays of a list chain summary of R chains -> dict (the library's order:
+        _LIST_SUMMARY_KEYS)."""
+        A = len(getattr(self, "_keep", (None, None, ()))[2])  # the alphabet's length
+        cells = A * int(W) + A if W is not None else 0
+        N, M = self.n_local, max(int(M), 0)
+        out = {}
+        if modes:
+            out["mode_sites"] = np.zeros((R, N), np.int32)
+            out["mode_sites_count"] = np.zeros((R, N), np.int32)
+            out["mode_cnt"] = np.zeros((R, N), np.int32)
+            out["mode_pos"] = np.full((R, N, M), -1, np.int32)
+            out["mode_count"] = np.zeros((R, N, M), np.int32)
+        if counts:
+            out["counts"] = np.zeros((R, max(cells, 0)), np.int64)
+        if pool:
+            out["pooled_sites"] = np.zeros(N, np.int32)
+            out["pooled_sites_count"] = np.zeros(N, np.int64)
+            out["pooled_cnt"] = np.zeros(N, np.int32)
+            out["pooled_pos"] = np.full((N, M), -1, np.int32)
+            out["pooled_count"] = np.zeros((N, M), np.int64)
+            out["pooled_counts"] = np.zeros(max(cells, 0), np.int64)
+            out["n_pooled"] = np.zeros(1, np.int32)
+        return out
+
+    def list_occupancy_summary(self, W: int, motif_amount: int, occupancy, sites, n_counted: int,
+                               modes: bool = True, counts: bool = True,
+                               pool: bool = True) -> dict:
+        """The reduction of caller-held list histograms occupancy[R, H] and site counts
+        sites[R, N, motif_amount + 1] (a motif_run_multi_batch_stats call's, or the sums of
+        several) on the device (gs_list_occupancy_summary) -> dict of the groups asked for.
+        Per chain: "mode_sites"[R, N], the first most frequent site count c of every sequence,
+        with "mode_sites_count"[R, N]; "mode_cnt"[R, N], "mode_pos"[R, N, M] and
+        "mode_count"[R, N, M]: the c most occupied starts pairwise more than W apart, taken
+        greedily (the first among equals), ascending, -1 / 0 past mode_cnt; "counts"[R, A W +
+        A], the count matrix summed over the counted states in counts()' layout.  Pooled over
+        the chains every sequence of which has n_counted site counts: "pooled_sites"[N],
+        "pooled_sites_count"[N] (int64), "pooled_cnt"[N], "pooled_pos"[N, M],
+        "pooled_count"[N, M] (int64), "pooled_counts"[A W + A] and "n_pooled"[1]."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.int32)
+        sites = np.ascontiguousarray(sites, dtype=np.int32)
+        H, M = int(self.lib.gs_occupancy_size(self.h, int(W))), int(motif_amount)
+        if occ.ndim != 2 or (H >= 0 and occ.shape[1] != H):
+            raise ArgumentError(GS_E_ARG, "occupancy needs the shape [chains, bins]")
+        R = occ.shape[0]
+        if 1 <= M <= 16 and sites.shape != (R, self.n_local, M + 1):
+            raise ArgumentError(GS_E_ARG,
+                                "sites needs the shape [chains, sequences, motif_amount + 1]")
+        out = self._list_summary_outputs(W if H >= 0 else None, M, R, modes, counts, pool)
+        self._check(self.lib.gs_list_occupancy_summary(
+            self.h, int(W), M, _ptr(occ) if R > 0 else None, _ptr(sites) if R > 0 else None, R,
+            int(n_counted), *(_ptr(out.get(k)) for k in self._LIST_SUMMARY_KEYS)))
+        return out
+
+    def motif_run_multi_batch_summary(self, motif_amount: int, W: int, pc: float, cutoff: float,
+                                      n_sweeps: int, seeds, cnt=None, pos=None,
+                                      init_mode: int = 0, first_sweep: int = 0,
+                                      cap: int | None = None, u=None, burn_in: int = 0,
+                                      thin: int = 1, occupancy: bool = False,
+                                      sites: bool = False, ic: bool = True, best: bool = True,
+                                      modes: bool = True, counts: bool = True, pool: bool = True,
+                                      strict: bool = False):
+        """motif_run_multi_batch_stats with the chains' list summaries and the pooled one
+        reduced on the device (gs_motif_run_multi_batch_summary) -> (cnt[R, N], pos[R, N, cap],
+        pwms[R, N], status[R], stats), stats with the groups of list_occupancy_summary besides
+        those of motif_run_multi_batch_stats and "n_counted".  The bins and the site counts are
+        downloaded only with occupancy=True / sites=True."""
+        seeds, cnt, pos, init_mode, cap, u = self._run_multi_batch_args(
+            motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u)
+        R, T, M = len(seeds), int(n_sweeps), int(motif_amount)
+        burn_in, thin = int(burn_in), int(thin)
+        ok = 0 <= burn_in <= T and thin >= 1
+        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        stats = {}
+        H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+        if occupancy:
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
+        if sites:
+            stats["sites"] = np.zeros((R, self.n_local, max(M, 0) + 1), np.int32)
+        if ic:
+            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(R, -1, np.int64)
+            stats["best_cnt"] = np.zeros((R, self.n_local), np.int32)
+            stats["best_pos"] = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
+            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats.update(self._list_summary_outputs(W if H >= 0 else None, M, R, modes, counts, pool))
+        st = self.lib.gs_motif_run_multi_batch_summary(
+            self.h, M, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
+            int(init_mode), cap, _ptr(u), burn_in, thin, _ptr(cnt), _ptr(pos), _ptr(pwms),
+            _ptr(status), _ptr(stats.get("occupancy")), _ptr(stats.get("sites")),
+            _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")), _ptr(stats.get("best_cnt")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")),
+            *(_ptr(stats.get(k)) for k in self._LIST_SUMMARY_KEYS))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        stats["n_counted"] = n_counted
         return cnt, pos, pwms, status, stats
 
     def motif_run_multi(self, motif_amount: int, W: int, pc: float, cutoff: float, n_sweeps: int,

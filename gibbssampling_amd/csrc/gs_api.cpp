@@ -1398,10 +1398,12 @@ static int motif_run_multi_batch_entry(gs_ctx *c, int32_t motif_amount, int32_t 
         const bool rows = st->best_cnt_out && st->best_pos_out && st->best_pwms_out;
         const bool any_row = st->best_cnt_out || st->best_pos_out || st->best_pwms_out;
         if (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
-            (st->best_sweep_out != nullptr) != rows || (!st->best_sweep_out && any_row))
+            (st->best_sweep_out != nullptr) != rows || (!st->best_sweep_out && any_row) ||
+            (st->sum && st->sum->ragged()))
             return fail(c, GS_E_ARG,
                         "gs_motif_run_multi_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
-                        "or best_sweep_out without all three best rows (or the reverse)");
+                        "best_sweep_out without all three best rows (or the reverse), or half of "
+                        "a summary's output group");
     }
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!cnt_inout || !pos_inout || !pwms_out))) return GS_E_ARG;
@@ -1447,6 +1449,74 @@ int gs_motif_run_multi_batch_stats(gs_ctx *c, int32_t motif_amount, int32_t W, d
     return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
                                        first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
                                        pwms_out, status_out, &st);
+}
+
+int gs_motif_run_multi_batch_summary(
+    gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+    const uint64_t *seeds, int32_t n_chains, int64_t first_sweep, int32_t init_mode, int32_t cap,
+    const double *u, int32_t burn_in, int32_t thin, int32_t *cnt_inout, int32_t *pos_inout,
+    double *pwms_out, int32_t *status_out, int32_t *occ_out, int32_t *sites_out, double *ic_out,
+    int64_t *best_sweep_out, int32_t *best_cnt_out, int32_t *best_pos_out, double *best_pwms_out,
+    int32_t *mode_sites_out, int32_t *mode_sites_count_out, int32_t *mode_cnt_out,
+    int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
+    int32_t *pool_mode_sites_out, int64_t *pool_mode_sites_count_out, int32_t *pool_mode_cnt_out,
+    int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+    int32_t *n_pooled_out) {
+    const ListSummaryOut sum{mode_sites_out,      mode_sites_count_out,
+                             mode_cnt_out,        mode_pos_out,
+                             mode_count_out,      counts_out,
+                             pool_mode_sites_out, pool_mode_sites_count_out,
+                             pool_mode_cnt_out,   pool_mode_pos_out,
+                             pool_mode_count_out, pool_counts_out,
+                             n_pooled_out};
+    const RunMultiStats st{burn_in,        thin,         occ_out,      sites_out,     ic_out,
+                           best_sweep_out, best_cnt_out, best_pos_out, best_pwms_out, &sum};
+    return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
+                                       first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
+                                       pwms_out, status_out, &st);
+}
+
+int gs_list_occupancy_summary(gs_ctx *c, int32_t W, int32_t motif_amount, const int32_t *occ,
+                              const int32_t *sites, int32_t n_chains, int64_t n_counted,
+                              int32_t *mode_sites_out, int32_t *mode_sites_count_out,
+                              int32_t *mode_cnt_out, int32_t *mode_pos_out,
+                              int32_t *mode_count_out, int64_t *counts_out,
+                              int32_t *pool_mode_sites_out, int64_t *pool_mode_sites_count_out,
+                              int32_t *pool_mode_cnt_out, int32_t *pool_mode_pos_out,
+                              int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+                              int32_t *n_pooled_out) {
+    if (!c) return GS_E_ARG;
+    const ListSummaryOut out{mode_sites_out,      mode_sites_count_out,
+                             mode_cnt_out,        mode_pos_out,
+                             mode_count_out,      counts_out,
+                             pool_mode_sites_out, pool_mode_sites_count_out,
+                             pool_mode_cnt_out,   pool_mode_pos_out,
+                             pool_mode_count_out, pool_counts_out,
+                             n_pooled_out};
+    if (n_chains < 0 || n_counted < 0 || (n_chains > 0 && (!occ || !sites)) ||
+        motif_amount < 1 || motif_amount > kMultiMaxAmount || out.ragged())
+        return fail(c, GS_E_ARG,
+                    "gs_list_occupancy_summary: n_chains < 0, n_counted < 0, no bins or site "
+                    "counts, motifAmount outside [1, 16], or half of an output group");
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_list_occupancy_summary: the cells are summed over every sequence: it needs "
+                    "all sequences on one device and no communicator");
+    if (n_chains == 0) return GS_OK;
+    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
+    const int64_t bytes = (int64_t)n_chains * (H + n * ((int64_t)motif_amount + 1)) * 4 +
+                          (n + 1) * 8 +
+                          out.bytes(n_chains, n, (int64_t)c->A * W + c->A, motif_amount);
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_list_occupancy_summary: the slabs and the results take " +
+                        std::to_string(bytes) + " B, more than the " +
+                        std::to_string(kBatchBytesMax) +
+                        " B a call may hold: split the chains over several calls");
+    return list_occupancy_summary(c, W, motif_amount, occ, sites, n_chains, n_counted, out);
 }
 
 int gs_motif_run_multi(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,

@@ -1249,6 +1249,170 @@ int occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64
     return GS_OK;
 }
 
+// The list chain summary's device side, as SummaryRun's: one slab, the cells
+// that start from zero first (one memset), then the 64-bit pooled outputs, then the 32-bit
+// ones and the pooled flags.
+ListSummaryRun::~ListSummaryRun() {
+    if (slab) (void)hipStreamSynchronize(c->stream);
+    dfree(slab);
+    for (hipEvent_t e : ev)
+        if (e) c->ev_pool.push_back(e);
+}
+
+int ListSummaryRun::enqueue(int32_t W, int32_t motif_amount, const int32_t *d_occ,
+                            const int32_t *d_sites, const int64_t *d_off, int64_t H,
+                            int32_t n_chains, int64_t n_counted, const ListSummaryOut &out) {
+    R = n_chains;
+    n = c->n_local;
+    M = motif_amount;
+    cells = (int64_t)c->A * W + c->A;
+    c->summary_ms = 0.0;
+    if (R <= 0 || n <= 0 || !out.any()) return GS_OK;
+    const bool m = out.modes(), k = out.counts != nullptr, p = out.pool();
+    int64_t bytes = 0;
+    const auto take = [&](bool wanted, int64_t b) {
+        const int64_t o = bytes;
+        if (wanted) bytes += (b + 7) / 8 * 8;
+        return o;
+    };
+    o_counts = take(k, R * cells * 8);
+    o_pcounts = take(p, cells * 8);
+    o_np = take(p, 8);
+    const int64_t zeroed = bytes;
+    o_psc = take(p, n * 8);
+    o_pcount = take(p, n * M * 8);
+    o_ms = take(m, R * n * 4);
+    o_msc = take(m, R * n * 4);
+    o_mcnt = take(m, R * n * 4);
+    o_mpos = take(m, R * n * M * 4);
+    o_mcount = take(m, R * n * M * 4);
+    o_ps = take(p, n * 4);
+    o_pcnt = take(p, n * 4);
+    o_ppos = take(p, n * M * 4);
+    const int64_t o_flags = take(p, R * 4);
+    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(bytes, 8)));
+    if (zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)zeroed, c->stream));
+    ListSummaryArgs a{};
+    a.n_chains = n_chains;
+    a.n_local = c->n_local;
+    a.A = c->A;
+    a.W = W;
+    a.CS = c->E + 1;
+    a.M = motif_amount;
+    a.H = H;
+    a.n_counted = n_counted;
+    a.occ = d_occ;
+    a.sites = d_sites;
+    a.off = d_off;
+    a.seq = c->d_seq;
+    a.doff = c->d_doff;
+    a.comp = c->d_comp;
+    if (m) {
+        a.mode_sites = (int32_t *)(slab + o_ms);
+        a.mode_sites_count = (int32_t *)(slab + o_msc);
+        a.mode_cnt = (int32_t *)(slab + o_mcnt);
+        a.mode_pos = (int32_t *)(slab + o_mpos);
+        a.mode_count = (int32_t *)(slab + o_mcount);
+    }
+    if (k) a.counts = (int64_t *)(slab + o_counts);
+    if (p) {
+        a.flags = (int32_t *)(slab + o_flags);
+        a.n_pooled = (int32_t *)(slab + o_np);
+        a.pool_sites = (int32_t *)(slab + o_ps);
+        a.pool_sites_count = (int64_t *)(slab + o_psc);
+        a.pool_cnt = (int32_t *)(slab + o_pcnt);
+        a.pool_pos = (int32_t *)(slab + o_ppos);
+        a.pool_count = (int64_t *)(slab + o_pcount);
+        a.pool_counts = (int64_t *)(slab + o_pcounts);
+    }
+    // (the grid of SummaryRun::enqueue: a wavefront a row, eight rows a wavefront, the GPU
+    // eight deep over all views)
+    const int64_t views = R + (p ? 1 : 0);
+    const int blocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>((n + 31) / 32, std::max<int64_t>(1, (int64_t)c->n_cu * 8 / views)));
+    for (hipEvent_t &e : ev) e = get_event(c);
+    HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+    HIP_TRY(c, gs_list_summary_launch(a, blocks, c->stream));
+    HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+    return GS_OK;
+}
+
+int ListSummaryRun::download(const ListSummaryOut &out) {
+    if (R <= 0 || !out.any()) return GS_OK;
+    if (n <= 0) {  // no sequences: no rows; every chain's (empty) site rows sum to anything asked
+        if (out.counts) std::fill(out.counts, out.counts + R * cells, (int64_t)0);
+        if (out.pool()) {
+            std::fill(out.pool_counts, out.pool_counts + cells, (int64_t)0);
+            *out.n_pooled = (int32_t)R;
+        }
+        return GS_OK;
+    }
+    const auto down = [&](void *dst, int64_t o, int64_t bytes) -> hipError_t {
+        return hipMemcpyAsync(dst, slab + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
+    };
+    if (out.modes()) {
+        HIP_TRY(c, down(out.mode_sites, o_ms, R * n * 4));
+        HIP_TRY(c, down(out.mode_sites_count, o_msc, R * n * 4));
+        HIP_TRY(c, down(out.mode_cnt, o_mcnt, R * n * 4));
+        HIP_TRY(c, down(out.mode_pos, o_mpos, R * n * M * 4));
+        HIP_TRY(c, down(out.mode_count, o_mcount, R * n * M * 4));
+    }
+    if (out.counts) HIP_TRY(c, down(out.counts, o_counts, R * cells * 8));
+    if (out.pool()) {
+        HIP_TRY(c, down(out.pool_sites, o_ps, n * 4));
+        HIP_TRY(c, down(out.pool_sites_count, o_psc, n * 8));
+        HIP_TRY(c, down(out.pool_cnt, o_pcnt, n * 4));
+        HIP_TRY(c, down(out.pool_pos, o_ppos, n * M * 4));
+        HIP_TRY(c, down(out.pool_count, o_pcount, n * M * 8));
+        HIP_TRY(c, down(out.pool_counts, o_pcounts, cells * 8));
+        HIP_TRY(c, down(out.n_pooled, o_np, 4));
+    }
+    return GS_OK;
+}
+
+void ListSummaryRun::finish() {
+    float ms = 0.0f;
+    if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->summary_ms = ms;
+}
+
+// gs_list_occupancy_summary: the caller's bins and site counts up, the reduction, the result
+// down (arguments validated).  The context's snapshot and state are not touched.
+int list_occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ,
+                           const int32_t *sites, int32_t R, int64_t n_counted,
+                           const ListSummaryOut &out) {
+    const int64_t n = c->n_local;
+    ListSummaryRun run(c);
+    if (n == 0) {
+        run.R = R;
+        run.cells = (int64_t)c->A * W + c->A;
+        return run.download(out);
+    }
+    const int64_t H = occupancy_offsets(c, W, nullptr), S = (int64_t)R * n * (M + 1);
+    std::vector<int64_t> h_off((size_t)n + 1);
+    occupancy_offsets(c, W, h_off.data());
+    DevBuf<int32_t> d_occ, d_sites;
+    DevBuf<int64_t> d_off;
+    GS_TRY(d_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
+    GS_TRY(d_sites.alloc(c, S));
+    GS_TRY(d_off.alloc(c, n + 1));
+    int rc = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_occ, occ, (size_t)R * H * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_sites, sites, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
+        GS_TRY(run.enqueue(W, M, d_occ, d_sites, d_off, H, R, n_counted, out));
+        GS_TRY(run.download(out));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    if (rc) {  // nothing in flight on the slabs when they go
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    run.finish();
+    return GS_OK;
+}
+
 // R independent chains of T synchronous sweeps with Positions lists (any motifAmount),
 // DESIGN.md §9.19.  Stage 1: the chains' lists, uploaded (mode -1) or their starts as
 // one-position lists as in multi_batch; then the aggregates of every chain's lists.  Stage 2:
@@ -1285,9 +1449,19 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
             std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
         if (stats && stats->best_sweep_out)
             std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
+        if (stats && stats->sum) {
+            ListSummaryRun none(c);
+            none.R = R;
+            none.cells = (int64_t)c->A * W + c->A;
+            return none.download(*stats->sum);
+        }
         return GS_OK;
     }
-    const bool st_occ = stats && stats->occ_out, st_sites = stats && stats->sites_out,
+    // the bins and site counts are kept on the device for the caller or for the summary
+    // (§9.29), and come down only for the caller
+    const ListSummaryOut *sum = stats && stats->sum && stats->sum->any() ? stats->sum : nullptr;
+    const bool st_occ = stats && (stats->occ_out || sum), st_sites = stats && (stats->sites_out || sum),
+               st_occ_down = stats && stats->occ_out, st_sites_down = stats && stats->sites_out,
                st_ic = stats && stats->ic_out, st_best = stats && stats->best_sweep_out;
     const int64_t H = st_occ ? occupancy_offsets(c, W, nullptr) : 0;
     MultiArgs a{};
@@ -1341,7 +1515,8 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
             // best and its rows
             (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) +
             (st_sites ? rows * ((int64_t)M + 1) * 4 : 0) + (st_ic ? R * n_counted * 8 : 0) +
-            (st_best ? (int64_t)R * 16 + rows * (4 + 4 * (int64_t)cap + 8) : 0)));
+            (st_best ? (int64_t)R * 16 + rows * (4 + 4 * (int64_t)cap + 8) : 0) +
+            (sum ? sum->bytes(R, n, cells, M) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     {  // the first round's arenas, so that no sweep waits for an allocation
         MultiArgs sized = a;
@@ -1382,6 +1557,7 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
     DevBuf<int64_t> s_off, s_bsweep;
     DevBuf<double> s_ic, s_bic, s_bpwms;
     std::vector<int64_t> h_off;  // alive for the upload
+    ListSummaryRun srun(c);
     RunMultiStatsArgs sa{};
     sa.n_local = (int32_t)n;
     sa.cap = cap;
@@ -1602,6 +1778,9 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
             }
         }
         HIP_TRY(c, ev.mark());
+        // the reduction of the bins and site counts as the last round's last statistics
+        // launch left them
+        if (sum) GS_TRY(srun.enqueue(W, M, s_occ, s_sites, s_off, H, R, n_counted, *sum));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;
     }();
@@ -1627,14 +1806,18 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
                          : hipSuccess;
     };
-    if (st_occ) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
-    if (st_sites) HIP_TRY(c, down(stats->sites_out, s_sites, rows * (M + 1) * 4));
+    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
+    if (st_sites_down) HIP_TRY(c, down(stats->sites_out, s_sites, rows * (M + 1) * 4));
     if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
     if (st_best) {
         HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
         HIP_TRY(c, down(stats->best_cnt_out, s_bcnt, rows * 4));
         HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * cap * 4));
         HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
+    }
+    if (sum) {
+        GS_TRY(srun.download(*sum));
+        srun.finish();
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int32_t r = 0; r < R; ++r)

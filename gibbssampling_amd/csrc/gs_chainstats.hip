@@ -335,6 +335,61 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     return v;
 }
 
+// The count matrix of a workgroup's rows (gs_summary_kernel and gs_list_summary_kernel): an LDS
+// copy of 64-bit cells, [A * W] C then [A] T, zeroed by cells_clear, filled a bin at a time by
+// cells_bin and a row at a time by cells_row, and added to the chain's and the pooled cells
+// by cells_flush.  A cell holds at most the sum of a workgroup's bins, each below 2^31, far
+// below 2^63.
+__device__ __forceinline__ void cells_clear(unsigned long long *cell, int cells) {
+    for (int i = threadIdx.x; i < cells; i += 256) cell[i] = 0;
+    __syncthreads();
+}
+
+// Bin b >= 1 (start b - 1 <= L - W: the window stays inside the sequence) with count x: x to
+// the W cells [s[b - 1 + j]][j], symbols outside the alphabet skipped as the sweeps' fold skips
+// them, and to the row's sum S.  A zero bin and bin 0 add nothing.
+__device__ __forceinline__ void cells_bin(unsigned long long *cell, const uint8_t *s, int b,
+                                          int32_t x, int A, int W, long long &S) {
+    if (x == 0 || b == 0) return;
+    const unsigned long long c = (unsigned long long)(long long)x;
+    S += x;
+    // (the window's symbols eight loads at a time, so that the adds wait for a round trip a
+    // chunk and not one a symbol; j < W keeps every load inside it)
+    for (int j0 = 0; j0 < W; j0 += 8) {
+        int sy[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sy[i] = j0 + i < W ? s[b - 1 + j0 + i] : A;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (sy[i] < A) atomicAdd(&cell[sy[i] * W + j0 + i], c);
+    }
+}
+
+// The row's share of T, by its wavefront: S comp[a] over the lanes' sums S of bins 1.. .
+__device__ __forceinline__ void cells_row(unsigned long long *cell, const int32_t *comp,
+                                          long long S, int lane, int A, int AW) {
+    S = wave_sum_i64(S);
+    if (S != 0 && lane < A)
+        atomicAdd(&cell[AW + lane], (unsigned long long)(S * (long long)comp[lane]));
+}
+
+// The workgroup's cells, T[a] less the sum of its row of C (T_n[a] = S_n comp_n[a] -
+// sum_j C_n[a][j]), every non-zero one by one 64-bit atomic add to the chain's cells (counts,
+// nullable) and to the pooled ones (pool_counts, nullable).
+__device__ __forceinline__ void cells_flush(const unsigned long long *cell, int A, int W,
+                                            int64_t *counts, int64_t *pool_counts) {
+    const int AW = A * W;
+    __syncthreads();
+    for (int i = threadIdx.x; i < AW + A; i += 256) {
+        unsigned long long val = cell[i];
+        if (i >= AW)
+            for (int j = 0; j < W; ++j) val -= cell[(i - AW) * W + j];
+        if (val == 0) continue;
+        if (counts) atomicAdd((unsigned long long *)&counts[i], val);
+        if (pool_counts) atomicAdd((unsigned long long *)&pool_counts[i], val);
+    }
+}
+
 // The pooled view, one wavefront a sequence: the first maximum of the pooled chains' bins
 // summed in int64.  Lane l takes the bins l, l + 64, .. of the row in increasing order, so a
 // strict comparison keeps its first; no pooled chain leaves every sum 0, i.e. (-1, 0).
@@ -427,10 +482,7 @@ gs_summary_kernel(SummaryArgs a) {
     const bool pooled = a.flags && a.flags[v] != 0;
     const bool want_cells = a.counts || pooled, want_mode = a.mode_pos != nullptr;
     if (!want_cells && !want_mode) return;
-    if (want_cells) {
-        for (int i = tid; i < cells; i += 256) cell[i] = 0;
-        __syncthreads();
-    }
+    if (want_cells) cells_clear(cell, cells);
     const int32_t *occ = a.occ + (int64_t)v * a.H;
     for (int n = blk * 4 + w; n < a.n_local; n += nblk * 4) {
         const int64_t o = a.off[n];
@@ -454,20 +506,7 @@ gs_summary_kernel(SummaryArgs a) {
                     best = x[k];
                     bidx = b;
                 }
-                if (!want_cells || x[k] == 0 || b == 0) continue;
-                // start b - 1 <= L - W: the window stays inside the sequence
-                const unsigned long long c = (unsigned long long)(long long)x[k];
-                S += x[k];
-                // (the window's symbols eight loads at a time, so that the adds wait for a
-                // round trip a chunk and not one a symbol; j < W keeps every load inside it)
-                for (int j0 = 0; j0 < W; j0 += 8) {
-                    int sy[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) sy[i] = j0 + i < W ? s[b - 1 + j0 + i] : A;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-                        if (sy[i] < A) atomicAdd(&cell[sy[i] * W + j0 + i], c);
-                }
+                if (want_cells) cells_bin(cell, s, b, x[k], A, W, S);
             }
         }
         if (want_mode) {
@@ -477,23 +516,11 @@ gs_summary_kernel(SummaryArgs a) {
                 a.mode_count[(int64_t)v * a.n_local + n] = best;
             }
         }
-        if (want_cells) {
-            S = wave_sum_i64(S);
-            if (S != 0 && lane < A)
-                atomicAdd(&cell[AW + lane],
-                          (unsigned long long)(S * (long long)a.comp[(int64_t)n * a.CS + lane]));
-        }
+        if (want_cells) cells_row(cell, a.comp + (int64_t)n * a.CS, S, lane, A, AW);
     }
     if (!want_cells) return;
-    __syncthreads();
-    for (int i = tid; i < cells; i += 256) {
-        unsigned long long val = cell[i];
-        if (i >= AW)
-            for (int j = 0; j < W; ++j) val -= cell[(i - AW) * W + j];
-        if (val == 0) continue;
-        if (a.counts) atomicAdd((unsigned long long *)&a.counts[(int64_t)v * cells + i], val);
-        if (pooled) atomicAdd((unsigned long long *)&a.pool_counts[i], val);
-    }
+    cells_flush(cell, A, W, a.counts ? a.counts + (int64_t)v * cells : nullptr,
+                pooled ? a.pool_counts : nullptr);
 }
 
 // The pooled outputs go together (flags, n_pooled, pool_*): first the launch that decides the
@@ -505,6 +532,239 @@ hipError_t gs_summary_launch(const SummaryArgs &a, int blocks, hipStream_t s) {
         hipLaunchKernelGGL(gs_summary_pool_kernel, dim3(a.n_chains), dim3(256), 0, s, a);
     const size_t lds = (size_t)(a.A * a.W + a.A) * 8;
     hipLaunchKernelGGL(gs_summary_kernel, dim3(blocks * (a.n_chains + (a.flags ? 1 : 0))),
+                       dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+// ---- List summaries (gs_list_occupancy_summary and gs_motif_run_multi_batch_summary, DESIGN.md
+// §9.29) ----
+// The reduction of the bins and site counts of Positions-list chains (the statistics launches
+// of §9.26 filled them, or a caller uploaded them) to what ListChainStats.mode() and a count
+// matrix keep: per sequence the modal site count c*, then c* rounds that each take the most
+// occupied start (the first among equals) not within W of a start already taken
+// (ceckForDistance, .fs:129-140), in ascending order; and the cells of §9.28, which are the
+// list aggregates' sum.  Two launches at most: gs_list_summary_pool_kernel decides which chains
+// are pooled (only with the pooled outputs), gs_list_summary_kernel reduces every row.
+namespace {
+
+// Bins of a row a wavefront keeps in LDS for its rounds (a longer row is read again a round)
+constexpr int kListStageBins = 512;
+
+template <class T>
+__device__ __forceinline__ constexpr T list_lowest() {
+    return sizeof(T) == 4 ? (T)INT_MIN : (T)LLONG_MIN;
+}
+
+// kSumDepth wavefront loads of a view's row from bin `base` on, all issued ahead of their use:
+// chain v's bins (T = int32_t), or for the pooled view (T = int64_t) the pooled chains' bins
+// summed in int64.  A bin index is checked against the row's length before its load.
+template <class T>
+__device__ __forceinline__ void list_load(const ListSummaryArgs &a, int v, int64_t o, int len,
+                                          int base, int lane, T (&x)[kSumDepth]) {
+    if constexpr (sizeof(T) == 4) {
+        const int32_t *row = a.occ + (int64_t)v * a.H + o;
+#pragma unroll
+        for (int k = 0; k < kSumDepth; ++k) {
+            const int b = base + lane + 64 * k;
+            x[k] = b < len ? row[b] : 0;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kSumDepth; ++k) x[k] = 0;
+        for (int r = 0; r < a.n_chains; ++r) {
+            if (!a.flags[r]) continue;  // wavefront-uniform
+            const int32_t *row = a.occ + (int64_t)r * a.H + o;
+            // (every load issued, at an index clamped into the row, and the value past the end
+            // dropped where it is added: a branch around a load makes the widening of its
+            // value, and so the wait, part of the branch, one round trip a load)
+            int32_t y[kSumDepth];
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) y[k] = row[min(base + lane + 64 * k, len - 1)];
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) x[k] += base + lane + 64 * k < len ? y[k] : 0;
+        }
+    }
+}
+
+// visit(b, x) for every bin b of the row with its count x: lane l sees the bins l, l + 64, ..
+// in increasing order.
+template <class T, class F>
+__device__ __forceinline__ void list_scan(const ListSummaryArgs &a, int v, int64_t o, int len,
+                                          int lane, F visit) {
+    for (int base = 0; base < len; base += 64 * kSumDepth) {
+        T x[kSumDepth];
+        list_load(a, v, o, len, base, lane, x);
+#pragma unroll
+        for (int k = 0; k < kSumDepth; ++k) {
+            const int b = base + lane + 64 * k;
+            if (b < len) visit(b, x[k]);
+        }
+    }
+}
+
+// One (view, sequence) row by one wavefront.  The row is read once: every bin goes to the
+// workgroup's cells (cell non-null: a chain's view that wants them) and, when the row fits,
+// into the wavefront's LDS stage, bin b by the lane b mod 64 that reads it again in the
+// rounds, so that no lane reads what another wrote.  The site counts: lane l <= M holds
+// count l, the first maximum across the wavefront is c*.  A round: every lane keeps the
+// first maximum over its free starts, the wavefront takes the first maximum of those; lane i
+// keeps the i-th start taken and its count, and a start is free when it is more than W from
+// every one of them, read by a uniform-index lane read.  The rounds end when no lane has a
+// free start.  At the end lane i ranks its start among those taken and writes it there.
+// Nothing is indexed by a bin's or a site count's value.
+template <class T>
+__device__ __forceinline__ void list_row(const ListSummaryArgs &a, int v, int n, int lane,
+                                         T *stage, unsigned long long *cell, int32_t *o_sites,
+                                         T *o_sites_count, int32_t *o_cnt, int32_t *o_pos,
+                                         T *o_count) {
+    const int64_t o = a.off[n];
+    const int len = (int)(a.off[n + 1] - o);  // 1 + (L - W + 1) bins
+    const int M = a.M, W = a.W;
+    const bool fits = len <= kListStageBins, want_mode = o_sites != nullptr;
+    if (cell || (fits && want_mode)) {
+        const uint8_t *s = a.seq + a.doff[n];
+        long long S = 0;
+        list_scan<T>(a, v, o, len, lane, [&](int b, T x) {
+            if (fits) stage[b] = x;
+            if constexpr (sizeof(T) == 4)
+                if (cell) cells_bin(cell, s, b, x, a.A, W, S);
+        });
+        if constexpr (sizeof(T) == 4)
+            if (cell) cells_row(cell, a.comp + (int64_t)n * a.CS, S, lane, a.A, a.A * W);
+    }
+    if (!want_mode) return;
+    // the modal site count
+    T sc = list_lowest<T>();
+    int si = INT_MAX;
+    if (lane <= M) {
+        si = lane;
+        if constexpr (sizeof(T) == 4) {
+            sc = a.sites[((int64_t)v * a.n_local + n) * (M + 1) + lane];
+        } else {
+            sc = 0;
+            for (int r = 0; r < a.n_chains; ++r)
+                if (a.flags[r]) sc += a.sites[((int64_t)r * a.n_local + n) * (M + 1) + lane];
+        }
+    }
+    wave_first_max(sc, si);
+    const int cstar = __builtin_amdgcn_readfirstlane(si);
+    // the rounds
+    int taken = 0, ntaken = 0;  // lane i < ntaken: the i-th start taken, and its count
+    T tcount = 0;
+    for (int round = 0; round < cstar; ++round) {
+        T best = list_lowest<T>();
+        int bidx = INT_MAX;
+        const auto cand = [&](int b, T x) {
+            if (b == 0) return;
+            const int k = b - 1;
+            bool is_free = true;
+            for (int q = 0; q < ntaken; ++q) {
+                const int d = k - __builtin_amdgcn_readlane(taken, q);
+                is_free = is_free && (d > W || d < -W);
+            }
+            if (is_free && (bidx == INT_MAX || x > best)) {
+                best = x;
+                bidx = k;
+            }
+        };
+        if (fits) {
+            for (int b = lane; b < len; b += 64) cand(b, stage[b]);
+        } else {
+            list_scan<T>(a, v, o, len, lane, cand);
+        }
+        wave_first_max(best, bidx);
+        if (__builtin_amdgcn_readfirstlane(bidx) == INT_MAX) break;  // every start excluded
+        if (lane == ntaken) {
+            taken = bidx;
+            tcount = best;
+        }
+        ++ntaken;
+    }
+    // ascending starts: the rank of a lane's start among the (distinct) starts taken
+    int rank = 0;
+    for (int q = 0; q < ntaken; ++q) rank += __builtin_amdgcn_readlane(taken, q) < taken ? 1 : 0;
+    if (lane == 0) {
+        o_sites[n] = cstar;
+        o_sites_count[n] = sc;
+        o_cnt[n] = ntaken;
+    }
+    if (lane < M) {
+        const bool t = lane < ntaken;
+        const int64_t slot = (int64_t)n * M + (t ? rank : lane);
+        o_pos[slot] = t ? taken : -1;
+        o_count[slot] = t ? tcount : (T)0;
+    }
+}
+
+}  // namespace
+
+// One workgroup a chain: whether every sequence's site counts sum to n_counted
+// (ListChainStats.finished), and the number of such chains.
+extern "C" __global__ void __launch_bounds__(256)
+gs_list_summary_pool_kernel(ListSummaryArgs a) {
+    __shared__ int short_rows;
+    const int r = blockIdx.x, tid = threadIdx.x, m1 = a.M + 1;
+    if (tid == 0) short_rows = 0;
+    __syncthreads();
+    const int32_t *sites = a.sites + (int64_t)r * a.n_local * m1;
+    bool bad = false;
+    for (int n = tid; n < a.n_local; n += 256) {
+        long long s = 0;
+        for (int i = 0; i < m1; ++i) s += sites[(int64_t)n * m1 + i];
+        bad = bad || s != a.n_counted;
+    }
+    if (bad) atomicOr(&short_rows, 1);
+    __syncthreads();
+    if (tid == 0) {
+        const int f = short_rows ? 0 : 1;
+        a.flags[r] = f;
+        if (f) atomicAdd(a.n_pooled, 1);
+    }
+}
+
+// gridDim.x / views workgroups a view, as gs_summary_kernel: view v < n_chains is chain v, view
+// n_chains (only with the pooled outputs) the pooled one, whose bins and site counts are the
+// pooled chains' summed in int64 (once, into the stage, when the row fits).  One wavefront a
+// (view, sequence) row (list_row).  A chain's view also fills the workgroup's cells
+// (cells_bin / cells_row / cells_flush: gs_summary_kernel's arithmetic) when its counts are
+// asked for or the chain is pooled.  Dynamic LDS: the cells, then kListStageBins 64-bit
+// entries a wavefront.  Integer sums only; no workgroup waits on another.
+extern "C" __global__ void __launch_bounds__(256)
+gs_list_summary_kernel(ListSummaryArgs a) {
+    extern __shared__ unsigned long long cell[];  // [A * W] C, [A] T, then the four stages
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nblk = gridDim.x / (a.n_chains + (a.flags ? 1 : 0));
+    const int v = blockIdx.x / nblk, blk = blockIdx.x - v * nblk;
+    const int cells = a.A * a.W + a.A;
+    int64_t *stage = (int64_t *)(cell + cells) + w * kListStageBins;
+    if (v == a.n_chains) {  // workgroup-uniform
+        for (int n = blk * 4 + w; n < a.n_local; n += nblk * 4)
+            list_row<int64_t>(a, v, n, lane, stage, nullptr, a.pool_sites, a.pool_sites_count,
+                              a.pool_cnt, a.pool_pos, a.pool_count);
+        return;
+    }
+    const bool pooled = a.flags && a.flags[v] != 0;
+    const bool want_cells = a.counts || pooled, want_mode = a.mode_sites != nullptr;
+    if (!want_cells && !want_mode) return;
+    if (want_cells) cells_clear(cell, cells);
+    const int64_t vrow = (int64_t)v * a.n_local;
+    for (int n = blk * 4 + w; n < a.n_local; n += nblk * 4)
+        list_row<int32_t>(a, v, n, lane, (int32_t *)stage, want_cells ? cell : nullptr,
+                          want_mode ? a.mode_sites + vrow : nullptr, a.mode_sites_count + vrow,
+                          a.mode_cnt + vrow, a.mode_pos + vrow * a.M, a.mode_count + vrow * a.M);
+    if (want_cells)
+        cells_flush(cell, a.A, a.W, a.counts ? a.counts + (int64_t)v * cells : nullptr,
+                    pooled ? a.pool_counts : nullptr);
+}
+
+// As gs_summary_launch: the pooled outputs go together, the cells and n_pooled are zero at
+// launch.
+hipError_t gs_list_summary_launch(const ListSummaryArgs &a, int blocks, hipStream_t s) {
+    if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
+    if (a.flags)
+        hipLaunchKernelGGL(gs_list_summary_pool_kernel, dim3(a.n_chains), dim3(256), 0, s, a);
+    const size_t lds = (size_t)(a.A * a.W + a.A) * 8 + (size_t)4 * kListStageBins * 8;
+    hipLaunchKernelGGL(gs_list_summary_kernel, dim3(blocks * (a.n_chains + (a.flags ? 1 : 0))),
                        dim3(256), lds, s, a);
     return hipGetLastError();
 }

@@ -279,6 +279,37 @@ struct SummaryArgs {
     int64_t *pool_counts;        // [A * W + A], zero at launch
 };
 hipError_t gs_summary_launch(const SummaryArgs &a, int blocks, hipStream_t s);
+// The reduction of n_chains list histograms for gs_list_summary_kernel (gs_chainstats.hip,
+// DESIGN.md §9.29): each sequence's modal site count, that many most occupied starts pairwise
+// more than W apart, and the count matrix summed over the counted states; per chain and
+// pooled over the chains every sequence of which has n_counted site counts.
+struct ListSummaryArgs {
+    int32_t n_chains, n_local;
+    int32_t A, W, CS, M;         // alphabet, motif length, entries a row of comp (E + 1), motifAmount
+    int64_t H;                   // off[n_local]
+    int64_t n_counted;
+    const int32_t *occ;          // [n_chains][H]
+    const int32_t *sites;        // [n_chains][n_local][M + 1]
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets
+    const uint8_t *seq;          // the encoded sequences (d_seq), sequence n at doff[n]
+    const int64_t *doff;
+    const int32_t *comp;         // [n_local][CS]: the sequences' symbol counts
+    int32_t *mode_sites;         // [n_chains][n_local], or null (the five go together)
+    int32_t *mode_sites_count;   // [n_chains][n_local]
+    int32_t *mode_cnt;           // [n_chains][n_local]
+    int32_t *mode_pos;           // [n_chains][n_local][M]
+    int32_t *mode_count;         // [n_chains][n_local][M]
+    int64_t *counts;             // [n_chains][A * W + A], zero at launch, or null
+    int32_t *flags;              // [n_chains]: the chain is pooled; null: no pooled outputs
+    int32_t *n_pooled;           // [1], zero at launch
+    int32_t *pool_sites;         // [n_local]
+    int64_t *pool_sites_count;   // [n_local]
+    int32_t *pool_cnt;           // [n_local]
+    int32_t *pool_pos;           // [n_local][M]
+    int64_t *pool_count;         // [n_local][M]
+    int64_t *pool_counts;        // [A * W + A], zero at launch
+};
+hipError_t gs_list_summary_launch(const ListSummaryArgs &a, int blocks, hipStream_t s);
 // What gs_motif_run_multi_batch adds to MultiArgs (gs_multi.hip): R chains
 // of Positions lists side by side, one sweep of all chains a launch.  The MultiArgs beside it
 // names the list slabs' bases (cnt_in / pos_in: the snapshot, cnt_out / pos_out: the next
@@ -721,6 +752,60 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
 int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off);
 int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
                  double *score_out, int32_t *pos_out, int32_t *status_out);
+// Where a list chain summary goes, each group nullable as a whole: the
+// chains' modes (five arrays), the chains' cells, the seven pooled outputs.
+struct ListSummaryOut {
+    int32_t *mode_sites, *mode_sites_count, *mode_cnt;  // [n_chains][n_local]
+    int32_t *mode_pos, *mode_count;                     // [n_chains][n_local][M]
+    int64_t *counts;                                    // [n_chains][A * W + A]
+    int32_t *pool_sites;                                // [n_local]
+    int64_t *pool_sites_count;                          // [n_local]
+    int32_t *pool_cnt;                                  // [n_local]
+    int32_t *pool_pos;                                  // [n_local][M]
+    int64_t *pool_count;                                // [n_local][M]
+    int64_t *pool_counts;                               // [A * W + A]
+    int32_t *n_pooled;                                  // [1]
+    bool modes() const {
+        return mode_sites && mode_sites_count && mode_cnt && mode_pos && mode_count;
+    }
+    bool pool() const {
+        return pool_sites && pool_sites_count && pool_cnt && pool_pos && pool_count &&
+               pool_counts && n_pooled;
+    }
+    bool any() const { return modes() || counts || pool(); }
+    // half of a group given
+    bool ragged() const {
+        return ((mode_sites || mode_sites_count || mode_cnt || mode_pos || mode_count) && !modes()) ||
+               ((pool_sites || pool_sites_count || pool_cnt || pool_pos || pool_count ||
+                 pool_counts || n_pooled) && !pool());
+    }
+    int64_t bytes(int64_t R, int64_t n, int64_t cells, int64_t M) const {
+        return (modes() ? R * n * (12 + 8 * M) : 0) + (counts ? R * cells * 8 : 0) +
+               (pool() ? n * (16 + 12 * M) + cells * 8 + R * 4 + 8 : 0);
+    }
+};
+// SummaryRun for list bins: the reduction of R list histograms resident at d_occ ([R][H]) and
+// d_sites ([R][n][M + 1]) behind whatever is on the stream.
+struct ListSummaryRun {
+    gs_ctx *c;
+    char *slab = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t o_counts = 0, o_pcounts = 0, o_np = 0, o_psc = 0, o_pcount = 0, o_ms = 0, o_msc = 0,
+            o_mcnt = 0, o_mpos = 0, o_mcount = 0, o_ps = 0, o_pcnt = 0, o_ppos = 0;
+    int64_t R = 0, n = 0, cells = 0, M = 0;
+    explicit ListSummaryRun(gs_ctx *ctx) : c(ctx) {}
+    ListSummaryRun(const ListSummaryRun &) = delete;
+    ListSummaryRun &operator=(const ListSummaryRun &) = delete;
+    ~ListSummaryRun();
+    int enqueue(int32_t W, int32_t M, const int32_t *d_occ, const int32_t *d_sites,
+                const int64_t *d_off, int64_t H, int32_t R, int64_t n_counted,
+                const ListSummaryOut &out);
+    int download(const ListSummaryOut &out);
+    void finish();
+};
+int list_occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ,
+                           const int32_t *sites, int32_t R, int64_t n_counted,
+                           const ListSummaryOut &out);
 // The caller's side of gs_motif_run_multi_batch_stats (each statistic nullable; the three
 // best rows go with best_sweep_out).
 struct RunMultiStats {
@@ -730,7 +815,11 @@ struct RunMultiStats {
     int64_t *best_sweep_out;
     int32_t *best_cnt_out, *best_pos_out;
     double *best_pwms_out;
-    bool any() const { return occ_out || sites_out || ic_out || best_sweep_out; }
+    // gs_motif_run_multi_batch_summary: the reduction of the bins and site counts (null: none)
+    const ListSummaryOut *sum = nullptr;
+    bool any() const {
+        return occ_out || sites_out || ic_out || best_sweep_out || (sum && sum->any());
+    }
 };
 // (stats null, or with no output: gs_motif_run_multi_batch)
 int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,

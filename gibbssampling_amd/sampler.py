@@ -289,6 +289,65 @@ class ListChainStats(ChainStats):
         return out
 
 
+@dataclass
+class ListChainSummary:
+    """What MotifSampler.runSweepsBatchedListSummary reduced on the device from the bins and site
+    counts of R chains of Positions lists, without either coming down.
+    mode_sites[R, N] / mode_sites_count[R, N]: each chain's most frequent number of sites of
+    every sequence, the first among equals, and how often.  mode_cnt[R, N], mode_pos[R, N, M],
+    mode_count[R, N, M]: that many most occupied starts pairwise more than motifLength apart,
+    taken greedily (the first among equals), in ascending order, with their bins; -1 / 0 past
+    mode_cnt.  counts[R, A W + A]: each chain's count matrix summed over its counted states
+    (C[a W + j], then T[a], as Context.counts).  pooled_*: the same over the sums of the
+    n_pooled finished chains' bins and site counts.  n_counted: the counted sweeps of a chain.
+    ic, best_sweep, best: as ListChainStats.  occupancy / offsets / sites: the bins and site
+    counts, only when asked for."""
+    mode_sites: np.ndarray
+    mode_sites_count: np.ndarray
+    mode_cnt: np.ndarray
+    mode_pos: np.ndarray
+    mode_count: np.ndarray
+    counts: np.ndarray
+    pooled_sites: np.ndarray
+    pooled_sites_count: np.ndarray
+    pooled_cnt: np.ndarray
+    pooled_pos: np.ndarray
+    pooled_count: np.ndarray
+    pooled_counts: np.ndarray
+    n_pooled: int
+    n_counted: int
+    ic: np.ndarray
+    best_sweep: np.ndarray
+    best: list
+    motifLength: int
+    alphabetSize: int
+    occupancy: np.ndarray | None = None
+    offsets: np.ndarray | None = None
+    sites: np.ndarray | None = None
+
+    def mode(self) -> list[MotifIndex]:
+        """ListChainStats.mode() of the same chains: per sequence the pooled list, its PWMS
+        field the pooled frequency of its number of sites, pooled_sites_count / (n_pooled
+        n_counted), or 0 without a pooled counted state."""
+        den = float(int(self.n_pooled) * int(self.n_counted))
+        out = []
+        for k, c, p in zip(np.asarray(self.pooled_sites_count), np.asarray(self.pooled_cnt),
+                           np.asarray(self.pooled_pos)):
+            f = float(np.float64(k) / den) if den > 0 else 0.0
+            out.append(createMotifIndex(f, [int(q) for q in p[:int(c)]]))
+        return out
+
+    def countMatrix(self, pool: bool = True):
+        """(C[A, W], T[A]) summed over the counted states of the pooled chains, or with
+        pool=False chain by chain: (C[R, A, W], T[R, A])."""
+        A, W = int(self.alphabetSize), int(self.motifLength)
+        if pool:
+            x = np.asarray(self.pooled_counts)
+            return x[:A * W].reshape(A, W), x[A * W:A * W + A]
+        x = np.asarray(self.counts)
+        return x[:, :A * W].reshape(-1, A, W), x[:, A * W:A * W + A]
+
+
 class MotifSampler:
     """MotifSampler module (.fs:709-1038): the hot-path entry points."""
 
@@ -532,6 +591,44 @@ class MotifSampler:
         stats = ListChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)),
                                st["ic"], st["best_sweep"], best, st["sites"], int(motifLength))
         return [_motif_lists(cnt[r], pos[r], pwms[r]) for r in range(R)], stats
+
+    @staticmethod
+    def runSweepsBatchedListSummary(motifLength: int, pseudoCount: float, cutOff: float, alphabet,
+                                    sources, sweeps: int, seeds, motifMems=None,
+                                    init_mode: int = 0, first_sweep: int = 0, burn_in: int = 0,
+                                    thin: int = 1, device: int = 0, motifAmount: int = 1,
+                                    occupancy: bool = False):
+        """runSweepsBatchedListStats with the bins and site counts reduced on the device
+        (Context.motif_run_multi_batch_summary) -> (chains, ListChainSummary): every chain's
+        modal lists and count matrix and those pooled over the finished chains, what
+        ListChainStats.mode() and a count matrix over the counted states give, without the
+        slabs coming down.  occupancy=True also returns the bins and the
+        site counts."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if motifMems is not None:
+            if len(motifMems) != len(seeds):
+                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+            if any(len(m) != len(sources) for m in motifMems):
+                raise _native.ArgumentError(_native.GS_E_ARG,
+                                            "a motifMem and sources differ in length")
+        cap, cnt, pos = _chain_lists(motifAmount, motifMems, len(sources))
+        ctx = _bind(alphabet, sources, device)
+        cnt, pos, pwms, status, st = ctx.motif_run_multi_batch_summary(
+            motifAmount, motifLength, pseudoCount, cutOff, sweeps, seeds, cnt, pos, init_mode,
+            first_sweep, cap, burn_in=burn_in, thin=thin, occupancy=occupancy, sites=occupancy)
+        _raise_failed_chain(status)
+        R = len(seeds)
+        best = [_motif_lists(st["best_cnt"][r], st["best_pos"][r], st["best_pwms"][r])
+                if st["best_sweep"][r] >= 0 else [] for r in range(R)]
+        summary = ListChainSummary(
+            st["mode_sites"], st["mode_sites_count"], st["mode_cnt"], st["mode_pos"],
+            st["mode_count"], st["counts"], st["pooled_sites"], st["pooled_sites_count"],
+            st["pooled_cnt"], st["pooled_pos"], st["pooled_count"], st["pooled_counts"],
+            int(st["n_pooled"][0]), st["ic"].shape[1], st["ic"], st["best_sweep"], best,
+            int(motifLength), len(alphabet_codes(alphabet)),
+            st["occupancy"] if occupancy else None, st.get("offsets") if occupancy else None,
+            st["sites"] if occupancy else None)
+        return [_motif_lists(cnt[r], pos[r], pwms[r]) for r in range(R)], summary
 
     @staticmethod
     def findBestMotifIndicesWithStartPositions(motifAmount: int, motifLength: int,

@@ -499,6 +499,75 @@ int gs_motif_run_multi_batch_stats(gs_ctx *ctx, int32_t motif_amount, int32_t W,
         int32_t *best_cnt_out,   /* [n_chains][n_local]                              */
         int32_t *best_pos_out,   /* [n_chains][n_local][cap], F# list order, -1 past cnt */
         double  *best_pwms_out   /* [n_chains][n_local]                              */);
+/* Chain summaries for Positions-list chains: the reduction, on the device, of
+ * list bins occ[r] (gs_occupancy_offsets) and site counts sites[r][n][0 .. motif_amount] (as
+ * gs_motif_run_multi_batch_stats writes them) to what a caller keeps; M = motif_amount.  For a
+ * view (chain r's own bins and site counts, or the pooled ones) and a sequence n:
+ *   (1) c* is the smallest c in 0 .. M whose site count is the row's largest:
+ *       mode_sites = c*, mode_sites_count that count (an all-zero row: 0, 0);
+ *   (2) c* rounds, each taking among the starts k in [0, L_n - W] not yet excluded the one
+ *       with the largest bin occ[off[n] + 1 + k], the smallest k among equals; a start is
+ *       excluded when |k - q| <= W for a start q already taken (ceckForDistance, .fs:129-140:
+ *       the starts kept are pairwise more than W apart); a zero bin is a candidate like any
+ *       other; the rounds end early when every start is excluded;
+ *   (3) mode_cnt is the number taken, mode_pos[0 .. M) the starts in ascending order (-1 past
+ *       mode_cnt) and mode_count[i] the bin of mode_pos[i] (0 past mode_cnt).
+ * counts_out[r] and pool_counts_out are gs_occupancy_summary's cells on the same bins: for
+ * bins a chain filled, the sum over its counted states of the list aggregates (C over every
+ * listed segment, T[a] the sum over list entries of the sequence's alphabet[a] outside that
+ * entry's segment).  Pooled: chain r is pooled when every sequence's site counts sum to
+ * n_counted; n_pooled_out[0] is their number, the pooled view's bins and site counts are the
+ * pooled chains' summed in int64; with no pooled chain every row is (0, 0) with an empty list
+ * and the cells are zero.  Integer sums only: the results are the same on every run.  Each
+ * output group is nullable as a whole: the five per-chain mode arrays, the counts, the seven
+ * pooled outputs.
+ * gs_list_occupancy_summary reduces caller-held slabs: it uploads, reduces and downloads.  It
+ * needs sequences (else GS_E_STATE) but no snapshot, and leaves the context's snapshot
+ * untouched.  GS_E_ARG: a bad W, motif_amount outside 1 .. 16, occ or sites null with
+ * n_chains > 0, n_chains < 0, n_counted < 0, half of a group given.  n_chains == 0 does
+ * nothing.  GS_E_UNSUPPORTED: sharded sequences or a communicator, or slabs and results
+ * beyond 4 GiB.  Negative bins or site counts are the caller's error: the result is
+ * unspecified, without a fault. */
+int gs_list_occupancy_summary(gs_ctx *ctx, int32_t W, int32_t motif_amount,
+        const int32_t *occ,                /* [n_chains][H]                              */
+        const int32_t *sites,              /* [n_chains][n_local][motif_amount + 1]      */
+        int32_t n_chains, int64_t n_counted,
+        int32_t *mode_sites_out,           /* [n_chains][n_local], nullable with the next 4 */
+        int32_t *mode_sites_count_out,     /* [n_chains][n_local]                        */
+        int32_t *mode_cnt_out,             /* [n_chains][n_local]                        */
+        int32_t *mode_pos_out,             /* [n_chains][n_local][motif_amount]          */
+        int32_t *mode_count_out,           /* [n_chains][n_local][motif_amount]          */
+        int64_t *counts_out,               /* [n_chains][A*W + A], nullable              */
+        int32_t *pool_mode_sites_out,      /* [n_local], nullable with the next 6        */
+        int64_t *pool_mode_sites_count_out,/* [n_local]                                  */
+        int32_t *pool_mode_cnt_out,        /* [n_local]                                  */
+        int32_t *pool_mode_pos_out,        /* [n_local][motif_amount]                    */
+        int64_t *pool_mode_count_out,      /* [n_local][motif_amount]                    */
+        int64_t *pool_counts_out,          /* [A*W + A]                                  */
+        int32_t *n_pooled_out              /* [1]                                        */);
+/* gs_motif_run_multi_batch_stats with the outputs of gs_list_occupancy_summary appended;
+ * n_counted is the call's own.  The bins and site counts are kept on the device whenever the
+ * caller asks for them or for any summary output, and are downloaded only when occ_out /
+ * sites_out are non-null; the reduction follows the last statistics launch of the last round
+ * (the resume rounds of chains run again with larger arenas included), before the final
+ * download.  Everything else is the stats call's contract: the chains, the refusals (half of
+ * a summary group: GS_E_ARG), the context left without a snapshot, and the rule for a chain
+ * that raises: it is summarised from its bins as they stand and left out of the pool, the
+ * other chains are untouched.  With every summary output null the call is the stats call, bit
+ * for bit.  The extra slabs count toward the 4 GiB of chain slabs.  gs_summary_last_ms reports
+ * this reduction's device time too. */
+int gs_motif_run_multi_batch_summary(gs_ctx *ctx, int32_t motif_amount, int32_t W,
+        double pseudo_count, double cut_off, int32_t n_sweeps, const uint64_t *seeds,
+        int32_t n_chains, int64_t first_sweep, int32_t init_mode, int32_t cap, const double *u,
+        int32_t burn_in, int32_t thin,
+        int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+        int32_t *occ_out, int32_t *sites_out, double *ic_out, int64_t *best_sweep_out,
+        int32_t *best_cnt_out, int32_t *best_pos_out, double *best_pwms_out,
+        int32_t *mode_sites_out, int32_t *mode_sites_count_out, int32_t *mode_cnt_out,
+        int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
+        int32_t *pool_mode_sites_out, int64_t *pool_mode_sites_count_out,
+        int32_t *pool_mode_cnt_out, int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out,
+        int64_t *pool_counts_out, int32_t *n_pooled_out);
 /* Device times of the last gs_motif_run_multi_batch or gs_motif_run_multi_batch_stats, ms:
  * starts (and first aggregates), sweeps (resumed chains and the statistics launches
  * included). */
