@@ -549,17 +549,9 @@ class Context:
         return dict(zip(("sweep_rounds", "restart_rounds", "chains_restarted", "slots"),
                         (int(v) for v in out)))
 
-    def motif_run_batch(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds, pos=None,
-                        init_mode: int = 0, first_sweep: int = 0, u=None, strict: bool = False):
-        """R independent chains of n_sweeps sweeps in one call, row r exactly
-        motif_run(W, pc, cutoff, n_sweeps, seeds[r], start r, first_sweep): one launch a
-        sweep over all (chain, target) pairs -> (pos[R, N], pwms[R, N], status[R]).  The
-        starts are the rows of `pos` (-1 = Positions []; implies init_mode -1) or those of
-        random_starts(W, pc, seeds[r], init_mode).  u[R, n_sweeps, N] replaces the counter
-        RNG's uniforms.  pwms is unspecified for n_sweeps = 0.  A chain that raises
-        (status[r] != 0) leaves the other rows valid; errors of the call itself raise, and
-        with strict=True so does a chain's (the lowest-index failing chain's status, the
-        exception's index its sequence)."""
+    def _run_batch_args(self, n_sweeps, seeds, pos, init_mode, u):
+        """The chains' seeds, starts and uniforms as the library takes them (motif_run_batch and
+        its _stats and _summary forms) -> (seeds, pos, init_mode, u)."""
         seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
         R = len(seeds)
         if pos is not None:
@@ -575,6 +567,55 @@ class Context:
             u = np.ascontiguousarray(u, dtype=np.float64)
             if u.shape != (R, max(int(n_sweeps), 0), self.n_local):
                 raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
+        return seeds, pos, init_mode, u
+
+    @staticmethod
+    def _n_counted(burn_in, thin, n_sweeps):
+        """The counted sweeps of a chain (out-of-range values go to the library, which refuses
+        them: the shapes are then moot)."""
+        ok = 0 <= burn_in <= n_sweeps and thin >= 1
+        return len(range(burn_in, n_sweeps, thin)) if ok else 0
+
+    def _stats_outputs(self, W, lead, n_counted, occupancy, ic, best, sites=False, M=None,
+                       cap=None, H=None):
+        """The output arrays of a chain's statistics, the parts asked for, under the leading
+        axes `lead` (() or (R,)) -> dict.  W: the motif length the bins are for (None: none can
+        be sized), H: their number where the caller has it; M and cap: a list chain's
+        motifAmount ("sites") and capacity ("best_cnt", a third axis of "best_pos")."""
+        N = self.n_local
+        stats = {}
+        if occupancy:
+            if H is None:
+                H = int(self.lib.gs_occupancy_size(self.h, int(W))) if W is not None else -1
+            if H >= 0:
+                stats["offsets"] = self.occupancy_offsets(W)
+            stats["occupancy"] = np.zeros(lead + (max(H, 0),), np.int32)
+        if sites:
+            stats["sites"] = np.zeros(lead + (N, max(M, 0) + 1), np.int32)
+        if ic:
+            stats["ic"] = np.full(lead + (n_counted,), np.nan, np.float64)
+        if best:
+            stats["best_sweep"] = np.full(lead or (1,), -1, np.int64)
+            if cap is not None:
+                stats["best_cnt"] = np.zeros(lead + (N,), np.int32)
+            stats["best_pos"] = np.full(lead + (N,) + (() if cap is None else (max(cap, 0),)), -1,
+                                        np.int32)
+            stats["best_pwms"] = np.zeros(lead + (N,), np.float64)
+        return stats
+
+    def motif_run_batch(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds, pos=None,
+                        init_mode: int = 0, first_sweep: int = 0, u=None, strict: bool = False):
+        """R independent chains of n_sweeps sweeps in one call, row r exactly
+        motif_run(W, pc, cutoff, n_sweeps, seeds[r], start r, first_sweep): one launch a
+        sweep over all (chain, target) pairs -> (pos[R, N], pwms[R, N], status[R]).  The
+        starts are the rows of `pos` (-1 = Positions []; implies init_mode -1) or those of
+        random_starts(W, pc, seeds[r], init_mode).  u[R, n_sweeps, N] replaces the counter
+        RNG's uniforms.  pwms is unspecified for n_sweeps = 0.  A chain that raises
+        (status[r] != 0) leaves the other rows valid; errors of the call itself raise, and
+        with strict=True so does a chain's (the lowest-index failing chain's status, the
+        exception's index its sequence)."""
+        seeds, pos, init_mode, u = self._run_batch_args(n_sweeps, seeds, pos, init_mode, u)
+        R = len(seeds)
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
         st = self.lib.gs_motif_run_batch(self.h, int(W), float(pc), float(cutoff), int(n_sweeps),
@@ -607,39 +648,12 @@ class Context:
         (first_sweep + t of the first largest ic, -1: none), "best_pos"[R, N] and
         "best_pwms"[R, N].  A chain that raises in sweep t contributes nothing from t on
         (its ic entries are NaN).  With no part asked for this is motif_run_batch."""
-        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        seeds, pos, init_mode, u = self._run_batch_args(n_sweeps, seeds, pos, init_mode, u)
         R, T = len(seeds), int(n_sweeps)
-        if pos is not None:
-            init_mode = -1
-            pos = np.array(pos, dtype=np.int32, copy=True)
-            if pos.shape != (R, self.n_local):
-                raise ArgumentError(GS_E_ARG, "pos needs one row per seed, one entry per sequence")
-        else:
-            if init_mode not in (0, 1):
-                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
-            pos = np.full((R, self.n_local), -1, np.int32)
-        if u is not None:
-            u = np.ascontiguousarray(u, dtype=np.float64)
-            if u.shape != (R, max(T, 0), self.n_local):
-                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
         burn_in, thin = int(burn_in), int(thin)
-        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
-        ok = 0 <= burn_in <= T and thin >= 1
-        n_counted = len(range(burn_in, T, thin)) if ok else 0
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
-        stats = {}
-        if occupancy:
-            H = int(self.lib.gs_occupancy_size(self.h, int(W)))
-            if H >= 0:
-                stats["offsets"] = self.occupancy_offsets(W)
-            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
-        if ic:
-            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
-        if best:
-            stats["best_sweep"] = np.full(R, -1, np.int64)
-            stats["best_pos"] = np.full((R, self.n_local), -1, np.int32)
-            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats = self._stats_outputs(W, (R,), self._n_counted(burn_in, thin, T), occupancy, ic, best)
         st = self.lib.gs_motif_run_batch_stats(
             self.h, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
             int(init_mode), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms), _ptr(status),
@@ -665,21 +679,7 @@ class Context:
             if u.shape != (max(T, 0), self.n_local):
                 raise ArgumentError(GS_E_ARG, "u needs the shape [sweeps, sequences]")
         burn_in, thin = int(burn_in), int(thin)
-        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
-        ok = 0 <= burn_in <= T and thin >= 1
-        n_counted = len(range(burn_in, T, thin)) if ok else 0
-        stats = {}
-        if occupancy:
-            H = int(self.lib.gs_occupancy_size(self.h, int(W))) if W is not None else -1
-            if H >= 0:
-                stats["offsets"] = self.occupancy_offsets(W)
-            stats["occupancy"] = np.zeros(max(H, 0), np.int32)
-        if ic:
-            stats["ic"] = np.full(n_counted, np.nan, np.float64)
-        if best:
-            stats["best_sweep"] = np.full(1, -1, np.int64)
-            stats["best_pos"] = np.full(self.n_local, -1, np.int32)
-            stats["best_pwms"] = np.zeros(self.n_local, np.float64)
+        stats = self._stats_outputs(W, (), self._n_counted(burn_in, thin, T), occupancy, ic, best)
         return u, burn_in, thin, stats
 
     def run_sweeps_stats(self, pc: float, cutoff: float, n_sweeps: int, seed: int,
@@ -740,12 +740,16 @@ class Context:
         self._check(self.lib.gs_run_stats_last_ms(self.h, _ptr(out)))
         return float(out[0]), float(out[1])
 
+    def _summary_cells(self, W):
+        """Entries of a summary's count matrix, A W + A (W None: it cannot be sized)."""
+        A = len(getattr(self, "_keep", (None, None, ()))[2])  # the alphabet's length
+        return A * int(W) + A if W is not None else 0
+
     def _summary_outputs(self, W, R, modes, counts, pool):
         """The output arrays of a chain summary of R chains (R None: the single chain's,
         without a chain axis) -> dict."""
         lead = () if R is None else (R,)
-        A = len(getattr(self, "_keep", (None, None, ()))[2])  # the alphabet's length
-        cells = A * int(W) + A if W is not None else 0
+        cells = self._summary_cells(W)
         out = {}
         if modes:
             out["mode_pos"] = np.full(lead + (self.n_local,), -1, np.int32)
@@ -839,38 +843,14 @@ class Context:
         device (gs_motif_run_batch_summary) -> (pos[R, N], pwms[R, N], status[R], stats), stats
         with the groups of occupancy_summary besides those of motif_run_batch_stats.  The bins
         are downloaded only with occupancy=True."""
-        seeds = np.array([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+        seeds, pos, init_mode, u = self._run_batch_args(n_sweeps, seeds, pos, init_mode, u)
         R, T = len(seeds), int(n_sweeps)
-        if pos is not None:
-            init_mode = -1
-            pos = np.array(pos, dtype=np.int32, copy=True)
-            if pos.shape != (R, self.n_local):
-                raise ArgumentError(GS_E_ARG, "pos needs one row per seed, one entry per sequence")
-        else:
-            if init_mode not in (0, 1):
-                raise ArgumentError(GS_E_ARG, "init_mode must be 0 or 1 when no starts are given")
-            pos = np.full((R, self.n_local), -1, np.int32)
-        if u is not None:
-            u = np.ascontiguousarray(u, dtype=np.float64)
-            if u.shape != (R, max(T, 0), self.n_local):
-                raise ArgumentError(GS_E_ARG, "u needs the shape [chains, sweeps, sequences]")
         burn_in, thin = int(burn_in), int(thin)
-        ok = 0 <= burn_in <= T and thin >= 1
-        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        n_counted = self._n_counted(burn_in, thin, T)
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
-        stats = {}
         H = int(self.lib.gs_occupancy_size(self.h, int(W)))
-        if occupancy:
-            if H >= 0:
-                stats["offsets"] = self.occupancy_offsets(W)
-            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
-        if ic:
-            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
-        if best:
-            stats["best_sweep"] = np.full(R, -1, np.int64)
-            stats["best_pos"] = np.full((R, self.n_local), -1, np.int32)
-            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats = self._stats_outputs(W, (R,), n_counted, occupancy, ic, best, H=H)
         stats.update(self._summary_outputs(W if H >= 0 else None, R, modes, counts, pool))
         st = self.lib.gs_motif_run_batch_summary(
             self.h, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
@@ -963,26 +943,10 @@ class Context:
             motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u)
         R, T, M = len(seeds), int(n_sweeps), int(motif_amount)
         burn_in, thin = int(burn_in), int(thin)
-        # (out-of-range values go to the library, which refuses them: the shapes are then moot)
-        ok = 0 <= burn_in <= T and thin >= 1
-        n_counted = len(range(burn_in, T, thin)) if ok else 0
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
-        stats = {}
-        if occupancy:
-            H = int(self.lib.gs_occupancy_size(self.h, int(W)))
-            if H >= 0:
-                stats["offsets"] = self.occupancy_offsets(W)
-            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
-        if sites:
-            stats["sites"] = np.zeros((R, self.n_local, max(M, 0) + 1), np.int32)
-        if ic:
-            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
-        if best:
-            stats["best_sweep"] = np.full(R, -1, np.int64)
-            stats["best_cnt"] = np.zeros((R, self.n_local), np.int32)
-            stats["best_pos"] = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
-            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats = self._stats_outputs(W, (R,), self._n_counted(burn_in, thin, T), occupancy, ic, best,
+                                    sites, M, cap)
         st = self.lib.gs_motif_run_multi_batch_stats(
             self.h, M, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
             int(init_mode), cap, _ptr(u), burn_in, thin, _ptr(cnt), _ptr(pos), _ptr(pwms),
@@ -1000,8 +964,7 @@ class Context:
     def _list_summary_outputs(self, W, M, R, modes, counts, pool):
         """The output arrays of a list chain summary of R chains -> dict (the library's order:
         _LIST_SUMMARY_KEYS)."""
-        A = len(getattr(self, "_keep", (None, None, ()))[2])  # the alphabet's length
-        cells = A * int(W) + A if W is not None else 0
+        cells = self._summary_cells(W)
         N, M = self.n_local, max(int(M), 0)
         out = {}
         if modes:
@@ -1068,25 +1031,11 @@ class Context:
             motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u)
         R, T, M = len(seeds), int(n_sweeps), int(motif_amount)
         burn_in, thin = int(burn_in), int(thin)
-        ok = 0 <= burn_in <= T and thin >= 1
-        n_counted = len(range(burn_in, T, thin)) if ok else 0
+        n_counted = self._n_counted(burn_in, thin, T)
         pwms = np.zeros((R, self.n_local), np.float64)
         status = np.zeros(R, np.int32)
-        stats = {}
         H = int(self.lib.gs_occupancy_size(self.h, int(W)))
-        if occupancy:
-            if H >= 0:
-                stats["offsets"] = self.occupancy_offsets(W)
-            stats["occupancy"] = np.zeros((R, max(H, 0)), np.int32)
-        if sites:
-            stats["sites"] = np.zeros((R, self.n_local, max(M, 0) + 1), np.int32)
-        if ic:
-            stats["ic"] = np.full((R, n_counted), np.nan, np.float64)
-        if best:
-            stats["best_sweep"] = np.full(R, -1, np.int64)
-            stats["best_cnt"] = np.zeros((R, self.n_local), np.int32)
-            stats["best_pos"] = np.full((R, self.n_local, max(cap, 0)), -1, np.int32)
-            stats["best_pwms"] = np.zeros((R, self.n_local), np.float64)
+        stats = self._stats_outputs(W, (R,), n_counted, occupancy, ic, best, sites, M, cap, H)
         stats.update(self._list_summary_outputs(W if H >= 0 else None, M, R, modes, counts, pool))
         st = self.lib.gs_motif_run_multi_batch_summary(
             self.h, M, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),

@@ -4,7 +4,7 @@
 // behaviour and the calls into the engine (gs_engine.cpp) and the batch drivers
 // (gs_batch.cpp).  The HBM layout (encoded symbols, 16-byte aligned per sequence), the
 // device snapshot state and the RCCL all-reduces live in the engine.
-#include "gs_ctx.h"
+#include "gs_stats.h"
 
 using namespace gs_host;
 
@@ -616,9 +616,7 @@ int gs_run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_
 // snapshot (W: the snapshot's, or the one about to be set).
 static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_sweeps,
                             int64_t first_sweep, const double *u, const RunStats &st) {
-    if (n_sweeps < 0 || first_sweep < 0 || st.burn_in < 0 || st.burn_in > n_sweeps || st.thin < 1 ||
-        (st.best_sweep_out != nullptr) != (st.best_pos_out && st.best_pwms_out) ||
-        (!st.best_sweep_out && (st.best_pos_out || st.best_pwms_out)) || (st.sum && st.sum->ragged()))
+    if (n_sweeps < 0 || first_sweep < 0 || st.bad(n_sweeps, false))
         return fail(c, GS_E_ARG,
                     std::string(entry) +
                         ": n_sweeps < 0, first_sweep < 0, burn_in outside [0, n_sweeps], thin < 1, "
@@ -631,13 +629,11 @@ static int run_stats_checks(gs_ctx *c, const char *entry, int32_t W, int32_t n_s
                         "one device and no communicator");
     // the bins, the trace, the running best and its rows, and the explicit uniforms
     const int64_t n = c->n_local;
-    const bool sum = st.sum && st.sum->any(), bins = st.occ_out || sum;
-    const int64_t H = bins ? std::max<int64_t>(0, occupancy_offsets(c, W, nullptr)) : 0;
-    const int64_t n_counted =
-        st.burn_in < n_sweeps ? ((int64_t)n_sweeps - st.burn_in + st.thin - 1) / st.thin : 0;
-    const int64_t bytes = (bins ? H * 4 + (n + 1) * 8 : 0) + (st.ic_out ? n_counted * 8 : 0) +
-                          (st.best_sweep_out ? 16 + n * 12 : 0) + (u ? (int64_t)n_sweeps * n * 8 : 0) +
-                          (sum ? st.sum->bytes(1, n, (int64_t)c->A * W + c->A) : 0);
+    const StatsWant want = st.want();
+    const int64_t H = want.occ ? std::max<int64_t>(0, occupancy_offsets(c, W, nullptr)) : 0;
+    const int64_t bytes = stats_bytes(1, n, H, st.plan(n_sweeps).n_counted(), 1, 1, false, want) +
+                          (u ? (int64_t)n_sweeps * n * 8 : 0) +
+                          (st.summed() ? st.sum->bytes(1, n, (int64_t)c->A * W + c->A, 1) : 0);
     if (bytes > kBatchBytesMax)
         return fail(c, GS_E_UNSUPPORTED,
                     std::string(entry) + ": the statistics take " + std::to_string(bytes) +
@@ -673,7 +669,8 @@ int gs_run_sweeps_summary(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps,
                           int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
                           int32_t *best_pos_out, double *best_pwms_out, int32_t *mode_pos_out,
                           int32_t *mode_count_out, int64_t *counts_out) {
-    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, nullptr, nullptr, nullptr, nullptr};
+    const SummaryOut sum = SummaryOut::single(mode_pos_out, mode_count_out, counts_out, nullptr,
+                                              nullptr, nullptr, nullptr);
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
                       &sum};
     return run_sweeps_stats_entry(c, "gs_run_sweeps_summary", pc, cutoff, n_sweeps, seed,
@@ -686,35 +683,47 @@ int gs_summary_last_ms(const gs_ctx *c, double out[1]) {
     return GS_OK;
 }
 
+// What gs_occupancy_summary and gs_list_occupancy_summary (sites non-null, `what`: what its
+// slabs are called) check once their own arguments are in range, and the call.
+static int occupancy_summary_entry(gs_ctx *c, const char *entry, const char *what, int32_t W,
+                                   int32_t M, const int32_t *occ, const int32_t *sites,
+                                   int32_t n_chains, int64_t n_counted, const SummaryOut &out) {
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    std::string(entry) +
+                        ": the cells are summed over every sequence: it needs all sequences on "
+                        "one device and no communicator");
+    if (n_chains == 0) return GS_OK;
+    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
+    const int64_t bytes = (int64_t)n_chains * (H + (sites ? n * ((int64_t)M + 1) : 0)) * 4 +
+                          (n + 1) * 8 + out.bytes(n_chains, n, (int64_t)c->A * W + c->A, M);
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    std::string(entry) + ": the " + what + " and the results take " +
+                        std::to_string(bytes) + " B, more than the " +
+                        std::to_string(kBatchBytesMax) +
+                        " B a call may hold: split the chains over several calls");
+    return occupancy_summary(c, W, M, occ, sites, n_chains, n_counted, out);
+}
+
 int gs_occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t n_chains,
                          int64_t n_counted, int32_t *mode_pos_out, int32_t *mode_count_out,
                          int64_t *counts_out, int32_t *pool_mode_pos_out,
                          int64_t *pool_mode_count_out, int64_t *pool_counts_out,
                          int32_t *n_pooled_out) {
     if (!c) return GS_E_ARG;
-    const SummaryOut out{mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
-                         pool_mode_count_out, pool_counts_out, n_pooled_out};
+    const SummaryOut out =
+        SummaryOut::single(mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
+                           pool_mode_count_out, pool_counts_out, n_pooled_out);
     if (n_chains < 0 || n_counted < 0 || (n_chains > 0 && !occ) || out.ragged())
         return fail(c, GS_E_ARG,
                     "gs_occupancy_summary: n_chains < 0, n_counted < 0, no bins, or half of an "
                     "output group");
-    int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_occupancy_summary: the cells are summed over every sequence: it needs all "
-                    "sequences on one device and no communicator");
-    if (n_chains == 0) return GS_OK;
-    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
-    const int64_t bytes = (int64_t)n_chains * H * 4 + (n + 1) * 8 +
-                          out.bytes(n_chains, n, (int64_t)c->A * W + c->A);
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_occupancy_summary: the bins and the results take " + std::to_string(bytes) +
-                        " B, more than the " + std::to_string(kBatchBytesMax) +
-                        " B a call may hold: split the chains over several calls");
-    return occupancy_summary(c, W, occ, n_chains, n_counted, out);
+    return occupancy_summary_entry(c, "gs_occupancy_summary", "bins", W, 1, occ, nullptr, n_chains,
+                                   n_counted, out);
 }
 
 int gs_run_stats_last_ms(const gs_ctx *c, double out[2]) {
@@ -820,7 +829,8 @@ int gs_motif_run_summary(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t
                          double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
                          double *best_pwms_out, int32_t *mode_pos_out, int32_t *mode_count_out,
                          int64_t *counts_out) {
-    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, nullptr, nullptr, nullptr, nullptr};
+    const SummaryOut sum = SummaryOut::single(mode_pos_out, mode_count_out, counts_out, nullptr,
+                                              nullptr, nullptr, nullptr);
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
                       &sum};
     return motif_run_stats_entry(c, "gs_motif_run_summary", W, pc, cutoff, n_sweeps, seed,
@@ -1303,10 +1313,7 @@ static int motif_run_batch_entry(gs_ctx *c, int32_t W, double pc, double cutoff,
                                  double *pwms_out, int32_t *status_out, const RunStats *st) {
     if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
         return GS_E_ARG;
-    if (st && (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
-               (st->best_sweep_out != nullptr) != (st->best_pos_out && st->best_pwms_out) ||
-               (!st->best_sweep_out && (st->best_pos_out || st->best_pwms_out)) ||
-               (st->sum && st->sum->ragged())))
+    if (st && st->bad(n_sweeps, false))
         return fail(c, GS_E_ARG,
                     "gs_motif_run_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
                     "best_sweep_out without both best rows (or the reverse), or half of a "
@@ -1367,8 +1374,9 @@ int gs_motif_run_batch_summary(gs_ctx *c, int32_t W, double pc, double cutoff, i
                                int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
                                int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out,
                                int64_t *pool_counts_out, int32_t *n_pooled_out) {
-    const SummaryOut sum{mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
-                         pool_mode_count_out, pool_counts_out, n_pooled_out};
+    const SummaryOut sum =
+        SummaryOut::single(mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
+                           pool_mode_count_out, pool_counts_out, n_pooled_out);
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
                       &sum};
     return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
@@ -1388,23 +1396,17 @@ static int motif_run_multi_batch_entry(gs_ctx *c, int32_t motif_amount, int32_t 
                                        int32_t n_chains, int64_t first_sweep, int32_t init_mode,
                                        int32_t cap, const double *u, int32_t *cnt_inout,
                                        int32_t *pos_inout, double *pwms_out, int32_t *status_out,
-                                       const RunMultiStats *st) {
+                                       const RunStats *st) {
     if (!c || n_chains < 0 || n_sweeps < 0 || first_sweep < 0 || init_mode < -1 || init_mode > 1)
         return GS_E_ARG;
     if (motif_amount < 1 || motif_amount > kMultiMaxAmount || cap < motif_amount ||
         cap > kMultiMaxAmount)
         return fail(c, GS_E_ARG, "motifAmount / list capacity out of range");
-    if (st) {
-        const bool rows = st->best_cnt_out && st->best_pos_out && st->best_pwms_out;
-        const bool any_row = st->best_cnt_out || st->best_pos_out || st->best_pwms_out;
-        if (st->burn_in < 0 || st->burn_in > n_sweeps || st->thin < 1 ||
-            (st->best_sweep_out != nullptr) != rows || (!st->best_sweep_out && any_row) ||
-            (st->sum && st->sum->ragged()))
-            return fail(c, GS_E_ARG,
-                        "gs_motif_run_multi_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
-                        "best_sweep_out without all three best rows (or the reverse), or half of "
-                        "a summary's output group");
-    }
+    if (st && st->bad(n_sweeps, true))
+        return fail(c, GS_E_ARG,
+                    "gs_motif_run_multi_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
+                    "best_sweep_out without all three best rows (or the reverse), or half of "
+                    "a summary's output group");
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!cnt_inout || !pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
@@ -1444,8 +1446,8 @@ int gs_motif_run_multi_batch_stats(gs_ctx *c, int32_t motif_amount, int32_t W, d
                                    int32_t *status_out, int32_t *occ_out, int32_t *sites_out,
                                    double *ic_out, int64_t *best_sweep_out, int32_t *best_cnt_out,
                                    int32_t *best_pos_out, double *best_pwms_out) {
-    const RunMultiStats st{burn_in,        thin,         occ_out,      sites_out,    ic_out,
-                           best_sweep_out, best_cnt_out, best_pos_out, best_pwms_out};
+    const RunStats st{burn_in,       thin,    occ_out,   ic_out,      best_sweep_out, best_pos_out,
+                      best_pwms_out, nullptr, sites_out, best_cnt_out};
     return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
                                        first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
                                        pwms_out, status_out, &st);
@@ -1462,15 +1464,13 @@ int gs_motif_run_multi_batch_summary(
     int32_t *pool_mode_sites_out, int64_t *pool_mode_sites_count_out, int32_t *pool_mode_cnt_out,
     int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out, int64_t *pool_counts_out,
     int32_t *n_pooled_out) {
-    const ListSummaryOut sum{mode_sites_out,      mode_sites_count_out,
-                             mode_cnt_out,        mode_pos_out,
-                             mode_count_out,      counts_out,
-                             pool_mode_sites_out, pool_mode_sites_count_out,
-                             pool_mode_cnt_out,   pool_mode_pos_out,
-                             pool_mode_count_out, pool_counts_out,
-                             n_pooled_out};
-    const RunMultiStats st{burn_in,        thin,         occ_out,      sites_out,     ic_out,
-                           best_sweep_out, best_cnt_out, best_pos_out, best_pwms_out, &sum};
+    const SummaryOut sum{{mode_sites_out, mode_sites_count_out, mode_cnt_out, mode_pos_out,
+                          mode_count_out, counts_out, pool_mode_sites_out,
+                          pool_mode_sites_count_out, pool_mode_cnt_out, pool_mode_pos_out,
+                          pool_mode_count_out, pool_counts_out, n_pooled_out},
+                         true};
+    const RunStats st{burn_in,       thin, occ_out,   ic_out,      best_sweep_out, best_pos_out,
+                      best_pwms_out, &sum, sites_out, best_cnt_out};
     return motif_run_multi_batch_entry(c, motif_amount, W, pc, cutoff, n_sweeps, seeds, n_chains,
                                        first_sweep, init_mode, cap, u, cnt_inout, pos_inout,
                                        pwms_out, status_out, &st);
@@ -1486,37 +1486,18 @@ int gs_list_occupancy_summary(gs_ctx *c, int32_t W, int32_t motif_amount, const 
                               int64_t *pool_mode_count_out, int64_t *pool_counts_out,
                               int32_t *n_pooled_out) {
     if (!c) return GS_E_ARG;
-    const ListSummaryOut out{mode_sites_out,      mode_sites_count_out,
-                             mode_cnt_out,        mode_pos_out,
-                             mode_count_out,      counts_out,
-                             pool_mode_sites_out, pool_mode_sites_count_out,
-                             pool_mode_cnt_out,   pool_mode_pos_out,
-                             pool_mode_count_out, pool_counts_out,
-                             n_pooled_out};
+    const SummaryOut out{{mode_sites_out, mode_sites_count_out, mode_cnt_out, mode_pos_out,
+                          mode_count_out, counts_out, pool_mode_sites_out,
+                          pool_mode_sites_count_out, pool_mode_cnt_out, pool_mode_pos_out,
+                          pool_mode_count_out, pool_counts_out, n_pooled_out},
+                         true};
     if (n_chains < 0 || n_counted < 0 || (n_chains > 0 && (!occ || !sites)) ||
         motif_amount < 1 || motif_amount > kMultiMaxAmount || out.ragged())
         return fail(c, GS_E_ARG,
                     "gs_list_occupancy_summary: n_chains < 0, n_counted < 0, no bins or site "
                     "counts, motifAmount outside [1, 16], or half of an output group");
-    int rc;
-    if ((rc = check_dev(c))) return rc;
-    if ((rc = validate_W(c, W))) return rc;
-    if ((int64_t)c->n_local != c->n_global || c->comm)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_list_occupancy_summary: the cells are summed over every sequence: it needs "
-                    "all sequences on one device and no communicator");
-    if (n_chains == 0) return GS_OK;
-    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
-    const int64_t bytes = (int64_t)n_chains * (H + n * ((int64_t)motif_amount + 1)) * 4 +
-                          (n + 1) * 8 +
-                          out.bytes(n_chains, n, (int64_t)c->A * W + c->A, motif_amount);
-    if (bytes > kBatchBytesMax)
-        return fail(c, GS_E_UNSUPPORTED,
-                    "gs_list_occupancy_summary: the slabs and the results take " +
-                        std::to_string(bytes) + " B, more than the " +
-                        std::to_string(kBatchBytesMax) +
-                        " B a call may hold: split the chains over several calls");
-    return list_occupancy_summary(c, W, motif_amount, occ, sites, n_chains, n_counted, out);
+    return occupancy_summary_entry(c, "gs_list_occupancy_summary", "slabs", W, motif_amount, occ,
+                                   sites, n_chains, n_counted, out);
 }
 
 int gs_motif_run_multi(gs_ctx *c, int32_t motif_amount, int32_t W, double pc, double cutoff,

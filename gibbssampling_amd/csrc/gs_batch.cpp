@@ -3,12 +3,13 @@
 // (gs_motif_sampling_multi_batch), run_batch (gs_motif_run_batch and, with the chains'
 // statistics, gs_motif_run_batch_stats, §9.25), run_multi_batch
 // (gs_motif_run_multi_batch and, with statistics, gs_motif_run_multi_batch_stats, §9.26) and
-// starts_batch (gs_random_starts_batch), and the chain summary's host side (SummaryRun,
-// occupancy_summary: gs_occupancy_summary and the ..._summary calls, §9.28), over one copy of the
-// stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
+// starts_batch (gs_random_starts_batch), and the host side of the chain statistics and
+// summaries (gs_stats.h, §9.30: StatsSlab for the three chain drivers, SummaryRun and
+// occupancy_summary for gs_occupancy_summary, gs_list_occupancy_summary and the ..._summary
+// calls, §9.28, §9.29), over one copy of the stages they share.  gs_api.cpp validates the arguments; the single-chain pieces they reuse
 // (set_snapshot_dev, starts_enqueue, starts_pass, greedy_carve, one_sweep) are in
 // gs_engine.cpp.
-#include "gs_ctx.h"
+#include "gs_stats.h"
 
 namespace gs_host {
 namespace {
@@ -878,30 +879,14 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     c->run_batch_ms[0] = c->run_batch_ms[1] = 0.0;
     if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
     if (stats && !stats->any()) stats = nullptr;
-    const auto counted = [&](int32_t t) {
-        return stats && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
-    };
-    const int64_t n_counted =
-        stats && stats->burn_in < T ? ((int64_t)T - stats->burn_in + stats->thin - 1) / stats->thin : 0;
-    if (n == 0) {  // no sequences: no bins, and no counted sweep completes
-        if (stats && stats->ic_out)
-            std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
-        if (stats && stats->best_sweep_out)
-            std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
-        if (stats && stats->sum) {
-            SummaryRun none(c);
-            none.R = R;
-            none.cells = (int64_t)c->A * W + c->A;
-            return none.download(*stats->sum);
-        }
-        return GS_OK;
-    }
+    const CountPlan plan = stats ? stats->plan(T) : CountPlan{T, 1, T};
+    const int64_t n_counted = plan.n_counted();
+    if (n == 0) return stats ? stats_of_nothing(c, W, R, n_counted, *stats) : GS_OK;
     const int64_t H = stats ? occupancy_offsets(c, W, nullptr) : 0;
     // the bins are kept on the device for the caller or for the summary (§9.28), and come
     // down only for the caller
-    const SummaryOut *sum = stats && stats->sum && stats->sum->any() ? stats->sum : nullptr;
-    const bool st_occ = stats && (stats->occ_out || sum), st_occ_down = stats && stats->occ_out,
-               st_ic = stats && stats->ic_out, st_best = stats && stats->best_sweep_out;
+    const SummaryOut *sum = stats && stats->summed() ? stats->sum : nullptr;
+    const StatsWant want = stats ? stats->want() : StatsWant{};
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
     GS_TRY(multi_lds_check(c, lds));
@@ -921,9 +906,8 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         (int64_t)R * (n * (8 + 8 + (mode == 1 ? 4 : 0)) + 3 * 8 * ((int64_t)cells + 1) + 8 + 8 +
                       (int64_t)sizeof(SpecCtl)) +
             n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax +
-            // the statistics: bins and their offsets, the trace, the running best and its rows
-            (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) + (st_ic ? R * n_counted * 8 : 0) +
-            (st_best ? (int64_t)R * (16 + n * 12) : 0) + (sum ? sum->bytes(R, n, cells) : 0)));
+            stats_bytes(R, n, H, n_counted, 1, 1, false, want) +
+            (sum ? sum->bytes(R, n, cells, 1) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     GS_TRY(multi_scratch(c, a, grid, 0));
     // the slabs (row r = chain r)
@@ -949,45 +933,23 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     }
     HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
     for (auto &q : b_agg) HIP_TRY(c, hipMemsetAsync(q, 0, (size_t)agg_elems * 8, c->stream));
-    // the statistics' slabs: zero bins, no best yet (-1); every counted sweep's launch
-    // writes its own trace entry of every chain
-    DevBuf<int32_t> s_occ, s_bpos;
-    DevBuf<int64_t> s_off, s_bsweep;
-    DevBuf<double> s_ic, s_bic, s_bpwms;
-    std::vector<int64_t> h_off;  // alive for the upload
+    // the statistics' slab; every counted sweep's launch writes its own trace entry of
+    // every chain
+    StatsSlab st(c);
     SummaryRun srun(c);
+    if (stats) GS_TRY(st.init(W, R, H, n_counted, 1, 1, false, want));
     RunStatsArgs sa{};
     sa.n_chains = R;
     sa.n_local = (int32_t)n;
     sa.atomic = c->tune.run_stats_atomic;
     sa.H = H;
     sa.ic_stride = n_counted;
-    if (st_occ) {
-        h_off.resize((size_t)n + 1);
-        occupancy_offsets(c, W, h_off.data());
-        GS_TRY(s_off.alloc(c, n + 1));
-        GS_TRY(s_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
-        HIP_TRY(c, hipMemcpyAsync(s_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_occ, 0, (size_t)R * H * 4, c->stream));
-        sa.off = s_off;
-        sa.occ = s_occ;
-    }
-    if (st_ic && n_counted > 0) GS_TRY(s_ic.alloc(c, R * n_counted));
-    if (st_best) {
-        GS_TRY(s_bsweep.alloc(c, R));
-        GS_TRY(s_bic.alloc(c, R));
-        GS_TRY(s_bpos.alloc(c, rows));
-        GS_TRY(s_bpwms.alloc(c, rows));
-        HIP_TRY(c, hipMemsetAsync(s_bsweep, 0xff, (size_t)R * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bic, 0, (size_t)R * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bpos, 0, (size_t)rows * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bpwms, 0, (size_t)rows * 8, c->stream));
-        sa.best_sweep = s_bsweep;
-        sa.best_ic = s_bic;
-        sa.best_pos = s_bpos;
-        sa.best_pwms = s_bpwms;
-    }
+    sa.off = st.dev<int64_t>(kStatOff);
+    sa.occ = st.dev<int32_t>(kStatOcc);
+    sa.best_sweep = st.dev<int64_t>(kStatBestSweep);
+    sa.best_ic = st.dev<double>(kStatBestIc);
+    sa.best_pos = st.dev<int32_t>(kStatBestPos);
+    sa.best_pwms = st.dev<double>(kStatBestPwms);
     const int sblocks = c->tune.run_stats_blocks > 0 ? c->tune.run_stats_blocks : agg_blocks(c, n, R);
     RunBatchArgs ba{};
     ba.n_chains = R;
@@ -1045,8 +1007,8 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
                 HIP_TRY(c, hipMemsetAsync(b_agg[nxt], 0, (size_t)agg_elems * 8, c->stream));
             ba.pos_in = b_pos[t & 1];
             ba.pos_out = b_pos[(t + 1) & 1];
-            const bool count = counted(t);
-            ba.pwms_out = t == T - 1 || (count && (st_ic || st_best)) ? b_pwms.p : nullptr;
+            const bool count = stats && plan.counted(t);
+            ba.pwms_out = t == T - 1 || (count && (want.ic || want.best)) ? b_pwms.p : nullptr;
             ba.agg_in = b_agg[cur];
             ba.agg_out = b_agg[nxt];
             ba.agg_clear = clear_in_kernel && t >= 1 ? b_agg[aft].p : nullptr;
@@ -1057,14 +1019,14 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
                 sa.skip = b_agg[nxt] + (int64_t)R * cells;
                 sa.pos = b_pos[(t + 1) & 1];
                 sa.pwms = b_pwms;
-                sa.ic = s_ic ? s_ic + (t - stats->burn_in) / stats->thin : nullptr;
+                sa.ic = want.ic ? st.dev<double>(kStatIc) + plan.slot(t) : nullptr;
                 sa.sweep = first_sweep + t;
                 HIP_TRY(c, gs_run_batch_stats_launch(sa, sblocks, c->stream));
             }
         }
         HIP_TRY(c, ev.mark());
         // the reduction of the bins as the last statistics launch left them
-        if (sum) GS_TRY(srun.enqueue(W, s_occ, s_off, H, R, n_counted, *sum));
+        if (sum) GS_TRY(srun.enqueue(W, 1, sa.occ, nullptr, sa.off, H, R, n_counted, *sum));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;
     }();
@@ -1083,17 +1045,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
                                   c->stream));
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
-    const auto down = [&](void *dst, const void *src, int64_t bytes) -> hipError_t {
-        return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
-                         : hipSuccess;
-    };
-    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
-    if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
-    if (st_best) {
-        HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
-        HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * 4));
-        HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
-    }
+    if (stats) GS_TRY(st.download(*stats));
     if (sum) {
         GS_TRY(srun.download(*sum));
         srun.finish();
@@ -1115,9 +1067,60 @@ int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off) {
     return h;
 }
 
-// The chain summary's device side.  One slab: the cells that start from
-// zero first (the chains' cells, the pooled cells, n_pooled: one memset), then the pooled
-// counts, the modes and the pooled flags.
+// The statistics' device side: one slab, the parts that start from zero
+// first (one memset), best_sweep and a list's best positions all-ones.
+StatsSlab::~StatsSlab() {
+    if (mem) (void)hipStreamSynchronize(c->stream);
+    dfree(mem);
+}
+
+int StatsSlab::init(int32_t W, int64_t R, int64_t H, int64_t n_counted, int64_t cap, int64_t M,
+                    bool list, const StatsWant &w) {
+    lay = stats_slab(R, c->n_local, H, n_counted, cap, M, list, w);
+    HIP_TRY(c, hipMalloc(&mem, (size_t)std::max<int64_t>(lay.total, 8)));
+    if (lay.zeroed > 0) HIP_TRY(c, hipMemsetAsync(mem, 0, (size_t)lay.zeroed, c->stream));
+    for (const int part : {(int)kStatBestSweep, (int)kStatBestPos}) {
+        const Part &p = lay.part[part];
+        if (p.bytes() > 0 && !p.zero)
+            HIP_TRY(c, hipMemsetAsync(mem + p.off, 0xff, (size_t)p.bytes(), c->stream));
+    }
+    if (w.occ) {
+        h_off.resize((size_t)c->n_local + 1);
+        occupancy_offsets(c, W, h_off.data());
+        HIP_TRY(c, hipMemcpyAsync(mem + lay.part[kStatOff].off, h_off.data(), h_off.size() * 8,
+                                  hipMemcpyHostToDevice, c->stream));
+    }
+    return GS_OK;
+}
+
+int StatsSlab::download(int part, void *dst) const {
+    const Part &p = lay.part[part];
+    if (dst && p.bytes() > 0)
+        HIP_TRY(c, hipMemcpyAsync(dst, mem + p.off, (size_t)p.bytes(), hipMemcpyDeviceToHost,
+                                  c->stream));
+    return GS_OK;
+}
+
+int StatsSlab::download(const RunStats &st) const {
+    GS_TRY(download(kStatOcc, st.occ_out));
+    GS_TRY(download(kStatSites, st.sites_out));
+    GS_TRY(download(kStatIc, st.ic_out));
+    GS_TRY(download(kStatBestSweep, st.best_sweep_out));
+    GS_TRY(download(kStatBestCnt, st.best_cnt_out));
+    GS_TRY(download(kStatBestPos, st.best_pos_out));
+    return download(kStatBestPwms, st.best_pwms_out);
+}
+
+// No sequences: no bins, no counted sweep completes, and the summary is that of nothing.
+int stats_of_nothing(const gs_ctx *c, int32_t W, int64_t R, int64_t n_counted, const RunStats &st) {
+    if (st.ic_out) std::fill(st.ic_out, st.ic_out + R * n_counted, std::nan(""));
+    if (st.best_sweep_out) std::fill(st.best_sweep_out, st.best_sweep_out + R, (int64_t)-1);
+    if (st.sum) summary_of_nothing(c, W, R, *st.sum);
+    return GS_OK;
+}
+
+// The chain summary's device side, over the table of its parts
+// (summary_slab): one slab, the cells that start from zero first (one memset).
 SummaryRun::~SummaryRun() {
     if (slab) (void)hipStreamSynchronize(c->stream);
     dfree(slab);
@@ -1125,87 +1128,73 @@ SummaryRun::~SummaryRun() {
         if (e) c->ev_pool.push_back(e);
 }
 
-int SummaryRun::enqueue(int32_t W, const int32_t *d_occ, const int64_t *d_off, int64_t H,
-                        int32_t n_chains, int64_t n_counted, const SummaryOut &out) {
-    R = n_chains;
-    n = c->n_local;
-    cells = (int64_t)c->A * W + c->A;
+int SummaryRun::enqueue(int32_t W, int32_t M, const int32_t *d_occ, const int32_t *d_sites,
+                        const int64_t *d_off, int64_t H, int32_t R, int64_t n_counted,
+                        const SummaryOut &out) {
+    const int64_t n = c->n_local;
     c->summary_ms = 0.0;
     if (R <= 0 || n <= 0 || !out.any()) return GS_OK;
-    const bool m = out.modes(), k = out.counts != nullptr, p = out.pool();
-    o_counts = 0;
-    o_pcounts = o_counts + (k ? R * cells * 8 : 0);
-    o_np = o_pcounts + (p ? cells * 8 : 0);
-    const int64_t zeroed = o_np + (p ? 8 : 0);
-    o_pcnt = zeroed;
-    o_mpos = o_pcnt + (p ? n * 8 : 0);
-    o_mcnt = o_mpos + (m ? R * n * 4 : 0);
-    o_ppos = o_mcnt + (m ? R * n * 4 : 0);
-    const int64_t o_flags = o_ppos + (p ? n * 4 : 0), bytes = o_flags + (p ? R * 4 : 0);
-    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(bytes, 8)));
-    if (zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)zeroed, c->stream));
-    SummaryArgs a{};
-    a.n_chains = n_chains;
-    a.n_local = c->n_local;
-    a.A = c->A;
-    a.W = W;
-    a.CS = c->E + 1;
-    a.H = H;
-    a.n_counted = n_counted;
-    a.occ = d_occ;
-    a.off = d_off;
-    a.seq = c->d_seq;
-    a.doff = c->d_doff;
-    a.comp = c->d_comp;
-    if (m) {
-        a.mode_pos = (int32_t *)(slab + o_mpos);
-        a.mode_count = (int32_t *)(slab + o_mcnt);
-    }
-    if (k) a.counts = (int64_t *)(slab + o_counts);
-    if (p) {
-        a.flags = (int32_t *)(slab + o_flags);
-        a.n_pooled = (int32_t *)(slab + o_np);
-        a.pool_pos = (int32_t *)(slab + o_ppos);
-        a.pool_count = (int64_t *)(slab + o_pcnt);
-        a.pool_counts = (int64_t *)(slab + o_pcounts);
-    }
+    const bool want[kSummaryGroups] = {out.modes(), out.counts(), out.pool()};
+    lay = summary_slab(R, n, (int64_t)c->A * W + c->A, M, out.list, want);
+    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(lay.total, 8)));
+    if (lay.zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)lay.zeroed, c->stream));
     // a wavefront a row, four a workgroup: eight rows a wavefront (a workgroup's cells cost
     // up to A W + A atomic adds at its end) while the GPU is eight deep over all views (what
     // its registers allow: a row is a chain of dependent loads, hidden by other rows only)
-    const int64_t views = R + (p ? 1 : 0);
+    const int64_t views = R + (want[kGroupPool] ? 1 : 0);
     const int blocks = (int)std::max<int64_t>(
         1, std::min<int64_t>((n + 31) / 32, std::max<int64_t>(1, (int64_t)c->n_cu * 8 / views)));
+    // what both kernels' arguments share
+    const auto fill = [&](auto &a) {
+        a.n_chains = R;
+        a.n_local = c->n_local;
+        a.A = c->A;
+        a.W = W;
+        a.CS = c->E + 1;
+        a.H = H;
+        a.n_counted = n_counted;
+        a.occ = d_occ;
+        a.off = d_off;
+        a.seq = c->d_seq;
+        a.doff = c->d_doff;
+        a.comp = c->d_comp;
+        a.mode_pos = dev<int32_t>(kModePos);
+        a.mode_count = dev<int32_t>(kModeCount);
+        a.counts = dev<int64_t>(kCounts);
+        a.flags = dev<int32_t>(kPoolFlags);
+        a.n_pooled = dev<int32_t>(kNPooled);
+        a.pool_pos = dev<int32_t>(kPoolPos);
+        a.pool_count = dev<int64_t>(kPoolCount);
+        a.pool_counts = dev<int64_t>(kPoolCounts);
+    };
     for (hipEvent_t &e : ev) e = get_event(c);
     HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-    HIP_TRY(c, gs_summary_launch(a, blocks, c->stream));
+    if (out.list) {
+        ListSummaryArgs a{};
+        fill(a);
+        a.M = M;
+        a.sites = d_sites;
+        a.mode_sites = dev<int32_t>(kModeSites);
+        a.mode_sites_count = dev<int32_t>(kModeSitesCount);
+        a.mode_cnt = dev<int32_t>(kModeCnt);
+        a.pool_sites = dev<int32_t>(kPoolSites);
+        a.pool_sites_count = dev<int64_t>(kPoolSitesCount);
+        a.pool_cnt = dev<int32_t>(kPoolCnt);
+        HIP_TRY(c, gs_list_summary_launch(a, blocks, c->stream));
+    } else {
+        SummaryArgs a{};
+        fill(a);
+        HIP_TRY(c, gs_summary_launch(a, blocks, c->stream));
+    }
     HIP_TRY(c, hipEventRecord(ev[1], c->stream));
     return GS_OK;
 }
 
 int SummaryRun::download(const SummaryOut &out) {
-    if (R <= 0 || !out.any()) return GS_OK;
-    if (n <= 0) {  // no sequences: no modes; every chain's (empty) row sums to anything asked
-        if (out.counts) std::fill(out.counts, out.counts + R * cells, (int64_t)0);
-        if (out.pool()) {
-            std::fill(out.pool_counts, out.pool_counts + cells, (int64_t)0);
-            *out.n_pooled = (int32_t)R;
-        }
-        return GS_OK;
-    }
-    const auto down = [&](void *dst, int64_t o, int64_t bytes) -> hipError_t {
-        return hipMemcpyAsync(dst, slab + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
-    };
-    if (out.modes()) {
-        HIP_TRY(c, down(out.mode_pos, o_mpos, R * n * 4));
-        HIP_TRY(c, down(out.mode_count, o_mcnt, R * n * 4));
-    }
-    if (out.counts) HIP_TRY(c, down(out.counts, o_counts, R * cells * 8));
-    if (out.pool()) {
-        HIP_TRY(c, down(out.pool_pos, o_ppos, n * 4));
-        HIP_TRY(c, down(out.pool_count, o_pcnt, n * 8));
-        HIP_TRY(c, down(out.pool_counts, o_pcounts, cells * 8));
-        HIP_TRY(c, down(out.n_pooled, o_np, 4));
-    }
+    for (int i = 0; slab && i < kSummaryOutputs; ++i)
+        if (lay.part[i].bytes() > 0)
+            HIP_TRY(c, hipMemcpyAsync(out.out[i], slab + lay.part[i].off, (size_t)lay.part[i].bytes(),
+                                      hipMemcpyDeviceToHost, c->stream));
     return GS_OK;
 }
 
@@ -1214,192 +1203,42 @@ void SummaryRun::finish() {
     if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->summary_ms = ms;
 }
 
-// gs_occupancy_summary: the caller's bins up, the reduction, the result down (arguments
-// validated).  The context's snapshot and state are not touched.
-int occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
-                      const SummaryOut &out) {
-    const int64_t n = c->n_local;
-    SummaryRun run(c);
-    if (n == 0) {
-        run.R = R;
-        run.cells = (int64_t)c->A * W + c->A;
-        return run.download(out);
-    }
-    const int64_t H = occupancy_offsets(c, W, nullptr);
-    std::vector<int64_t> h_off((size_t)n + 1);
-    occupancy_offsets(c, W, h_off.data());
-    DevBuf<int32_t> d_occ;
-    DevBuf<int64_t> d_off;
-    GS_TRY(d_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
-    GS_TRY(d_off.alloc(c, n + 1));
-    int rc = [&]() -> int {
-        HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_occ, occ, (size_t)R * H * 4, hipMemcpyHostToDevice, c->stream));
-        GS_TRY(run.enqueue(W, d_occ, d_off, H, R, n_counted, out));
-        GS_TRY(run.download(out));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }();
-    if (rc) {  // nothing in flight on the slabs when they go
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    run.finish();
-    return GS_OK;
-}
-
-// The list chain summary's device side, as SummaryRun's: one slab, the cells
-// that start from zero first (one memset), then the 64-bit pooled outputs, then the 32-bit
-// ones and the pooled flags.
-ListSummaryRun::~ListSummaryRun() {
-    if (slab) (void)hipStreamSynchronize(c->stream);
-    dfree(slab);
-    for (hipEvent_t e : ev)
-        if (e) c->ev_pool.push_back(e);
-}
-
-int ListSummaryRun::enqueue(int32_t W, int32_t motif_amount, const int32_t *d_occ,
-                            const int32_t *d_sites, const int64_t *d_off, int64_t H,
-                            int32_t n_chains, int64_t n_counted, const ListSummaryOut &out) {
-    R = n_chains;
-    n = c->n_local;
-    M = motif_amount;
-    cells = (int64_t)c->A * W + c->A;
-    c->summary_ms = 0.0;
-    if (R <= 0 || n <= 0 || !out.any()) return GS_OK;
-    const bool m = out.modes(), k = out.counts != nullptr, p = out.pool();
-    int64_t bytes = 0;
-    const auto take = [&](bool wanted, int64_t b) {
-        const int64_t o = bytes;
-        if (wanted) bytes += (b + 7) / 8 * 8;
-        return o;
-    };
-    o_counts = take(k, R * cells * 8);
-    o_pcounts = take(p, cells * 8);
-    o_np = take(p, 8);
-    const int64_t zeroed = bytes;
-    o_psc = take(p, n * 8);
-    o_pcount = take(p, n * M * 8);
-    o_ms = take(m, R * n * 4);
-    o_msc = take(m, R * n * 4);
-    o_mcnt = take(m, R * n * 4);
-    o_mpos = take(m, R * n * M * 4);
-    o_mcount = take(m, R * n * M * 4);
-    o_ps = take(p, n * 4);
-    o_pcnt = take(p, n * 4);
-    o_ppos = take(p, n * M * 4);
-    const int64_t o_flags = take(p, R * 4);
-    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(bytes, 8)));
-    if (zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)zeroed, c->stream));
-    ListSummaryArgs a{};
-    a.n_chains = n_chains;
-    a.n_local = c->n_local;
-    a.A = c->A;
-    a.W = W;
-    a.CS = c->E + 1;
-    a.M = motif_amount;
-    a.H = H;
-    a.n_counted = n_counted;
-    a.occ = d_occ;
-    a.sites = d_sites;
-    a.off = d_off;
-    a.seq = c->d_seq;
-    a.doff = c->d_doff;
-    a.comp = c->d_comp;
-    if (m) {
-        a.mode_sites = (int32_t *)(slab + o_ms);
-        a.mode_sites_count = (int32_t *)(slab + o_msc);
-        a.mode_cnt = (int32_t *)(slab + o_mcnt);
-        a.mode_pos = (int32_t *)(slab + o_mpos);
-        a.mode_count = (int32_t *)(slab + o_mcount);
-    }
-    if (k) a.counts = (int64_t *)(slab + o_counts);
-    if (p) {
-        a.flags = (int32_t *)(slab + o_flags);
-        a.n_pooled = (int32_t *)(slab + o_np);
-        a.pool_sites = (int32_t *)(slab + o_ps);
-        a.pool_sites_count = (int64_t *)(slab + o_psc);
-        a.pool_cnt = (int32_t *)(slab + o_pcnt);
-        a.pool_pos = (int32_t *)(slab + o_ppos);
-        a.pool_count = (int64_t *)(slab + o_pcount);
-        a.pool_counts = (int64_t *)(slab + o_pcounts);
-    }
-    // (the grid of SummaryRun::enqueue: a wavefront a row, eight rows a wavefront, the GPU
-    // eight deep over all views)
-    const int64_t views = R + (p ? 1 : 0);
-    const int blocks = (int)std::max<int64_t>(
-        1, std::min<int64_t>((n + 31) / 32, std::max<int64_t>(1, (int64_t)c->n_cu * 8 / views)));
-    for (hipEvent_t &e : ev) e = get_event(c);
-    HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-    HIP_TRY(c, gs_list_summary_launch(a, blocks, c->stream));
-    HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-    return GS_OK;
-}
-
-int ListSummaryRun::download(const ListSummaryOut &out) {
-    if (R <= 0 || !out.any()) return GS_OK;
-    if (n <= 0) {  // no sequences: no rows; every chain's (empty) site rows sum to anything asked
-        if (out.counts) std::fill(out.counts, out.counts + R * cells, (int64_t)0);
-        if (out.pool()) {
-            std::fill(out.pool_counts, out.pool_counts + cells, (int64_t)0);
-            *out.n_pooled = (int32_t)R;
-        }
-        return GS_OK;
-    }
-    const auto down = [&](void *dst, int64_t o, int64_t bytes) -> hipError_t {
-        return hipMemcpyAsync(dst, slab + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
-    };
-    if (out.modes()) {
-        HIP_TRY(c, down(out.mode_sites, o_ms, R * n * 4));
-        HIP_TRY(c, down(out.mode_sites_count, o_msc, R * n * 4));
-        HIP_TRY(c, down(out.mode_cnt, o_mcnt, R * n * 4));
-        HIP_TRY(c, down(out.mode_pos, o_mpos, R * n * M * 4));
-        HIP_TRY(c, down(out.mode_count, o_mcount, R * n * M * 4));
-    }
-    if (out.counts) HIP_TRY(c, down(out.counts, o_counts, R * cells * 8));
+// No sequences: no modes; every chain's (empty) row sums to anything asked.
+void summary_of_nothing(const gs_ctx *c, int32_t W, int64_t R, const SummaryOut &out) {
+    const int64_t cells = (int64_t)c->A * W + c->A;
+    if (R <= 0) return;
+    if (out.counts()) std::fill_n((int64_t *)out.out[kCounts], R * cells, (int64_t)0);
     if (out.pool()) {
-        HIP_TRY(c, down(out.pool_sites, o_ps, n * 4));
-        HIP_TRY(c, down(out.pool_sites_count, o_psc, n * 8));
-        HIP_TRY(c, down(out.pool_cnt, o_pcnt, n * 4));
-        HIP_TRY(c, down(out.pool_pos, o_ppos, n * M * 4));
-        HIP_TRY(c, down(out.pool_count, o_pcount, n * M * 8));
-        HIP_TRY(c, down(out.pool_counts, o_pcounts, cells * 8));
-        HIP_TRY(c, down(out.n_pooled, o_np, 4));
+        std::fill_n((int64_t *)out.out[kPoolCounts], cells, (int64_t)0);
+        *(int32_t *)out.out[kNPooled] = (int32_t)R;
     }
-    return GS_OK;
 }
 
-void ListSummaryRun::finish() {
-    float ms = 0.0f;
-    if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->summary_ms = ms;
-}
-
-// gs_list_occupancy_summary: the caller's bins and site counts up, the reduction, the result
-// down (arguments validated).  The context's snapshot and state are not touched.
-int list_occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ,
-                           const int32_t *sites, int32_t R, int64_t n_counted,
-                           const ListSummaryOut &out) {
+// gs_occupancy_summary and (sites non-null) gs_list_occupancy_summary: the caller's bins and
+// site counts up, the reduction, the result down (arguments validated).  The context's
+// snapshot and state are not touched.
+int occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ, const int32_t *sites,
+                      int32_t R, int64_t n_counted, const SummaryOut &out) {
     const int64_t n = c->n_local;
-    ListSummaryRun run(c);
     if (n == 0) {
-        run.R = R;
-        run.cells = (int64_t)c->A * W + c->A;
-        return run.download(out);
+        summary_of_nothing(c, W, R, out);
+        return GS_OK;
     }
     const int64_t H = occupancy_offsets(c, W, nullptr), S = (int64_t)R * n * (M + 1);
     std::vector<int64_t> h_off((size_t)n + 1);
     occupancy_offsets(c, W, h_off.data());
+    SummaryRun run(c);
     DevBuf<int32_t> d_occ, d_sites;
     DevBuf<int64_t> d_off;
     GS_TRY(d_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
-    GS_TRY(d_sites.alloc(c, S));
+    if (sites) GS_TRY(d_sites.alloc(c, S));
     GS_TRY(d_off.alloc(c, n + 1));
     int rc = [&]() -> int {
         HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
                                   c->stream));
         HIP_TRY(c, hipMemcpyAsync(d_occ, occ, (size_t)R * H * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_sites, sites, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
+        if (sites)
+            HIP_TRY(c, hipMemcpyAsync(d_sites, sites, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
         GS_TRY(run.enqueue(W, M, d_occ, d_sites, d_off, H, R, n_counted, out));
         GS_TRY(run.download(out));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1433,37 +1272,20 @@ int list_occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ,
 int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
                     const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
                     const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
-                    int32_t *status_out, const RunMultiStats *stats) {
+                    int32_t *status_out, const RunStats *stats) {
     const int64_t n = c->n_local;
     c->run_multi_batch_ms[0] = c->run_multi_batch_ms[1] = 0.0;
     for (int i = 0; i < 4; ++i) c->run_multi_batch_info[i] = 0;
     if (status_out) std::fill(status_out, status_out + R, (int32_t)GS_OK);
     if (stats && !stats->any()) stats = nullptr;
-    const auto counted = [&](int32_t t) {
-        return stats && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
-    };
-    const int64_t n_counted =
-        stats && stats->burn_in < T ? ((int64_t)T - stats->burn_in + stats->thin - 1) / stats->thin : 0;
-    if (n == 0) {  // no sequences: no bins, and no counted sweep completes
-        if (stats && stats->ic_out)
-            std::fill(stats->ic_out, stats->ic_out + R * n_counted, std::nan(""));
-        if (stats && stats->best_sweep_out)
-            std::fill(stats->best_sweep_out, stats->best_sweep_out + R, (int64_t)-1);
-        if (stats && stats->sum) {
-            ListSummaryRun none(c);
-            none.R = R;
-            none.cells = (int64_t)c->A * W + c->A;
-            return none.download(*stats->sum);
-        }
-        return GS_OK;
-    }
+    const CountPlan plan = stats ? stats->plan(T) : CountPlan{T, 1, T};
+    const int64_t n_counted = plan.n_counted();
+    if (n == 0) return stats ? stats_of_nothing(c, W, R, n_counted, *stats) : GS_OK;
     // the bins and site counts are kept on the device for the caller or for the summary
     // (§9.29), and come down only for the caller
-    const ListSummaryOut *sum = stats && stats->sum && stats->sum->any() ? stats->sum : nullptr;
-    const bool st_occ = stats && (stats->occ_out || sum), st_sites = stats && (stats->sites_out || sum),
-               st_occ_down = stats && stats->occ_out, st_sites_down = stats && stats->sites_out,
-               st_ic = stats && stats->ic_out, st_best = stats && stats->best_sweep_out;
-    const int64_t H = st_occ ? occupancy_offsets(c, W, nullptr) : 0;
+    const SummaryOut *sum = stats && stats->summed() ? stats->sum : nullptr;
+    const StatsWant want = stats ? stats->want() : StatsWant{};
+    const int64_t H = want.occ ? occupancy_offsets(c, W, nullptr) : 0;
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, M, W, cap, pc, cutoff, false);
     // (the kernel stages its pick in static LDS beside the carve: both have to fit)
@@ -1511,11 +1333,7 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
                       3 * 8 * ((int64_t)cells + 1) + 8 + 4 + 8 + (int64_t)sizeof(SpecCtl) + 4) +
             (ovf_elems + novf_elems) * 4 + u_elems * 8 + cpart_bytes +
             scratch_bytes(rows, arena0) +
-            // the statistics: bins and their offsets, site counts, the trace, the running
-            // best and its rows
-            (st_occ ? (int64_t)R * H * 4 + (n + 1) * 8 : 0) +
-            (st_sites ? rows * ((int64_t)M + 1) * 4 : 0) + (st_ic ? R * n_counted * 8 : 0) +
-            (st_best ? (int64_t)R * 16 + rows * (4 + 4 * (int64_t)cap + 8) : 0) +
+            stats_bytes(R, n, H, n_counted, cap, M, true, want) +
             (sum ? sum->bytes(R, n, cells, M) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     {  // the first round's arenas, so that no sweep waits for an allocation
@@ -1551,13 +1369,11 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
     }
     HIP_TRY(c, hipMemcpyAsync(b_seeds, seeds, (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(b_park, 0xff, (size_t)R * 4, c->stream));
-    // the statistics' slabs, cleared here once for all rounds: zero bins and site counts, no
-    // best yet (-1, empty lists); the first round's launches write every chain's trace entries
-    DevBuf<int32_t> s_occ, s_sites, s_bcnt, s_bpos;
-    DevBuf<int64_t> s_off, s_bsweep;
-    DevBuf<double> s_ic, s_bic, s_bpwms;
-    std::vector<int64_t> h_off;  // alive for the upload
-    ListSummaryRun srun(c);
+    // the statistics' slab, cleared here once for all rounds; the first round's launches
+    // write every chain's trace entries
+    StatsSlab st(c);
+    SummaryRun srun(c);
+    if (stats) GS_TRY(st.init(W, R, H, n_counted, cap, M, true, want));
     RunMultiStatsArgs sa{};
     sa.n_local = (int32_t)n;
     sa.cap = cap;
@@ -1565,40 +1381,14 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
     sa.atomic = c->tune.run_stats_atomic;
     sa.H = H;
     sa.ic_stride = n_counted;
-    if (st_occ) {
-        h_off.resize((size_t)n + 1);
-        occupancy_offsets(c, W, h_off.data());
-        GS_TRY(s_off.alloc(c, n + 1));
-        GS_TRY(s_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
-        HIP_TRY(c, hipMemcpyAsync(s_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_occ, 0, (size_t)R * H * 4, c->stream));
-        sa.off = s_off;
-        sa.occ = s_occ;
-    }
-    if (st_sites) {
-        GS_TRY(s_sites.alloc(c, rows * (M + 1)));
-        HIP_TRY(c, hipMemsetAsync(s_sites, 0, (size_t)(rows * (M + 1)) * 4, c->stream));
-        sa.sites = s_sites;
-    }
-    if (st_ic && n_counted > 0) GS_TRY(s_ic.alloc(c, R * n_counted));
-    if (st_best) {
-        GS_TRY(s_bsweep.alloc(c, R));
-        GS_TRY(s_bic.alloc(c, R));
-        GS_TRY(s_bcnt.alloc(c, rows));
-        GS_TRY(s_bpos.alloc(c, rows * cap));
-        GS_TRY(s_bpwms.alloc(c, rows));
-        HIP_TRY(c, hipMemsetAsync(s_bsweep, 0xff, (size_t)R * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bic, 0, (size_t)R * 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bcnt, 0, (size_t)rows * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bpos, 0xff, (size_t)(rows * cap) * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(s_bpwms, 0, (size_t)rows * 8, c->stream));
-        sa.best_sweep = s_bsweep;
-        sa.best_ic = s_bic;
-        sa.best_cnt = s_bcnt;
-        sa.best_pos = s_bpos;
-        sa.best_pwms = s_bpwms;
-    }
+    sa.off = st.dev<int64_t>(kStatOff);
+    sa.occ = st.dev<int32_t>(kStatOcc);
+    sa.sites = st.dev<int32_t>(kStatSites);
+    sa.best_sweep = st.dev<int64_t>(kStatBestSweep);
+    sa.best_ic = st.dev<double>(kStatBestIc);
+    sa.best_cnt = st.dev<int32_t>(kStatBestCnt);
+    sa.best_pos = st.dev<int32_t>(kStatBestPos);
+    sa.best_pwms = st.dev<double>(kStatBestPwms);
     RunMultiBatchArgs ba{};
     ba.cells = cells;
     ba.n_all = R;
@@ -1655,12 +1445,13 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         if (first) HIP_TRY(c, ev.mark());
         for (int32_t t = rd.t0; t < T; ++t) {
             const int k = t - rd.t0, cur = k % 3, nxt = (k + 1) % 3, aft = (k + 2) % 3;
+            const bool count = stats && plan.counted(t);
             for (MultiArgs *m : {&am, &ao}) {
                 m->cnt_in = b_cnt[t & 1];
                 m->pos_in = b_pos[t & 1];
                 m->cnt_out = b_cnt[(t + 1) & 1];
                 m->pos_out = b_pos[(t + 1) & 1];
-                m->pwms_out = t == T - 1 || (counted(t) && (st_ic || st_best)) ? b_pwms.p : nullptr;
+                m->pwms_out = t == T - 1 || (count && (want.ic || want.best)) ? b_pwms.p : nullptr;
                 m->stream = stream_sweep((uint64_t)(first_sweep + t));
             }
             ba.sweep = t;
@@ -1684,14 +1475,14 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
                 HIP_TRY(c, gs_run_multi_batch_sweep_launch(ao, bo, (int)ogrid, (size_t)lds,
                                                            c->stream));
             }
-            if (counted(t)) {  // the consumer of this sweep's state, before the next sweep's launch
+            if (count) {  // the consumer of this sweep's state, before the next sweep's launch
                 sa.n_chains = nc;
                 sa.chains = ba.chains;
                 sa.skip = b_agg[nxt] + (int64_t)R * cells;
                 sa.cnt = b_cnt[(t + 1) & 1];
                 sa.pos = b_pos[(t + 1) & 1];
                 sa.pwms = b_pwms;
-                sa.ic = s_ic ? s_ic + (t - stats->burn_in) / stats->thin : nullptr;
+                sa.ic = want.ic ? st.dev<double>(kStatIc) + plan.slot(t) : nullptr;
                 sa.sweep = first_sweep + t;
                 const int sblocks = c->tune.run_stats_blocks > 0
                                         ? c->tune.run_stats_blocks
@@ -1780,7 +1571,7 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         HIP_TRY(c, ev.mark());
         // the reduction of the bins and site counts as the last round's last statistics
         // launch left them
-        if (sum) GS_TRY(srun.enqueue(W, M, s_occ, s_sites, s_off, H, R, n_counted, *sum));
+        if (sum) GS_TRY(srun.enqueue(W, M, sa.occ, sa.sites, sa.off, H, R, n_counted, *sum));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;
     }();
@@ -1802,19 +1593,7 @@ int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, i
         HIP_TRY(c, hipMemcpyAsync(pwms_out, b_pwms, (size_t)rows * 8, hipMemcpyDeviceToHost,
                                   c->stream));
     HIP_TRY(c, hipMemcpyAsync(herr.data(), b_err, (size_t)R * 8, hipMemcpyDeviceToHost, c->stream));
-    const auto down = [&](void *dst, const void *src, int64_t bytes) -> hipError_t {
-        return bytes > 0 ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
-                         : hipSuccess;
-    };
-    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, s_occ, (int64_t)R * H * 4));
-    if (st_sites_down) HIP_TRY(c, down(stats->sites_out, s_sites, rows * (M + 1) * 4));
-    if (st_ic) HIP_TRY(c, down(stats->ic_out, s_ic, R * n_counted * 8));
-    if (st_best) {
-        HIP_TRY(c, down(stats->best_sweep_out, s_bsweep, (int64_t)R * 8));
-        HIP_TRY(c, down(stats->best_cnt_out, s_bcnt, rows * 4));
-        HIP_TRY(c, down(stats->best_pos_out, s_bpos, rows * cap * 4));
-        HIP_TRY(c, down(stats->best_pwms_out, s_bpwms, rows * 8));
-    }
+    if (stats) GS_TRY(st.download(*stats));
     if (sum) {
         GS_TRY(srun.download(*sum));
         srun.finish();

@@ -684,147 +684,5 @@ int site_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R
 int multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, const uint64_t *seeds,
                 int32_t R, int32_t mode, int32_t max_passes, int32_t cap, int32_t *cnt_out,
                 int32_t *pos_out, double *pwms_out, int32_t *passes_out, int32_t *status_out);
-// The caller's side of gs_motif_run_batch_stats and gs_run_sweeps_stats: which sweeps count and
-// where the chains' statistics go (each nullable; the best rows go with best_sweep_out).
-struct RunStats {
-    int32_t burn_in, thin;
-    int32_t *occ_out;
-    double *ic_out;
-    int64_t *best_sweep_out;
-    int32_t *best_pos_out;
-    double *best_pwms_out;
-    // gs_run_sweeps_summary / gs_motif_run_summary / gs_motif_run_batch_summary: the
-    // reduction of the bins (null: none)
-    const struct SummaryOut *sum = nullptr;
-    bool any() const;
-};
-// Where a chain summary goes, each group nullable as a whole: the chains'
-// modes, the chains' cells, the four pooled outputs.
-struct SummaryOut {
-    int32_t *mode_pos, *mode_count;  // [n_chains][n_local]
-    int64_t *counts;                 // [n_chains][A * W + A]
-    int32_t *pool_pos;               // [n_local]
-    int64_t *pool_count;             // [n_local]
-    int64_t *pool_counts;            // [A * W + A]
-    int32_t *n_pooled;               // [1]
-    bool modes() const { return mode_pos && mode_count; }
-    bool pool() const { return pool_pos && pool_count && pool_counts && n_pooled; }
-    bool any() const { return modes() || counts || pool(); }
-    // half of a group given
-    bool ragged() const {
-        return (mode_pos != nullptr) != (mode_count != nullptr) ||
-               ((pool_pos || pool_count || pool_counts || n_pooled) && !pool());
-    }
-    int64_t bytes(int64_t R, int64_t n, int64_t cells) const {
-        return (modes() ? R * n * 8 : 0) + (counts ? R * cells * 8 : 0) +
-               (pool() ? n * 12 + cells * 8 + R * 4 + 8 : 0);
-    }
-};
-inline bool RunStats::any() const {
-    return occ_out || ic_out || best_sweep_out || (sum && sum->any());
-}
-// The reduction of R histograms resident at d_occ ([R][H], bins of d_off) behind whatever is
-// on the stream: enqueue() allocates the result slab, zeroes its cells and launches between
-// two events; download() enqueues the copies to the caller's arrays; finish(), after the
-// caller's synchronisation, reads the device time into the context.  The slab lives until
-// the object goes, which the caller lets happen only with nothing in flight.
-struct SummaryRun {
-    gs_ctx *c;
-    char *slab = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t o_mpos = 0, o_mcnt = 0, o_counts = 0, o_ppos = 0, o_pcnt = 0, o_pcounts = 0, o_np = 0;
-    int64_t R = 0, n = 0, cells = 0;
-    explicit SummaryRun(gs_ctx *ctx) : c(ctx) {}
-    SummaryRun(const SummaryRun &) = delete;
-    SummaryRun &operator=(const SummaryRun &) = delete;
-    ~SummaryRun();
-    int enqueue(int32_t W, const int32_t *d_occ, const int64_t *d_off, int64_t H, int32_t R,
-                int64_t n_counted, const SummaryOut &out);
-    int download(const SummaryOut &out);
-    void finish();
-};
-int occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
-                      const SummaryOut &out);
-// (stats null, or with no output: gs_motif_run_batch)
-int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const uint64_t *seeds,
-              int32_t R, int64_t first_sweep, int32_t mode, const double *u, int32_t *pos_inout,
-              double *pwms_out, int32_t *status_out, const RunStats *stats = nullptr);
-int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off);
-int starts_batch(gs_ctx *c, int32_t W, double pc, const uint64_t *seeds, int32_t R, int32_t mode,
-                 double *score_out, int32_t *pos_out, int32_t *status_out);
-// Where a list chain summary goes, each group nullable as a whole: the
-// chains' modes (five arrays), the chains' cells, the seven pooled outputs.
-struct ListSummaryOut {
-    int32_t *mode_sites, *mode_sites_count, *mode_cnt;  // [n_chains][n_local]
-    int32_t *mode_pos, *mode_count;                     // [n_chains][n_local][M]
-    int64_t *counts;                                    // [n_chains][A * W + A]
-    int32_t *pool_sites;                                // [n_local]
-    int64_t *pool_sites_count;                          // [n_local]
-    int32_t *pool_cnt;                                  // [n_local]
-    int32_t *pool_pos;                                  // [n_local][M]
-    int64_t *pool_count;                                // [n_local][M]
-    int64_t *pool_counts;                               // [A * W + A]
-    int32_t *n_pooled;                                  // [1]
-    bool modes() const {
-        return mode_sites && mode_sites_count && mode_cnt && mode_pos && mode_count;
-    }
-    bool pool() const {
-        return pool_sites && pool_sites_count && pool_cnt && pool_pos && pool_count &&
-               pool_counts && n_pooled;
-    }
-    bool any() const { return modes() || counts || pool(); }
-    // half of a group given
-    bool ragged() const {
-        return ((mode_sites || mode_sites_count || mode_cnt || mode_pos || mode_count) && !modes()) ||
-               ((pool_sites || pool_sites_count || pool_cnt || pool_pos || pool_count ||
-                 pool_counts || n_pooled) && !pool());
-    }
-    int64_t bytes(int64_t R, int64_t n, int64_t cells, int64_t M) const {
-        return (modes() ? R * n * (12 + 8 * M) : 0) + (counts ? R * cells * 8 : 0) +
-               (pool() ? n * (16 + 12 * M) + cells * 8 + R * 4 + 8 : 0);
-    }
-};
-// SummaryRun for list bins: the reduction of R list histograms resident at d_occ ([R][H]) and
-// d_sites ([R][n][M + 1]) behind whatever is on the stream.
-struct ListSummaryRun {
-    gs_ctx *c;
-    char *slab = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t o_counts = 0, o_pcounts = 0, o_np = 0, o_psc = 0, o_pcount = 0, o_ms = 0, o_msc = 0,
-            o_mcnt = 0, o_mpos = 0, o_mcount = 0, o_ps = 0, o_pcnt = 0, o_ppos = 0;
-    int64_t R = 0, n = 0, cells = 0, M = 0;
-    explicit ListSummaryRun(gs_ctx *ctx) : c(ctx) {}
-    ListSummaryRun(const ListSummaryRun &) = delete;
-    ListSummaryRun &operator=(const ListSummaryRun &) = delete;
-    ~ListSummaryRun();
-    int enqueue(int32_t W, int32_t M, const int32_t *d_occ, const int32_t *d_sites,
-                const int64_t *d_off, int64_t H, int32_t R, int64_t n_counted,
-                const ListSummaryOut &out);
-    int download(const ListSummaryOut &out);
-    void finish();
-};
-int list_occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ,
-                           const int32_t *sites, int32_t R, int64_t n_counted,
-                           const ListSummaryOut &out);
-// The caller's side of gs_motif_run_multi_batch_stats (each statistic nullable; the three
-// best rows go with best_sweep_out).
-struct RunMultiStats {
-    int32_t burn_in, thin;
-    int32_t *occ_out, *sites_out;
-    double *ic_out;
-    int64_t *best_sweep_out;
-    int32_t *best_cnt_out, *best_pos_out;
-    double *best_pwms_out;
-    // gs_motif_run_multi_batch_summary: the reduction of the bins and site counts (null: none)
-    const ListSummaryOut *sum = nullptr;
-    bool any() const {
-        return occ_out || sites_out || ic_out || best_sweep_out || (sum && sum->any());
-    }
-};
-// (stats null, or with no output: gs_motif_run_multi_batch)
-int run_multi_batch(gs_ctx *c, int32_t M, int32_t W, double pc, double cutoff, int32_t T,
-                    const uint64_t *seeds, int32_t R, int64_t first_sweep, int32_t mode, int32_t cap,
-                    const double *u, int32_t *cnt_inout, int32_t *pos_inout, double *pwms_out,
-                    int32_t *status_out, const RunMultiStats *stats = nullptr);
 
 }  // namespace gs_host

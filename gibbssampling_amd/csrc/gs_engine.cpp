@@ -2,7 +2,7 @@
 // the choice of sweep kernel (general / DNA) and its launch geometry, RCCL
 // all-reduces, hipGraph capture of sweep chains, the greedy / site / list-path
 // drivers.  gs_api.cpp validates arguments and calls in here.
-#include "gs_ctx.h"
+#include "gs_stats.h"
 
 namespace gs_host {
 
@@ -1081,8 +1081,8 @@ hipGraphExec_t sweep_graph(gs_ctx *c, double pc, double cutoff, uint64_t seed) {
 // with the explicit uniforms u[t] when given; a counted sweep writes its PWMS as the last one
 // does and is followed on the stream by one launch of gs_run_stats_kernel, which reads
 // d_pos[cur_pos], d_pwms and the error word that sweep left; one synchronisation at the end,
-// one download, then the status gs_synchronize would give).  The statistics live in one
-// device slab of the call: offsets, running best, trace, best PWMS, bins, best positions.
+// one download, then the status gs_synchronize would give).  The statistics live in the
+// call's StatsSlab.
 int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t seed,
                int64_t first_sweep, const double *u, const RunStats *stats) {
     int rc;
@@ -1091,69 +1091,45 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
     const bool st_any = stats && stats->any() && n > 0;
     // the bins are kept on the device for the caller or for the summary (§9.28), and come
     // down only for the caller
-    const SummaryOut *sum = st_any && stats->sum && stats->sum->any() ? stats->sum : nullptr;
-    const bool st_occ = st_any && (stats->occ_out || sum), st_occ_down = st_any && stats->occ_out,
-               st_ic = st_any && stats->ic_out, st_best = st_any && stats->best_sweep_out;
-    const auto counted = [&](int32_t t) {
-        return st_any && t >= stats->burn_in && (t - stats->burn_in) % stats->thin == 0;
-    };
-    const int64_t n_counted = stats && stats->burn_in < n_sweeps
-                                  ? ((int64_t)n_sweeps - stats->burn_in + stats->thin - 1) / stats->thin
-                                  : 0;
+    const SummaryOut *sum = st_any && stats->summed() ? stats->sum : nullptr;
+    const StatsWant want = st_any ? stats->want() : StatsWant{};
+    const CountPlan plan = stats ? stats->plan(n_sweeps) : CountPlan{n_sweeps, 1, n_sweeps};
+    const int64_t n_counted = plan.n_counted();
     if (stats) c->run_stats_ms[0] = c->run_stats_ms[1] = 0.0;
-    std::vector<int64_t> h_off;  // alive until its upload is over
     // the call's device memory, freed on every path once nothing is in flight on it
     struct Slabs {
         gs_ctx *c;
-        char *stat = nullptr;
         double *u = nullptr;
         std::vector<hipEvent_t> ev;
         ~Slabs() {
-            if (stat || u) (void)hipStreamSynchronize(c->stream);
-            dfree(stat);
+            if (u) (void)hipStreamSynchronize(c->stream);
             dfree(u);
             for (hipEvent_t e : ev) c->ev_pool.push_back(e);
         }
     } m{c};
+    StatsSlab st(c);
     SummaryRun srun(c);
     ChainStatsArgs sa{};
-    const int64_t H = st_occ ? occupancy_offsets(c, c->W, nullptr) : 0;
-    // (8-byte parts first: every part stays aligned to its element)
-    const int64_t o_off = 0, o_best = o_off + (st_occ ? (n + 1) * 8 : 0),
-                  o_ic = o_best + (st_best ? 16 : 0), o_bpwms = o_ic + (st_ic ? n_counted * 8 : 0),
-                  o_occ = o_bpwms + (st_best ? n * 8 : 0), o_bpos = o_occ + (st_occ ? H * 4 : 0),
-                  stat_bytes = o_bpos + (st_best ? n * 4 : 0);
+    const int64_t H = want.occ ? occupancy_offsets(c, c->W, nullptr) : 0;
     int bin_blocks = 0;
     if (st_any) {
-        HIP_TRY(c, hipMalloc(&m.stat, (size_t)std::max<int64_t>(stat_bytes, 8)));
+        if ((rc = st.init(c->W, 1, H, n_counted, 1, 1, false, want))) return rc;
         sa.n_local = c->n_local;
         sa.atomic = c->tune.run_stats_atomic;
         sa.copy_inline = c->n_local < kStatsCopyLaunch ? 1 : 0;
         sa.err = c->d_err_code;
         sa.pwms = c->d_pwms;
-        if (st_occ) {
-            h_off.resize((size_t)n + 1);
-            occupancy_offsets(c, c->W, h_off.data());
-            HIP_TRY(c, hipMemcpyAsync(m.stat + o_off, h_off.data(), (size_t)(n + 1) * 8,
-                                      hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemsetAsync(m.stat + o_occ, 0, (size_t)H * 4, c->stream));
-            sa.off = (const int64_t *)(m.stat + o_off);
-            sa.occ = (int32_t *)(m.stat + o_occ);
-            // 256 targets a workgroup while the GPU is four deep
+        sa.off = st.dev<int64_t>(kStatOff);
+        sa.occ = st.dev<int32_t>(kStatOcc);
+        sa.best_ic = st.dev<double>(kStatBestIc);
+        sa.best_sweep = st.dev<int64_t>(kStatBestSweep);
+        sa.best_pwms = st.dev<double>(kStatBestPwms);
+        sa.best_pos = st.dev<int32_t>(kStatBestPos);
+        // 256 targets a workgroup while the GPU is four deep
+        if (want.occ)
             bin_blocks = c->tune.run_stats_blocks > 0
                              ? c->tune.run_stats_blocks
                              : (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 4));
-        }
-        if (st_best) {  // no best yet (-1); the rows zero until a sweep wins
-            HIP_TRY(c, hipMemsetAsync(m.stat + o_best, 0, 8, c->stream));
-            HIP_TRY(c, hipMemsetAsync(m.stat + o_best + 8, 0xff, 8, c->stream));
-            HIP_TRY(c, hipMemsetAsync(m.stat + o_bpwms, 0, (size_t)n * 8, c->stream));
-            HIP_TRY(c, hipMemsetAsync(m.stat + o_bpos, 0, (size_t)n * 4, c->stream));
-            sa.best_ic = (double *)(m.stat + o_best);
-            sa.best_sweep = (int64_t *)(m.stat + o_best + 8);
-            sa.best_pwms = (double *)(m.stat + o_bpwms);
-            sa.best_pos = (int32_t *)(m.stat + o_bpos);
-        }
     }
     if (u && n > 0 && n_sweeps > 0) {
         HIP_TRY(c, hipMalloc(&m.u, (size_t)n_sweeps * n * 8));
@@ -1188,15 +1164,15 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
     // nothing reads them in between, so only the last direct launch computes them, and
     // the counted ones whose PWMS the statistics read
     for (; t < n_sweeps; ++t) {
-        const bool count = counted(t);
+        const bool count = st_any && plan.counted(t);
         if ((rc = one_sweep(c, pc, cutoff, m.u ? m.u + (int64_t)t * n : nullptr, seed,
                             stream_sweep((uint64_t)(first_sweep + t)),
-                            t == n_sweeps - 1 || (count && (st_ic || st_best)))))
+                            t == n_sweeps - 1 || (count && (want.ic || want.best)))))
             return rc;
         if (!count) continue;
         // the consumer of this sweep's state, before the next sweep's launch
         sa.pos = c->d_pos[c->cur_pos];
-        sa.ic = st_ic ? (double *)(m.stat + o_ic) + (t - stats->burn_in) / stats->thin : nullptr;
+        sa.ic = want.ic ? st.dev<double>(kStatIc) + plan.slot(t) : nullptr;
         sa.sweep = first_sweep + t;
         if (timed) HIP_TRY(c, mark());
         HIP_TRY(c, gs_run_stats_launch(sa, bin_blocks, c->stream));
@@ -1205,35 +1181,16 @@ int run_sweeps(gs_ctx *c, double pc, double cutoff, int32_t n_sweeps, uint64_t s
     if (stats) HIP_TRY(c, mark());
     // the reduction of the bins as the last statistics launch left them
     if (sum)
-        if ((rc = srun.enqueue(c->W, sa.occ, sa.off, H, 1, n_counted, *sum))) return rc;
+        if ((rc = srun.enqueue(c->W, 1, sa.occ, nullptr, sa.off, H, 1, n_counted, *sum))) return rc;
     // the rest of the chain by the all-background kernel once a sweep saw the state
     if (n_sweeps > 0 && (rc = bg_check_note(c, pc, cutoff))) return rc;
     if (!stats) return GS_OK;
-    const auto down = [&](void *dst, int64_t o, int64_t bytes) -> hipError_t {
-        return bytes > 0 ? hipMemcpyAsync(dst, m.stat + o, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)
-                         : hipSuccess;
-    };
-    if (st_occ_down) HIP_TRY(c, down(stats->occ_out, o_occ, H * 4));
+    if (st_any && (rc = st.download(*stats))) return rc;
     if (sum)
         if ((rc = srun.download(*sum))) return rc;
-    if (st_ic) HIP_TRY(c, down(stats->ic_out, o_ic, n_counted * 8));
-    if (st_best) {
-        HIP_TRY(c, down(stats->best_sweep_out, o_best + 8, 8));
-        HIP_TRY(c, down(stats->best_pos_out, o_bpos, n * 4));
-        HIP_TRY(c, down(stats->best_pwms_out, o_bpwms, n * 8));
-    }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (sum) srun.finish();
-    if (n == 0) {  // no sequences: no bins, and no counted sweep completes
-        if (stats->sum) {
-            SummaryRun none(c);
-            none.R = 1;
-            none.cells = (int64_t)c->A * c->W + c->A;
-            (void)none.download(*stats->sum);
-        }
-        if (stats->ic_out) std::fill(stats->ic_out, stats->ic_out + n_counted, std::nan(""));
-        if (stats->best_sweep_out) *stats->best_sweep_out = -1;
-    }
+    if (n == 0) (void)stats_of_nothing(c, c->W, 1, n_counted, *stats);
     float ms = 0.0f;
     double stat_ms = 0.0;
     for (size_t i = 1; i + 2 < m.ev.size(); i += 2)

@@ -400,17 +400,12 @@ class MotifSampler:
         sweep kernels: the way to a posterior from about 2 000 sequences on, where the chain
         batch (runSweepsBatchedStats) no longer pays.  A chain that raises
         raises here."""
-        if len(motifMem) != len(sources):
-            raise _native.ArgumentError(_native.GS_E_ARG, "motifMem and sources differ in length")
-        if not _is_single(1, motifMem):
-            raise _native.ArgumentError(_native.GS_E_ARG,
-                                        "the chain statistics need single positions")
+        start = _single_start(motifMem, sources)
         ctx = _bind(alphabet, sources, device)
         pos, pwms, st = ctx.motif_run_stats(motifLength, pseudoCount, cutOff, sweeps,
-                                            int(seed) & (2**64 - 1), _single_positions(motifMem),
-                                            first_sweep, burn_in=burn_in, thin=thin)
-        best = [_motif_indices(st["best_pos"], st["best_pwms"]) if st["best_sweep"][0] >= 0
-                else []]
+                                            int(seed) & (2**64 - 1), start, first_sweep,
+                                            burn_in=burn_in, thin=thin)
+        best = _best_states(st, single_chain=True)
         stats = ChainStats(st["occupancy"][None, :], st.get("offsets", np.zeros(1, np.int64)),
                            st["ic"][None, :], st["best_sweep"], best)
         return _motif_indices(pos, pwms), stats
@@ -425,18 +420,12 @@ class MotifSampler:
         and the count matrix over the counted states, without the histogram coming down
         (DESIGN.md §9.28).  occupancy=True also returns the bins.  A chain that raises raises
         here."""
-        if len(motifMem) != len(sources):
-            raise _native.ArgumentError(_native.GS_E_ARG, "motifMem and sources differ in length")
-        if not _is_single(1, motifMem):
-            raise _native.ArgumentError(_native.GS_E_ARG,
-                                        "the chain statistics need single positions")
+        start = _single_start(motifMem, sources)
         ctx = _bind(alphabet, sources, device)
         pos, pwms, st = ctx.motif_run_summary(motifLength, pseudoCount, cutOff, sweeps,
-                                              int(seed) & (2**64 - 1), _single_positions(motifMem),
-                                              first_sweep, burn_in=burn_in, thin=thin,
-                                              occupancy=occupancy)
-        best = [_motif_indices(st["best_pos"], st["best_pwms"]) if st["best_sweep"][0] >= 0
-                else []]
+                                              int(seed) & (2**64 - 1), start, first_sweep,
+                                              burn_in=burn_in, thin=thin, occupancy=occupancy)
+        best = _best_states(st, single_chain=True)
         n_counted = st["ic"].shape[0]
         # the single chain finished (a raise raised above): it is the pool
         summary = ChainSummary(st["mode_pos"][None, :], st["mode_count"][None, :],
@@ -461,26 +450,14 @@ class MotifSampler:
         if motifAmount != 1:
             raise _native.ArgumentError(_native.GS_E_ARG,
                                         "the chain statistics need motifAmount = 1")
-        pos = None
-        if motifMems is not None:
-            if len(motifMems) != len(seeds):
-                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
-            if any(len(m) != len(sources) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "a motifMem and sources differ in length")
-            if not all(_is_single(1, m) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "the chain statistics need single positions")
-            pos = np.array([_single_positions(m) for m in motifMems],
-                           np.int32).reshape(len(seeds), len(sources))
+        pos = _chain_starts(motifMems, seeds, sources, single=True)
         ctx = _bind(alphabet, sources, device)
         pos, pwms, status, st = ctx.motif_run_batch_summary(
             motifLength, pseudoCount, cutOff, sweeps, seeds, pos, init_mode, first_sweep,
             burn_in=burn_in, thin=thin, occupancy=occupancy)
         _raise_failed_chain(status)
         R = len(seeds)
-        best = [_motif_indices(st["best_pos"][r], st["best_pwms"][r]) if st["best_sweep"][r] >= 0
-                else [] for r in range(R)]
+        best = _best_states(st)
         summary = ChainSummary(st["mode_pos"], st["mode_count"], st["counts"], st["pooled_pos"],
                                st["pooled_count"], st["pooled_counts"], int(st["n_pooled"][0]),
                                st["ic"].shape[1], st["ic"], st["best_sweep"], best,
@@ -504,20 +481,12 @@ class MotifSampler:
         Context.motif_run_multi_batch call: faster than the loop at every shape measured,
         5 to 2 000 sequences a chain; not measured beyond."""
         seeds = [int(s) & (2**64 - 1) for s in seeds]
-        pos = None
-        if motifMems is not None:
-            if len(motifMems) != len(seeds):
-                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
-            if any(len(m) != len(sources) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "a motifMem and sources differ in length")
+        _chain_starts(motifMems, seeds, sources)
         if not all(_is_single(motifAmount, m) for m in motifMems or [[]]):
             return _run_lists_batched(motifAmount, motifLength, pseudoCount, cutOff, alphabet,
                                       sources, sweeps, seeds, motifMems, init_mode, first_sweep,
                                       device)
-        if motifMems is not None:
-            pos = np.array([_single_positions(m) for m in motifMems],
-                           np.int32).reshape(len(seeds), len(sources))
+        pos = _chain_starts(motifMems, seeds, sources, single=True)
         ctx = _bind(alphabet, sources, device)
         pos, pwms, status = ctx.motif_run_batch(motifLength, pseudoCount, cutOff, sweeps, seeds,
                                                 pos, init_mode, first_sweep)
@@ -538,26 +507,14 @@ class MotifSampler:
         if motifAmount != 1:
             raise _native.ArgumentError(_native.GS_E_ARG,
                                         "the chain statistics need motifAmount = 1")
-        pos = None
-        if motifMems is not None:
-            if len(motifMems) != len(seeds):
-                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
-            if any(len(m) != len(sources) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "a motifMem and sources differ in length")
-            if not all(_is_single(1, m) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "the chain statistics need single positions")
-            pos = np.array([_single_positions(m) for m in motifMems],
-                           np.int32).reshape(len(seeds), len(sources))
+        pos = _chain_starts(motifMems, seeds, sources, single=True)
         ctx = _bind(alphabet, sources, device)
         pos, pwms, status, st = ctx.motif_run_batch_stats(
             motifLength, pseudoCount, cutOff, sweeps, seeds, pos, init_mode, first_sweep,
             burn_in=burn_in, thin=thin)
         _raise_failed_chain(status)
         R = len(seeds)
-        best = [_motif_indices(st["best_pos"][r], st["best_pwms"][r]) if st["best_sweep"][r] >= 0
-                else [] for r in range(R)]
+        best = _best_states(st)
         stats = ChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)), st["ic"],
                            st["best_sweep"], best)
         return [_motif_indices(pos[r], pwms[r]) for r in range(R)], stats
@@ -573,12 +530,7 @@ class MotifSampler:
         sweeps (t >= burn_in, every thin-th), the trace of informationContent, and the best
         state each chain visited."""
         seeds = [int(s) & (2**64 - 1) for s in seeds]
-        if motifMems is not None:
-            if len(motifMems) != len(seeds):
-                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
-            if any(len(m) != len(sources) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "a motifMem and sources differ in length")
+        _chain_starts(motifMems, seeds, sources)
         cap, cnt, pos = _chain_lists(motifAmount, motifMems, len(sources))
         ctx = _bind(alphabet, sources, device)
         cnt, pos, pwms, status, st = ctx.motif_run_multi_batch_stats(
@@ -586,8 +538,7 @@ class MotifSampler:
             first_sweep, cap, burn_in=burn_in, thin=thin)
         _raise_failed_chain(status)
         R = len(seeds)
-        best = [_motif_lists(st["best_cnt"][r], st["best_pos"][r], st["best_pwms"][r])
-                if st["best_sweep"][r] >= 0 else [] for r in range(R)]
+        best = _best_states(st)
         stats = ListChainStats(st["occupancy"], st.get("offsets", np.zeros(1, np.int64)),
                                st["ic"], st["best_sweep"], best, st["sites"], int(motifLength))
         return [_motif_lists(cnt[r], pos[r], pwms[r]) for r in range(R)], stats
@@ -605,12 +556,7 @@ class MotifSampler:
         slabs coming down.  occupancy=True also returns the bins and the
         site counts."""
         seeds = [int(s) & (2**64 - 1) for s in seeds]
-        if motifMems is not None:
-            if len(motifMems) != len(seeds):
-                raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
-            if any(len(m) != len(sources) for m in motifMems):
-                raise _native.ArgumentError(_native.GS_E_ARG,
-                                            "a motifMem and sources differ in length")
+        _chain_starts(motifMems, seeds, sources)
         cap, cnt, pos = _chain_lists(motifAmount, motifMems, len(sources))
         ctx = _bind(alphabet, sources, device)
         cnt, pos, pwms, status, st = ctx.motif_run_multi_batch_summary(
@@ -618,8 +564,7 @@ class MotifSampler:
             first_sweep, cap, burn_in=burn_in, thin=thin, occupancy=occupancy, sites=occupancy)
         _raise_failed_chain(status)
         R = len(seeds)
-        best = [_motif_lists(st["best_cnt"][r], st["best_pos"][r], st["best_pwms"][r])
-                if st["best_sweep"][r] >= 0 else [] for r in range(R)]
+        best = _best_states(st)
         summary = ListChainSummary(
             st["mode_sites"], st["mode_sites_count"], st["mode_cnt"], st["mode_pos"],
             st["mode_count"], st["counts"], st["pooled_sites"], st["pooled_sites_count"],
@@ -873,6 +818,45 @@ def _raise_failed_chain(status) -> None:
         if st != _native.GS_OK:
             raise _native._ERRORS.get(int(st), _native.DeviceError)(
                 int(st), f"chain {r} of the batch failed")
+
+
+def _single_start(motifMem, sources) -> np.ndarray:
+    """The single chain statistics' start: one single position a sequence -> pos[N]."""
+    if len(motifMem) != len(sources):
+        raise _native.ArgumentError(_native.GS_E_ARG, "motifMem and sources differ in length")
+    if not _is_single(1, motifMem):
+        raise _native.ArgumentError(_native.GS_E_ARG, "the chain statistics need single positions")
+    return _single_positions(motifMem)
+
+
+def _chain_starts(motifMems, seeds, sources, single: bool = False):
+    """What every batched chain driver checks of the starts it is given: one motifMem a seed,
+    one entry a sequence.  With `single` they are single positions too -> pos[R, N] (None
+    without motifMems, or without `single`)."""
+    if motifMems is None:
+        return None
+    if len(motifMems) != len(seeds):
+        raise _native.ArgumentError(_native.GS_E_ARG, "motifMems and seeds differ in length")
+    if any(len(m) != len(sources) for m in motifMems):
+        raise _native.ArgumentError(_native.GS_E_ARG, "a motifMem and sources differ in length")
+    if not single:
+        return None
+    if not all(_is_single(1, m) for m in motifMems):
+        raise _native.ArgumentError(_native.GS_E_ARG, "the chain statistics need single positions")
+    return np.array([_single_positions(m) for m in motifMems],
+                    np.int32).reshape(len(seeds), len(sources))
+
+
+def _best_states(st, single_chain: bool = False) -> list:
+    """The best state every chain visited, from a statistics dict: MotifIndex lists by
+    _motif_lists where the chains have Positions lists ("best_cnt"), else by _motif_indices;
+    [] for a chain that completed no counted sweep."""
+    cnt, pos, pwms = st.get("best_cnt"), st["best_pos"], st["best_pwms"]
+    if single_chain:
+        pos, pwms = pos[None], pwms[None]
+    return [[] if sweep < 0 else
+            _motif_indices(pos[r], pwms[r]) if cnt is None else
+            _motif_lists(cnt[r], pos[r], pwms[r]) for r, sweep in enumerate(st["best_sweep"])]
 
 
 def _chain_lists(motifAmount, motifMems, n_sources):

@@ -14,6 +14,7 @@ from gibbssampling_amd.sampler import createMotifIndex
 from test_gpu_run_multi_batch import PC, SEEDS, SHAPES, bits, data, one_lists
 from test_gpu_run_multi_batch_stats import STATS, T_STEP, bound, counted_sweeps, steps_of
 from test_gpu_run_multi_batch_stats import same as same_array
+from test_gpu_summary import G_BURN, G_SEEDS, G_T, G_THIN, G_W, check_subset, group_data
 
 pytestmark = pytest.mark.gpu
 
@@ -671,3 +672,35 @@ def test_mirror_returns_the_summary_of_the_list_chains():
     _, s = MotifSampler.runSweepsBatchedListSummary(*args, occupancy=True, **kw)
     assert np.array_equal(s.occupancy, st.occupancy) and np.array_equal(s.sites, st.sites)
     assert np.array_equal(s.offsets, st.offsets)
+
+
+# ---- group by group: what a call returns does not depend on what else was asked for ----
+# (the data, shape and comparison of test_gpu_summary.py's group tests; lists of up to
+# motifAmount 3 sites at capacity 5)
+
+G_M, G_CAP = 3, 5
+G_LIST_STATS = {"occupancy": ("offsets", "occupancy"), "sites": ("sites",), "ic": ("ic",),
+                "best": ("best_sweep", "best_cnt", "best_pos", "best_pwms")}
+LIST_GROUPS = dict(G_LIST_STATS, **GROUPS)
+
+
+@pytest.fixture(scope="module")
+def group_lists(gpu_ctx):
+    gpu_ctx.set_sequences(*group_data(), DNA)
+    kw = dict(init_mode=1, cap=G_CAP, burn_in=G_BURN, thin=G_THIN)
+    return kw, gpu_ctx.motif_run_multi_batch_summary(G_M, G_W, PC, 1.0, G_T, G_SEEDS,
+                                                     occupancy=True, sites=True, **kw)
+
+
+@pytest.mark.parametrize("only", list(LIST_GROUPS) + ["none", "stats"])
+def test_lists_group_by_group(gpu_ctx, group_lists, only):
+    kw, ref = group_lists
+    gpu_ctx.set_sequences(*group_data(), DNA)
+    assert ref[4]["n_counted"] == 3 and not ref[3].any() and ref[1].shape[2] == G_CAP
+    if only == "stats":
+        got = gpu_ctx.motif_run_multi_batch_stats(G_M, G_W, PC, 1.0, G_T, G_SEEDS, **kw)
+        check_subset(ref, got, dict(G_LIST_STATS), only)
+    else:
+        got = gpu_ctx.motif_run_multi_batch_summary(G_M, G_W, PC, 1.0, G_T, G_SEEDS, **kw,
+                                                    **{g: g == only for g in LIST_GROUPS})
+        check_subset(ref, got, LIST_GROUPS, only, extra=("n_counted",))

@@ -597,3 +597,98 @@ def test_edges(gpu_ctx, batch):
     again = ctx.motif_sampling(W, PC, CUTOFF, 31)
     assert np.array_equal(again[0], want[0]) and again[2] == want[2]
     assert np.array_equal(bits(again[1]), bits(want[1]))
+
+
+# ---- group by group: what a call returns does not depend on what else was asked for ----
+# The statistics' device slab and the summary's are carved from the parts a call asks for
+# (DESIGN.md §9.30): a part left out must move nothing else.  Odd sizes everywhere (ragged
+# lengths, W = 3, three chains, three counted sweeps), so that every part boundary is one a
+# wrong alignment would show at.
+
+G_LENS, G_W, G_T, G_BURN, G_THIN = (9, 10, 12, 13, 17), 3, 7, 2, 2
+G_SEEDS = [11, 5_000_000_011, 23]
+G_STATS = {"occupancy": ("offsets", "occupancy"), "ic": ("ic",),
+           "best": ("best_sweep", "best_pos", "best_pwms")}
+
+
+def group_data():
+    offsets = np.concatenate([[0], np.cumsum(G_LENS)]).astype(np.int64)
+    codes = np.frombuffer(DNA, np.uint8)[np.random.default_rng(90).integers(0, 4, offsets[-1])]
+    return np.ascontiguousarray(codes), offsets
+
+
+def same_bits(got, want, key):
+    """Bit for bit: integers as they are, doubles as uint64; scalars by value."""
+    if not isinstance(want, np.ndarray):
+        assert got == want, key
+        return
+    assert got.dtype == want.dtype and got.shape == want.shape, key
+    if want.dtype == np.float64:
+        got, want = got.view(np.uint64), want.view(np.uint64)
+    assert np.array_equal(got, want), key
+
+
+def check_subset(ref, got, groups, only, extra=()):
+    """`got` (chain outputs..., stats) of a call that asked for `only` (a group's name, "none",
+    or "stats": every statistic through the _stats method) against the all-groups call."""
+    for k, (a, b) in enumerate(zip(got[:-1], ref[:-1])):
+        same_bits(a, b, f"chain output {k}")
+    want_keys = set(extra)
+    for g in (groups if only == "stats" else [only] if only != "none" else []):
+        want_keys |= set(groups[g])
+    assert set(got[-1]) == want_keys
+    for key in want_keys:
+        same_bits(got[-1][key], ref[-1][key], key)
+
+
+@pytest.fixture(scope="module")
+def group_single(gpu_ctx):
+    codes, offsets = group_data()
+    gpu_ctx.set_sequences(codes, offsets, DNA)
+    p0 = init_positions(offsets, G_W, 91)
+    kw = dict(burn_in=G_BURN, thin=G_THIN)
+    return p0, kw, [gpu_ctx.motif_run_summary(G_W, PC, 1.0, G_T, s, p0, occupancy=True, **kw)
+                    for s in G_SEEDS]
+
+
+SINGLE_GROUPS = dict(G_STATS, modes=GROUPS["modes"], counts=GROUPS["counts"])
+
+
+@pytest.mark.parametrize("only", list(SINGLE_GROUPS) + ["none", "stats"])
+def test_single_chain_group_by_group(gpu_ctx, group_single, only):
+    p0, kw, refs = group_single
+    gpu_ctx.set_sequences(*group_data(), DNA)
+    assert refs[0][2]["ic"].shape == (3,)
+    for seed, ref in zip(G_SEEDS, refs):
+        if only == "stats":
+            got = gpu_ctx.motif_run_stats(G_W, PC, 1.0, G_T, seed, p0, **kw)
+        else:
+            got = gpu_ctx.motif_run_summary(G_W, PC, 1.0, G_T, seed, p0, **kw,
+                                            **{g: g == only for g in SINGLE_GROUPS})
+        check_subset(ref, got, dict(G_STATS) if only == "stats" else SINGLE_GROUPS, only,
+                     extra=("status",))
+
+
+@pytest.fixture(scope="module")
+def group_batch(gpu_ctx):
+    codes, offsets = group_data()
+    gpu_ctx.set_sequences(codes, offsets, DNA)
+    kw = dict(init_mode=1, burn_in=G_BURN, thin=G_THIN)
+    return kw, gpu_ctx.motif_run_batch_summary(G_W, PC, 1.0, G_T, G_SEEDS, occupancy=True, **kw)
+
+
+BATCH_GROUPS = dict(G_STATS, **GROUPS)
+
+
+@pytest.mark.parametrize("only", list(BATCH_GROUPS) + ["none", "stats"])
+def test_batch_group_by_group(gpu_ctx, group_batch, only):
+    kw, ref = group_batch
+    gpu_ctx.set_sequences(*group_data(), DNA)
+    assert ref[3]["n_counted"] == 3 and not ref[2].any()
+    if only == "stats":
+        got = gpu_ctx.motif_run_batch_stats(G_W, PC, 1.0, G_T, G_SEEDS, **kw)
+        check_subset(ref, got, dict(G_STATS), only)
+    else:
+        got = gpu_ctx.motif_run_batch_summary(G_W, PC, 1.0, G_T, G_SEEDS, **kw,
+                                              **{g: g == only for g in BATCH_GROUPS})
+        check_subset(ref, got, BATCH_GROUPS, only, extra=("n_counted",))
