@@ -7,12 +7,12 @@ hand-written HIP kernels behind the C ABI in include/gibbs_hip.h.
 from . import bioarray
 from ._native import (ArgumentError, ChecksumOverflowError, Context, DeviceError, GibbsError,
                       RouletteOverrunError, load_library)
-from .sampler import (ChainStats, ChainSummary, ListChainStats, ListChainSummary, MotifIndex,
-                      MotifSampler, SiteSampler, createMotifIndex)
+from .sampler import (ChainAgreement, ChainStats, ChainSummary, ListChainStats, ListChainSummary,
+                      MotifIndex, MotifSampler, SiteSampler, createMotifIndex)
 
 __all__ = [
-    "bioarray", "Context", "load_library", "ChainStats", "ChainSummary", "ListChainStats", "MotifIndex",
-    "ListChainSummary", "MotifSampler",
+    "bioarray", "Context", "load_library", "ChainAgreement", "ChainStats", "ChainSummary",
+    "ListChainStats", "MotifIndex", "ListChainSummary", "MotifSampler",
     "SiteSampler", "createMotifIndex", "GibbsError", "ArgumentError", "RouletteOverrunError",
     "ChecksumOverflowError", "DeviceError",
 ]

@@ -182,6 +182,10 @@ def _declare(lib: C.CDLL, strict: bool = True) -> None:
                                                  i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                  vp, vp, vp]),
         "gs_summary_last_ms": (C.c_int, [vp, vp]),
+        "gs_occupancy_agreement": (C.c_int, [vp, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_motif_run_batch_agreement": (C.c_int, [vp, i32, f64, f64, i32, vp, i32, i64, i32, vp,
+                                                   i32, i32] + [vp] * 21),
+        "gs_agreement_last_ms": (C.c_int, [vp, vp]),
         "gs_state_motif_length": (i32, [vp]),
         "gs_motif_run_multi_batch": (C.c_int, [vp, i32, i32, f64, f64, i32, vp, i32, i64, i32, i32,
                                                vp, vp, vp, vp, vp]),
@@ -869,6 +873,90 @@ class Context:
         """Device milliseconds of the last chain summary's reduction."""
         out = np.zeros(1, np.float64)
         self._check(self.lib.gs_summary_last_ms(self.h, _ptr(out)))
+        return float(out[0])
+
+    def _agreement_outputs(self, R):
+        """The output arrays of a chain agreement of R chains -> dict."""
+        return {"agree": np.zeros(self.n_local, np.int32),
+                "spread": np.zeros(self.n_local, np.int64),
+                "spread_chain": np.full(self.n_local, -1, np.int32),
+                "chain_agree": np.full(R, -1, np.int32),
+                "chain_dist": np.full(R, -1, np.int64),
+                "agree_n_pooled": np.zeros(1, np.int32)}
+
+    _AGREEMENT = ("agree", "spread", "spread_chain", "chain_agree", "chain_dist", "agree_n_pooled")
+
+    def occupancy_agreement(self, W: int, occupancy, n_counted: int, pooled=None) -> dict:
+        """Whether the chains of caller-held histograms occupancy[R, H] (occupancy_offsets(W))
+        agree with their pool, on the device (gs_occupancy_agreement) -> dict.  With P pooled
+        chains and pool the sum of their bins, D(r, n) is the sum over sequence n's bins of
+        |P occupancy[r] - pool|: D / (2 P n_counted) is the total variation distance between
+        the chain's marginal of the sequence and the pooled one.  "agree"[N]: the pooled chains
+        whose first-maximum bin of the sequence is the pool's; "spread"[N] (int64) and
+        "spread_chain"[N]: the largest D(r, n) and the lowest chain that has it ((0, 0, -1)
+        without a pooled chain); "chain_dist"[R] (int64): the sum of the chain's D;
+        "chain_agree"[R]: the sequences whose chain mode is the pool's ((-1, -1) for a chain
+        that is not pooled); "n_pooled"[1].  A chain is pooled when its sequence 0 has n_counted
+        counts (the summaries' rule) or, with pooled[R] given, when its entry is non-zero
+        (ListChainStats.finished() for list chains, whose rows do not sum to n_counted)."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.int32)
+        H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+        if occ.ndim != 2 or (H >= 0 and occ.shape[1] != H):
+            raise ArgumentError(GS_E_ARG, "occupancy needs the shape [chains, bins]")
+        R = occ.shape[0]
+        mask = None
+        if pooled is not None:
+            mask = np.ascontiguousarray(np.asarray(pooled) != 0, dtype=np.int32)
+            if mask.shape != (R,):
+                raise ArgumentError(GS_E_ARG, "pooled needs one entry per chain")
+        out = self._agreement_outputs(R)
+        self._check(self.lib.gs_occupancy_agreement(
+            self.h, int(W), _ptr(occ) if R > 0 else None, R, int(n_counted),
+            _ptr(mask) if R > 0 else None, *(_ptr(out[k]) for k in self._AGREEMENT)))
+        out["n_pooled"] = out.pop("agree_n_pooled")
+        return out
+
+    def motif_run_batch_agreement(self, W: int, pc: float, cutoff: float, n_sweeps: int, seeds,
+                                  pos=None, init_mode: int = 0, first_sweep: int = 0, u=None,
+                                  burn_in: int = 0, thin: int = 1, occupancy: bool = False,
+                                  ic: bool = True, best: bool = True, modes: bool = True,
+                                  counts: bool = True, pool: bool = True, agreement: bool = True,
+                                  strict: bool = False):
+        """motif_run_batch_summary with the chains' agreement with their pool reduced on the
+        device behind the summary (gs_motif_run_batch_agreement) -> (pos[R, N], pwms[R, N],
+        status[R], stats), stats with the arrays of occupancy_agreement ("agree", "spread",
+        "spread_chain", "chain_agree", "chain_dist", and the pool's count as "agree_n_pooled")
+        besides those of motif_run_batch_summary.  A chain that raised is not pooled.  The bins
+        are downloaded only with occupancy=True; agreement=False is motif_run_batch_summary."""
+        seeds, pos, init_mode, u = self._run_batch_args(n_sweeps, seeds, pos, init_mode, u)
+        R, T = len(seeds), int(n_sweeps)
+        burn_in, thin = int(burn_in), int(thin)
+        n_counted = self._n_counted(burn_in, thin, T)
+        pwms = np.zeros((R, self.n_local), np.float64)
+        status = np.zeros(R, np.int32)
+        H = int(self.lib.gs_occupancy_size(self.h, int(W)))
+        stats = self._stats_outputs(W, (R,), n_counted, occupancy, ic, best, H=H)
+        stats.update(self._summary_outputs(W if H >= 0 else None, R, modes, counts, pool))
+        if agreement:
+            stats.update(self._agreement_outputs(R))
+        st = self.lib.gs_motif_run_batch_agreement(
+            self.h, int(W), float(pc), float(cutoff), T, _ptr(seeds), R, int(first_sweep),
+            int(init_mode), _ptr(u), burn_in, thin, _ptr(pos), _ptr(pwms), _ptr(status),
+            _ptr(stats.get("occupancy")), _ptr(stats.get("ic")), _ptr(stats.get("best_sweep")),
+            _ptr(stats.get("best_pos")), _ptr(stats.get("best_pwms")),
+            _ptr(stats.get("mode_pos")), _ptr(stats.get("mode_count")), _ptr(stats.get("counts")),
+            _ptr(stats.get("pooled_pos")), _ptr(stats.get("pooled_count")),
+            _ptr(stats.get("pooled_counts")), _ptr(stats.get("n_pooled")),
+            *(_ptr(stats.get(k)) for k in self._AGREEMENT))
+        if st != GS_OK and (strict or not status.any()):
+            self._check(st)
+        stats["n_counted"] = n_counted
+        return pos, pwms, status, stats
+
+    def agreement_last_ms(self) -> float:
+        """Device milliseconds of the last chain agreement's reduction."""
+        out = np.zeros(1, np.float64)
+        self._check(self.lib.gs_agreement_last_ms(self.h, _ptr(out)))
         return float(out[0])
 
     def _run_multi_batch_args(self, motif_amount, n_sweeps, seeds, cnt, pos, init_mode, cap, u):

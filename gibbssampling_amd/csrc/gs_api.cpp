@@ -726,6 +726,43 @@ int gs_occupancy_summary(gs_ctx *c, int32_t W, const int32_t *occ, int32_t n_cha
                                    n_counted, out);
 }
 
+int gs_occupancy_agreement(gs_ctx *c, int32_t W, const int32_t *occ, int32_t n_chains,
+                           int64_t n_counted, const int32_t *pooled, int32_t *agree_out,
+                           int64_t *spread_out, int32_t *spread_chain_out,
+                           int32_t *chain_agree_out, int64_t *chain_dist_out,
+                           int32_t *n_pooled_out) {
+    if (!c) return GS_E_ARG;
+    const AgreementOut out{{agree_out, spread_out, spread_chain_out, chain_agree_out,
+                            chain_dist_out, n_pooled_out}};
+    if (n_chains < 0 || n_counted < 0 || (n_chains > 0 && !occ) || out.ragged())
+        return fail(c, GS_E_ARG,
+                    "gs_occupancy_agreement: n_chains < 0, n_counted < 0, no bins, or half of "
+                    "the output group");
+    int rc;
+    if ((rc = check_dev(c))) return rc;
+    if ((rc = validate_W(c, W))) return rc;
+    if ((int64_t)c->n_local != c->n_global || c->comm)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_occupancy_agreement: a chain's distance is summed over every sequence: it "
+                    "needs all sequences on one device and no communicator");
+    if (n_chains == 0 || !out.any()) return GS_OK;
+    const int64_t n = c->n_local, H = std::max<int64_t>(0, occupancy_offsets(c, W, nullptr));
+    const int64_t bytes = (int64_t)n_chains * H * 4 + (n + 1) * 8 + agreement_bytes(n_chains, n);
+    if (bytes > kBatchBytesMax)
+        return fail(c, GS_E_UNSUPPORTED,
+                    "gs_occupancy_agreement: the bins and the results take " +
+                        std::to_string(bytes) + " B, more than the " +
+                        std::to_string(kBatchBytesMax) +
+                        " B a call may hold: split the sequences over several contexts");
+    return occupancy_agreement(c, W, occ, n_chains, n_counted, pooled, out);
+}
+
+int gs_agreement_last_ms(const gs_ctx *c, double out[1]) {
+    if (!c || !out) return GS_E_ARG;
+    out[0] = c->agreement_ms;
+    return GS_OK;
+}
+
 int gs_run_stats_last_ms(const gs_ctx *c, double out[2]) {
     if (!c || !out) return GS_E_ARG;
     out[0] = c->run_stats_ms[0];
@@ -1317,7 +1354,7 @@ static int motif_run_batch_entry(gs_ctx *c, int32_t W, double pc, double cutoff,
         return fail(c, GS_E_ARG,
                     "gs_motif_run_batch_stats: burn_in outside [0, n_sweeps], thin < 1, "
                     "best_sweep_out without both best rows (or the reverse), or half of a "
-                    "summary's output group");
+                    "summary's or the agreement's output group");
     if (n_chains == 0) return GS_OK;
     if (!seeds || (c->n_local > 0 && (!pos_inout || !pwms_out))) return GS_E_ARG;
     int rc;
@@ -1379,6 +1416,29 @@ int gs_motif_run_batch_summary(gs_ctx *c, int32_t W, double pc, double cutoff, i
                            pool_mode_count_out, pool_counts_out, n_pooled_out);
     const RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out,
                       &sum};
+    return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
+                                 init_mode, u, pos_inout, pwms_out, status_out, &st);
+}
+
+int gs_motif_run_batch_agreement(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t n_sweeps,
+                                 const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+                                 int32_t init_mode, const double *u, int32_t burn_in, int32_t thin,
+                                 int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+                                 int32_t *occ_out, double *ic_out, int64_t *best_sweep_out,
+                                 int32_t *best_pos_out, double *best_pwms_out,
+                                 int32_t *mode_pos_out, int32_t *mode_count_out,
+                                 int64_t *counts_out, int32_t *pool_mode_pos_out,
+                                 int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+                                 int32_t *n_pooled_out, int32_t *agree_out, int64_t *spread_out,
+                                 int32_t *spread_chain_out, int32_t *chain_agree_out,
+                                 int64_t *chain_dist_out, int32_t *agree_n_pooled_out) {
+    const SummaryOut sum =
+        SummaryOut::single(mode_pos_out, mode_count_out, counts_out, pool_mode_pos_out,
+                           pool_mode_count_out, pool_counts_out, n_pooled_out);
+    const AgreementOut agr{{agree_out, spread_out, spread_chain_out, chain_agree_out,
+                            chain_dist_out, agree_n_pooled_out}};
+    RunStats st{burn_in, thin, occ_out, ic_out, best_sweep_out, best_pos_out, best_pwms_out, &sum};
+    st.agr = &agr;
     return motif_run_batch_entry(c, W, pc, cutoff, n_sweeps, seeds, n_chains, first_sweep,
                                  init_mode, u, pos_inout, pwms_out, status_out, &st);
 }

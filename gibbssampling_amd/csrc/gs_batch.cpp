@@ -886,6 +886,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     // the bins are kept on the device for the caller or for the summary (§9.28), and come
     // down only for the caller
     const SummaryOut *sum = stats && stats->summed() ? stats->sum : nullptr;
+    const AgreementOut *agr = stats && stats->agreed() ? stats->agr : nullptr;
     const StatsWant want = stats ? stats->want() : StatsWant{};
     MultiArgs a{};
     const int64_t lds = multi_args(c, a, 1, W, 1, pc, cutoff, false);
@@ -907,7 +908,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
                       (int64_t)sizeof(SpecCtl)) +
             n * 4 + u_elems * 8 + cpart_bytes + grid * 16 * (int64_t)a.kmax +
             stats_bytes(R, n, H, n_counted, 1, 1, false, want) +
-            (sum ? sum->bytes(R, n, cells, 1) : 0)));
+            (sum ? sum->bytes(R, n, cells, 1) : 0) + (agr ? agreement_bytes(R, n) : 0)));
     if (mode >= 0) GS_TRY(ensure_state(c, W));
     GS_TRY(multi_scratch(c, a, grid, 0));
     // the slabs (row r = chain r)
@@ -937,6 +938,7 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     // every chain
     StatsSlab st(c);
     SummaryRun srun(c);
+    AgreementRun arun(c);
     if (stats) GS_TRY(st.init(W, R, H, n_counted, 1, 1, false, want));
     RunStatsArgs sa{};
     sa.n_chains = R;
@@ -1027,6 +1029,10 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
         HIP_TRY(c, ev.mark());
         // the reduction of the bins as the last statistics launch left them
         if (sum) GS_TRY(srun.enqueue(W, 1, sa.occ, nullptr, sa.off, H, R, n_counted, *sum));
+        // the chains against their pool, which the summary decided if it has the pooled outputs
+        if (agr)
+            GS_TRY(arun.enqueue(sa.occ, sa.off, H, R, n_counted, srun.dev<int32_t>(kPoolFlags),
+                                srun.dev<int32_t>(kNPooled), nullptr));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;
     }();
@@ -1049,6 +1055,10 @@ int run_batch(gs_ctx *c, int32_t W, double pc, double cutoff, int32_t T, const u
     if (sum) {
         GS_TRY(srun.download(*sum));
         srun.finish();
+    }
+    if (agr) {
+        GS_TRY(arun.download(*agr));
+        arun.finish();
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return report_chain_errors(c, herr, status_out, nullptr);
@@ -1116,6 +1126,7 @@ int stats_of_nothing(const gs_ctx *c, int32_t W, int64_t R, int64_t n_counted, c
     if (st.ic_out) std::fill(st.ic_out, st.ic_out + R * n_counted, std::nan(""));
     if (st.best_sweep_out) std::fill(st.best_sweep_out, st.best_sweep_out + R, (int64_t)-1);
     if (st.sum) summary_of_nothing(c, W, R, *st.sum);
+    if (st.agreed()) agreement_of_nothing(R, nullptr, *st.agr);
     return GS_OK;
 }
 
@@ -1240,6 +1251,129 @@ int occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ, const
         if (sites)
             HIP_TRY(c, hipMemcpyAsync(d_sites, sites, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
         GS_TRY(run.enqueue(W, M, d_occ, d_sites, d_off, H, R, n_counted, out));
+        GS_TRY(run.download(out));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }();
+    if (rc) {  // nothing in flight on the slabs when they go
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    run.finish();
+    return GS_OK;
+}
+
+// The chain agreement's device side, over the table of its parts
+// (agreement_slab): one slab, the chains' sums (and a pool count decided here) first, zero.
+AgreementRun::~AgreementRun() {
+    if (slab) (void)hipStreamSynchronize(c->stream);
+    dfree(slab);
+    for (hipEvent_t e : ev)
+        if (e) c->ev_pool.push_back(e);
+}
+
+int AgreementRun::enqueue(const int32_t *d_occ, const int64_t *d_off, int64_t H, int32_t R,
+                          int64_t n_counted, int32_t *d_flags, const int32_t *d_count,
+                          const int32_t *mask) {
+    const int64_t n = c->n_local;
+    c->agreement_ms = 0.0;
+    if (R <= 0 || n <= 0) return GS_OK;
+    const bool shared = d_flags && d_count && !mask;
+    lay = agreement_slab(R, n, !shared, !mask);
+    HIP_TRY(c, hipMalloc(&slab, (size_t)std::max<int64_t>(lay.total, 8)));
+    if (lay.zeroed > 0) HIP_TRY(c, hipMemsetAsync(slab, 0, (size_t)lay.zeroed, c->stream));
+    AgreementArgs a{};
+    a.n_chains = R;
+    a.n_local = c->n_local;
+    a.H = H;
+    a.n_counted = n_counted;
+    a.occ = d_occ;
+    a.off = d_off;
+    a.flags = shared ? d_flags : dev<int32_t>(kAgrFlags);
+    a.n_pooled = dev<int32_t>(kAgrNPooled);
+    a.decide = !shared && !mask;
+    a.agree = dev<int32_t>(kAgrAgree);
+    a.spread = dev<int64_t>(kAgrSpread);
+    a.spread_chain = dev<int32_t>(kAgrSpreadChain);
+    a.chain_agree = dev<int32_t>(kAgrChainAgree);
+    a.chain_dist = dev<int64_t>(kAgrChainDist);
+    d_n_pooled = shared ? d_count : a.n_pooled;
+    if (mask) {
+        h_flags.resize((size_t)R);
+        h_pooled = 0;
+        for (int32_t r = 0; r < R; ++r) h_pooled += h_flags[(size_t)r] = mask[r] != 0;
+        HIP_TRY(c, hipMemcpyAsync(a.flags, h_flags.data(), (size_t)R * 4, hipMemcpyHostToDevice,
+                                  c->stream));
+    }
+    // a wavefront a row, four a workgroup; a workgroup's chains cost up to 2 R atomic adds at
+    // its end, so no more workgroups than keep the GPU eight deep
+    const int blocks =
+        (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)c->n_cu * 8));
+    for (hipEvent_t &e : ev) e = get_event(c);
+    HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+    HIP_TRY(c, gs_agreement_launch(a, blocks, c->stream));
+    HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+    return GS_OK;
+}
+
+int AgreementRun::download(const AgreementOut &out) {
+    for (int i = 0; slab && i < kAgreementOutputs; ++i) {
+        if (i == kAgrNPooled) {
+            if (!d_n_pooled)
+                *(int32_t *)out.out[i] = h_pooled;  // the mask's
+            else
+                HIP_TRY(c, hipMemcpyAsync(out.out[i], d_n_pooled, 4, hipMemcpyDeviceToHost,
+                                          c->stream));
+        } else if (lay.part[i].bytes() > 0)
+            HIP_TRY(c, hipMemcpyAsync(out.out[i], slab + lay.part[i].off,
+                                      (size_t)lay.part[i].bytes(), hipMemcpyDeviceToHost,
+                                      c->stream));
+    }
+    return GS_OK;
+}
+
+void AgreementRun::finish() {
+    float ms = 0.0f;
+    if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        c->agreement_ms = ms;
+}
+
+// No sequences: nothing to compare; every chain's (empty) row sums to anything asked, so
+// without a mask every chain is pooled (summary_of_nothing), and a pooled chain has no
+// distance and no sequence to agree on.
+void agreement_of_nothing(int64_t R, const int32_t *mask, const AgreementOut &out) {
+    int32_t pooled = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        const bool f = !mask || mask[r] != 0;
+        pooled += f;
+        ((int64_t *)out.out[kAgrChainDist])[r] = f ? 0 : -1;
+        ((int32_t *)out.out[kAgrChainAgree])[r] = f ? 0 : -1;
+    }
+    if (R > 0) *(int32_t *)out.out[kAgrNPooled] = pooled;
+}
+
+// gs_occupancy_agreement: the caller's bins up, the reduction, the result down (arguments
+// validated).  The context's snapshot and state are not touched.
+int occupancy_agreement(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
+                        const int32_t *mask, const AgreementOut &out) {
+    const int64_t n = c->n_local;
+    if (n == 0) {
+        agreement_of_nothing(R, mask, out);
+        return GS_OK;
+    }
+    const int64_t H = occupancy_offsets(c, W, nullptr);
+    std::vector<int64_t> h_off((size_t)n + 1);
+    occupancy_offsets(c, W, h_off.data());
+    AgreementRun run(c);
+    DevBuf<int32_t> d_occ;
+    DevBuf<int64_t> d_off;
+    GS_TRY(d_occ.alloc(c, std::max<int64_t>(1, (int64_t)R * H)));
+    GS_TRY(d_off.alloc(c, n + 1));
+    int rc = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_occ, occ, (size_t)R * H * 4, hipMemcpyHostToDevice, c->stream));
+        GS_TRY(run.enqueue(d_occ, d_off, H, R, n_counted, nullptr, nullptr, mask));
         GS_TRY(run.download(out));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return GS_OK;

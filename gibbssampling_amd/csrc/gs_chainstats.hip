@@ -6,7 +6,8 @@
 // counted sweep of any of the sweep kernels, which left d_pos, d_pwms and the error word.
 // And the reduction of the bins those launches filled to what a caller keeps of them (the
 // ..._summary calls and gs_occupancy_summary, §9.28): each sequence's first-maximum bin and the
-// count matrix over the counted states.
+// count matrix over the counted states.  And the chains' agreement with their pool
+// (gs_occupancy_agreement, gs_motif_run_batch_agreement, §9.31).
 #include "gs_ctx.h"
 #include "gs_wave.h"
 
@@ -766,5 +767,189 @@ hipError_t gs_list_summary_launch(const ListSummaryArgs &a, int blocks, hipStrea
     const size_t lds = (size_t)(a.A * a.W + a.A) * 8 + (size_t)4 * kListStageBins * 8;
     hipLaunchKernelGGL(gs_list_summary_kernel, dim3(blocks * (a.n_chains + (a.flags ? 1 : 0))),
                        dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+// ---- Chain agreement (gs_occupancy_agreement and gs_motif_run_batch_agreement, DESIGN.md
+// §9.31) ----
+// Whether pooling the chains was justified: with P pooled chains and pool[b] the sum of their
+// bins in int64, D(r, n) = the sum over the bins b of sequence n's row of |P occ[r][b] -
+// pool[b]| (for chains that finished, 2 P n_counted times the total variation distance between
+// chain r's marginal of the sequence and the pooled one); m(r, n) and m*(n) are the first
+// maxima of the chain's and of the pooled row, as gs_summary_kernel takes them.  One launch
+// behind the launch that decides the pool, unless the flags are already there (a summary's of
+// the same call, or the caller's mask).
+namespace {
+
+constexpr int kAgrStageBins = kListStageBins;  // bins of a pooled row a wavefront keeps in LDS
+constexpr int kAgrLdsChains = 512;             // chains whose sums a workgroup collects in LDS
+
+// kSumDepth wavefront loads of the pooled row from bin `base` on: the pooled chains' bins
+// summed in int64.  Every load is issued, at an index clamped into the row, and the value past
+// the end dropped where it is added (list_load's reason).
+__device__ __forceinline__ void agr_pool_load(const AgreementArgs &a, int64_t o, int len, int base,
+                                              int lane, long long (&x)[kSumDepth]) {
+#pragma unroll
+    for (int k = 0; k < kSumDepth; ++k) x[k] = 0;
+    for (int r = 0; r < a.n_chains; ++r) {
+        if (!a.flags[r]) continue;  // wavefront-uniform
+        const int32_t *row = a.occ + (int64_t)r * a.H + o;
+        int32_t y[kSumDepth];
+#pragma unroll
+        for (int k = 0; k < kSumDepth; ++k) y[k] = row[min(base + lane + 64 * k, len - 1)];
+#pragma unroll
+        for (int k = 0; k < kSumDepth; ++k) x[k] += base + lane + 64 * k < len ? y[k] : 0;
+    }
+}
+
+}  // namespace
+
+// One wavefront a sequence row, four a workgroup; lane l owns the bins l, l + 64, .. in
+// increasing order, kSumDepth coalesced wavefront loads issued ahead of their use, every bin
+// index clamped into the row before its load.  Phase A: the pooled row, its first maximum m*,
+// and, when the row has at most kAgrStageBins bins, the row into the wavefront's LDS stage, bin
+// b by the lane b mod 64 that reads it again, so that no lane reads what another wrote (a
+// longer row is summed again a chunk in phase B).  Phase B, per pooled chain in increasing r:
+// the chain's first maximum and D; the running largest D by a strict comparison, so the lowest
+// r keeps it.  A chain's D and agreement go to the workgroup's LDS accumulators, and every
+// non-zero one to the chain's sums by one atomic add at the workgroup's end (more than
+// kAgrLdsChains chains: straight to global memory).  Integer adds: the result does not depend
+// on their order.  A chain that is not pooled gets (-1, -1) from workgroup 0; nothing is added
+// to it.  No workgroup waits on another.  Negative bins are the caller's error: nothing is
+// indexed by a bin's value, so no access depends on them.
+extern "C" __global__ void __launch_bounds__(256)
+gs_agreement_kernel(AgreementArgs a) {
+    extern __shared__ unsigned long long agr_lds[];  // four stages, the chains' D, their agreement
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int R = a.n_chains;
+    long long *stage = (long long *)agr_lds + w * kAgrStageBins;
+    unsigned long long *acc_d = agr_lds + 4 * kAgrStageBins;
+    unsigned int *acc_a = (unsigned int *)(acc_d + kAgrLdsChains);
+    const bool in_lds = R <= kAgrLdsChains;  // grid-uniform
+    if (in_lds) {
+        for (int r = tid; r < R; r += 256) {
+            acc_d[r] = 0;
+            acc_a[r] = 0;
+        }
+        __syncthreads();
+    }
+    if (blockIdx.x == 0)
+        for (int r = tid; r < R; r += 256)
+            if (!a.flags[r]) {
+                a.chain_dist[r] = -1;
+                a.chain_agree[r] = -1;
+            }
+    int P = 0;
+    for (int r = lane; r < R; r += 64) P += a.flags[r] != 0 ? 1 : 0;
+    P = (int)wave_sum_i64(P);
+    for (int n = blockIdx.x * 4 + w; n < a.n_local; n += gridDim.x * 4) {
+        const int64_t o = a.off[n];
+        const int len = (int)(a.off[n + 1] - o);  // 1 + (L - W + 1) bins
+        if (len <= 0) continue;
+        const bool fits = len <= kAgrStageBins;
+        // ---- phase A: the pooled row and its first maximum ----
+        long long best = LLONG_MIN;
+        int bidx = INT_MAX;
+        for (int base = 0; base < len; base += 64 * kSumDepth) {
+            long long x[kSumDepth];
+            agr_pool_load(a, o, len, base, lane, x);
+#pragma unroll
+            for (int k = 0; k < kSumDepth; ++k) {
+                const int b = base + lane + 64 * k;
+                if (b >= len) continue;
+                if (fits) stage[b] = x[k];
+                if (x[k] > best) {
+                    best = x[k];
+                    bidx = b;
+                }
+            }
+        }
+        wave_first_max(best, bidx);  // m* = bidx, in every lane
+        // ---- phase B: every pooled chain against the pool ----
+        long long maxd = -1;
+        int argr = -1, agree = 0;
+        for (int r = 0; r < R; ++r) {
+            if (!a.flags[r]) continue;  // wavefront-uniform
+            const int32_t *row = a.occ + (int64_t)r * a.H + o;
+            int cbest = INT_MIN, cidx = INT_MAX;
+            long long d = 0;
+            for (int base = 0; base < len; base += 64 * kSumDepth) {
+                int32_t y[kSumDepth];
+                long long pv[kSumDepth];
+#pragma unroll
+                for (int k = 0; k < kSumDepth; ++k) y[k] = row[min(base + lane + 64 * k, len - 1)];
+                if (fits) {
+#pragma unroll
+                    for (int k = 0; k < kSumDepth; ++k) {
+                        const int b = base + lane + 64 * k;
+                        pv[k] = b < len ? stage[b] : 0;
+                    }
+                } else {
+                    agr_pool_load(a, o, len, base, lane, pv);
+                }
+#pragma unroll
+                for (int k = 0; k < kSumDepth; ++k) {
+                    const int b = base + lane + 64 * k;
+                    if (b >= len) continue;
+                    if (y[k] > cbest) {
+                        cbest = y[k];
+                        cidx = b;
+                    }
+                    const long long t = (long long)P * y[k] - pv[k];
+                    d += t < 0 ? -t : t;
+                }
+            }
+            wave_first_max(cbest, cidx);
+            d = wave_sum_i64(d);
+            const bool same = cidx == bidx;
+            agree += same ? 1 : 0;
+            if (d > maxd) {
+                maxd = d;
+                argr = r;
+            }
+            if (lane == 0) {
+                if (in_lds) {
+                    if (d != 0) atomicAdd(&acc_d[r], (unsigned long long)d);
+                    if (same) atomicAdd(&acc_a[r], 1u);
+                } else {
+                    if (d != 0)
+                        atomicAdd((unsigned long long *)&a.chain_dist[r], (unsigned long long)d);
+                    if (same) atomicAdd(&a.chain_agree[r], 1);
+                }
+            }
+        }
+        if (lane == 0) {
+            a.agree[n] = agree;
+            a.spread[n] = argr >= 0 ? maxd : 0;
+            a.spread_chain[n] = argr;
+        }
+    }
+    if (!in_lds) return;
+    __syncthreads();
+    for (int r = tid; r < R; r += 256) {
+        if (acc_d[r] != 0) atomicAdd((unsigned long long *)&a.chain_dist[r], acc_d[r]);
+        if (acc_a[r] != 0) atomicAdd(&a.chain_agree[r], (int)acc_a[r]);
+    }
+}
+
+// With a.decide first the launch that decides the pool by the summaries' rule
+// (gs_summary_pool_kernel: flags and n_pooled, which is zero at launch); then `blocks`
+// workgroups over the sequence rows.  chain_agree and chain_dist are zero at launch.
+hipError_t gs_agreement_launch(const AgreementArgs &a, int blocks, hipStream_t s) {
+    if (a.n_local <= 0 || a.n_chains <= 0) return hipSuccess;
+    if (a.decide) {
+        SummaryArgs p{};
+        p.n_chains = a.n_chains;
+        p.n_local = a.n_local;
+        p.H = a.H;
+        p.n_counted = a.n_counted;
+        p.occ = a.occ;
+        p.off = a.off;
+        p.flags = a.flags;
+        p.n_pooled = a.n_pooled;
+        hipLaunchKernelGGL(gs_summary_pool_kernel, dim3(a.n_chains), dim3(256), 0, s, p);
+    }
+    const size_t lds = (size_t)4 * kAgrStageBins * 8 + (size_t)kAgrLdsChains * 12;
+    hipLaunchKernelGGL(gs_agreement_kernel, dim3(blocks), dim3(256), lds, s, a);
     return hipGetLastError();
 }

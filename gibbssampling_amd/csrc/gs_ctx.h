@@ -279,6 +279,26 @@ struct SummaryArgs {
     int64_t *pool_counts;        // [A * W + A], zero at launch
 };
 hipError_t gs_summary_launch(const SummaryArgs &a, int blocks, hipStream_t s);
+// The chains' agreement with their pool for gs_agreement_kernel (gs_chainstats.hip, DESIGN.md
+// §9.31): per sequence how many pooled chains share the pooled mode and the largest distance
+// D(r, n) = sum over the row's bins of |P occ[r][b] - pool[b]| with the chain that has it; per
+// chain the sum of its D and the number of its modes that are the pool's.
+struct AgreementArgs {
+    int32_t n_chains, n_local;
+    int64_t H;                   // off[n_local]
+    int64_t n_counted;           // (the rule's launch only)
+    const int32_t *occ;          // [n_chains][H]
+    const int64_t *off;          // [n_local + 1]: gs_occupancy_offsets
+    int32_t *flags;              // [n_chains]: non-zero = pooled (written only with decide)
+    int32_t *n_pooled;           // [1], zero at launch: written only with decide
+    int32_t decide;              // the flags are decided here, by the summaries' rule
+    int32_t *agree;              // [n_local]
+    int64_t *spread;             // [n_local]
+    int32_t *spread_chain;       // [n_local]
+    int32_t *chain_agree;        // [n_chains], zero at launch
+    int64_t *chain_dist;         // [n_chains], zero at launch
+};
+hipError_t gs_agreement_launch(const AgreementArgs &a, int blocks, hipStream_t s);
 // The reduction of n_chains list histograms for gs_list_summary_kernel (gs_chainstats.hip,
 // DESIGN.md §9.29): each sequence's modal site count, that many most occupied starts pairwise
 // more than W apart, and the count matrix summed over the counted states; per chain and
@@ -483,6 +503,7 @@ struct gs_ctx {
     double run_batch_ms[2] = {0.0, 0.0};  // the last chain batch (gs_motif_run_batch): starts, sweeps
     double run_stats_ms[2] = {0.0, 0.0};  // the last gs_run_sweeps_stats: sweeps, statistics launches
     double summary_ms = 0.0;  // the last chain summary's reduction (gs_summary_last_ms)
+    double agreement_ms = 0.0;  // the last chain agreement's reduction (gs_agreement_last_ms)
     double starts_batch_ms[2] = {0.0, 0.0};  // the last gs_random_starts_batch: counts / aggregates, scans
     double run_multi_batch_ms[2] = {0.0, 0.0};  // the last list chain batch (gs_motif_run_multi_batch): starts, sweeps
     int32_t run_multi_batch_info[4] = {0, 0, 0, 0};  // ... pairs rescored by overflow launches, chains parked, resume rounds, first arena

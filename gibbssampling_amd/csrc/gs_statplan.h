@@ -1,7 +1,7 @@
-// gs_statplan.h — the host-side decisions of the chain statistics and summaries (DESIGN.md
-// §9.30), free of HIP so that a plain host compiler builds and tests them
-// (tests/host/stats_plan_main.cpp): which sweeps count, where the parts of a call's device
-// slab lie, and how many bytes a call is charged before it is refused.
+// gs_statplan.h — the host-side decisions of the chain statistics, summaries and agreement
+// (DESIGN.md §9.30, §9.31), free of HIP so that a plain host compiler builds and tests them
+// (tests/host/stats_plan_main.cpp, agreement_plan_main.cpp): which sweeps count, where the
+// parts of a call's device slab lie, and how many bytes a call is charged before it is refused.
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -103,6 +103,32 @@ inline Slab<kSummaryParts> summary_slab(int64_t R, int64_t n, int64_t cells, int
     return s;
 }
 
+// ---- the chain agreement's result slab (gs_agreement_kernel) ----
+// The outputs in the order of the C entry points' arguments, then the pooled flags, which stay
+// on the device.  The per-chain parts collect atomic adds and are zero at launch, and so is the
+// pool's count where this slab decides the pool by the rule; the per-sequence parts are written
+// in full.  own_flags: the flags are this slab's (the rule, or the caller's mask), not a
+// summary's of the same call; own_count: the rule decides them here, and counts them.
+enum AgreementPart {
+    kAgrAgree, kAgrSpread, kAgrSpreadChain, kAgrChainAgree, kAgrChainDist, kAgrNPooled,
+    kAgreementOutputs,
+    kAgrFlags = kAgreementOutputs,
+    kAgreementParts
+};
+
+inline Slab<kAgreementParts> agreement_slab(int64_t R, int64_t n, bool own_flags, bool own_count) {
+    Slab<kAgreementParts> s;
+    s.part[kAgrAgree] = Part{4, n, true, false, 0};
+    s.part[kAgrSpread] = Part{8, n, true, false, 0};
+    s.part[kAgrSpreadChain] = Part{4, n, true, false, 0};
+    s.part[kAgrChainAgree] = Part{4, R, true, true, 0};
+    s.part[kAgrChainDist] = Part{8, R, true, true, 0};
+    s.part[kAgrNPooled] = Part{4, 1, own_flags && own_count, true, 0};
+    s.part[kAgrFlags] = Part{4, R, own_flags, false, 0};
+    s.carve();
+    return s;
+}
+
 // ---- the statistics' slab of the three chain drivers ----
 // (run_sweeps: R = 1; the single-position drivers: cap = 1, no kStatSites, no kStatBestCnt)
 enum StatsPart {
@@ -142,6 +168,8 @@ inline int64_t summary_bytes(int64_t R, int64_t n, int64_t cells, int64_t M, boo
            (want[kGroupCells] ? R * cells * 8 : 0) +
            (want[kGroupPool] ? (list ? n * (16 + 12 * M) : n * 12) + cells * 8 + R * 4 + 8 : 0);
 }
+// the agreement's five arrays, the pooled flags and the pool's count
+inline int64_t agreement_bytes(int64_t R, int64_t n) { return n * 16 + R * 12 + R * 4 + 8; }
 // the bins and their offsets, the site counts, the trace, the running best and its rows
 inline int64_t stats_bytes(int64_t R, int64_t n, int64_t H, int64_t n_counted, int64_t cap,
                            int64_t M, bool list, const StatsWant &w) {

@@ -55,6 +55,20 @@ struct SummaryOut {
     }
 };
 
+// Where a chain agreement goes: the host arrays by AgreementPart, one group,
+// nullable as a whole.
+struct AgreementOut {
+    void *out[kAgreementOutputs];
+    int given() const {
+        int g = 0;
+        for (void *p : out) g += p != nullptr;
+        return g;
+    }
+    bool any() const { return given() == kAgreementOutputs; }
+    // half of the group given
+    bool ragged() const { return given() != 0 && given() != kAgreementOutputs; }
+};
+
 // The caller's side of the ..._stats and ..._summary entries: which sweeps count and where the
 // chains' statistics go (each nullable; the best rows go with best_sweep_out).  sites_out and
 // best_cnt_out: Positions-list chains only.
@@ -68,21 +82,28 @@ struct RunStats {
     // the reduction of the bins (and site counts), null: none
     const SummaryOut *sum = nullptr;
     int32_t *sites_out = nullptr, *best_cnt_out = nullptr;
+    // the chains' agreement with their pool (run_batch only), null: none
+    const AgreementOut *agr = nullptr;
     bool summed() const { return sum && sum->any(); }
-    bool any() const { return occ_out || sites_out || ic_out || best_sweep_out || summed(); }
-    // what lives on the device: the bins and site counts for the caller or for the summary
+    bool agreed() const { return agr && agr->any(); }
+    bool any() const {
+        return occ_out || sites_out || ic_out || best_sweep_out || summed() || agreed();
+    }
+    // what lives on the device: the bins and site counts for the caller, for the summary or
+    // (the bins) for the agreement
     StatsWant want() const {
-        return StatsWant{occ_out || summed(), sites_out || summed(), ic_out != nullptr,
+        return StatsWant{occ_out || summed() || agreed(), sites_out || summed(), ic_out != nullptr,
                          best_sweep_out != nullptr};
     }
     CountPlan plan(int32_t T) const { return CountPlan{burn_in, thin, T}; }
     // what every entry refuses: burn_in / thin out of range, the best rows (with best_cnt_out
-    // on lists) not all-or-none with best_sweep_out, half of a summary's output group
+    // on lists) not all-or-none with best_sweep_out, half of a summary's output group or of the
+    // agreement's
     bool bad(int32_t n_sweeps, bool list) const {
         const bool rows = best_pos_out && best_pwms_out && (!list || best_cnt_out);
         const bool any_row = best_pos_out || best_pwms_out || (list && best_cnt_out);
         return burn_in < 0 || burn_in > n_sweeps || thin < 1 || (best_sweep_out != nullptr) != rows ||
-               (!best_sweep_out && any_row) || (sum && sum->ragged());
+               (!best_sweep_out && any_row) || (sum && sum->ragged()) || (agr && agr->ragged());
     }
 };
 
@@ -135,6 +156,34 @@ struct SummaryRun {
         return lay.part[part].wanted ? (T *)(slab + lay.part[part].off) : nullptr;
     }
 };
+// The agreement of R histograms resident at d_occ with their pool, behind
+// whatever is on the stream, as SummaryRun: enqueue() carves and allocates the result slab
+// (agreement_slab), zeroes its prefix and launches between two events; download() enqueues the
+// copies; finish(), after the caller's synchronisation, reads the device time into the context.
+// The pooled flags are, in this order: the summary's of the same call (d_flags with its count
+// d_n_pooled: the pool is decided once); the caller's mask (mask, [R], non-zero = pooled); the
+// summaries' rule, decided here.
+struct AgreementRun {
+    gs_ctx *c;
+    char *slab = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    Slab<kAgreementParts> lay{};
+    std::vector<int32_t> h_flags;        // the mask as flags, alive until its upload is over
+    int32_t h_pooled = 0;                // ... and their number
+    const int32_t *d_n_pooled = nullptr; // where the pool's count is on the device (no mask)
+    explicit AgreementRun(gs_ctx *ctx) : c(ctx) {}
+    AgreementRun(const AgreementRun &) = delete;
+    AgreementRun &operator=(const AgreementRun &) = delete;
+    ~AgreementRun();
+    int enqueue(const int32_t *d_occ, const int64_t *d_off, int64_t H, int32_t R, int64_t n_counted,
+                int32_t *d_flags, const int32_t *d_n_pooled, const int32_t *mask);
+    int download(const AgreementOut &out);
+    void finish();
+    template <class T>
+    T *dev(int part) const {
+        return lay.part[part].wanted ? (T *)(slab + lay.part[part].off) : nullptr;
+    }
+};
 // What chains over no sequences leave: no bins, an all-NaN trace, no best, summary_of_nothing.
 int stats_of_nothing(const gs_ctx *c, int32_t W, int64_t R, int64_t n_counted, const RunStats &st);
 // The summary of chains over no sequences: no modes, zero cells, every chain pooled.
@@ -142,6 +191,12 @@ void summary_of_nothing(const gs_ctx *c, int32_t W, int64_t R, const SummaryOut 
 // gs_occupancy_summary (sites null) and gs_list_occupancy_summary
 int occupancy_summary(gs_ctx *c, int32_t W, int32_t M, const int32_t *occ, const int32_t *sites,
                       int32_t R, int64_t n_counted, const SummaryOut &out);
+// The agreement of chains over no sequences: every chain pooled (or the mask's), (0, 0) a
+// pooled chain.
+void agreement_of_nothing(int64_t R, const int32_t *mask, const AgreementOut &out);
+// gs_occupancy_agreement
+int occupancy_agreement(gs_ctx *c, int32_t W, const int32_t *occ, int32_t R, int64_t n_counted,
+                        const int32_t *mask, const AgreementOut &out);
 int64_t occupancy_offsets(const gs_ctx *c, int32_t W, int64_t *off);
 // gs_batch.cpp: the drivers of the chain batches and of the batched starts (arguments
 // validated; stats null, or with no output: the entry without statistics)

@@ -120,6 +120,60 @@ def informationContent(pwms) -> float:
 
 
 @dataclass
+class ChainAgreement:
+    """Whether pooling R chains was justified: the chains against the pool of
+    the n_pooled chains that finished.  With pool the sum of the pooled chains' bins, D(r, n)
+    is the sum over sequence n's bins of |n_pooled occupancy[r] - pool|, an integer; D / (2
+    n_pooled n_counted) is the total variation distance between chain r's marginal of the
+    sequence and the pooled marginal.  agree[N]: the pooled chains whose most frequent bin of
+    the sequence (the first among equals) is the pool's.  spread[N] (int64) / spread_chain[N]:
+    the largest D(r, n) over the pooled chains and the lowest chain that has it; (0, 0, -1)
+    without a pooled chain.  chain_dist[R] (int64): the sum of D(r, n) over the sequences;
+    chain_agree[R]: the sequences whose chain mode is the pool's; (-1, -1) for a chain that is
+    not pooled.  n_counted: the counted sweeps of a chain."""
+    agree: np.ndarray
+    spread: np.ndarray
+    spread_chain: np.ndarray
+    chain_agree: np.ndarray
+    chain_dist: np.ndarray
+    n_pooled: int
+    n_counted: int
+
+    def distance(self) -> np.ndarray:
+        """[N] float64: per sequence the largest total variation distance between a pooled
+        chain's marginal and the pooled one, spread / (2 n_pooled n_counted); 0 without a
+        pooled counted state."""
+        den = 2.0 * float(int(self.n_pooled) * int(self.n_counted))
+        x = np.asarray(self.spread, np.float64)
+        return x / den if den > 0 else np.zeros_like(x)
+
+    def outliers(self, threshold: float) -> np.ndarray:
+        """The pooled chains whose total variation distance to the pool, averaged over the
+        sequences, chain_dist / (2 n_pooled n_counted N), exceeds threshold."""
+        den = 2.0 * float(int(self.n_pooled) * int(self.n_counted) * len(self.agree))
+        d = np.asarray(self.chain_dist)
+        if den <= 0:
+            return np.zeros(0, np.int64)
+        return np.nonzero((d >= 0) & (d.astype(np.float64) / den > threshold))[0]
+
+
+def _rhat(ic, keep) -> float:
+    """The Gelman-Rubin potential scale reduction of the traces ic[keep] (m chains of n
+    entries), in binary64: B / n the variance of the chain means, Wv the mean of the chains'
+    variances (both ddof 1); sqrt(((n - 1) / n Wv + B / n) / Wv).  NaN with fewer than two
+    chains or entries, Wv == 0, or a NaN in a trace."""
+    x = np.asarray(ic, np.float64)[np.asarray(keep, bool)]
+    m, n = x.shape if x.ndim == 2 else (0, 0)
+    if m < 2 or n < 2 or np.isnan(x).any():
+        return float("nan")
+    b_over_n = float(np.var(x.mean(axis=1), ddof=1))
+    wv = float(np.mean(np.var(x, axis=1, ddof=1)))
+    if wv == 0:
+        return float("nan")
+    return float(np.sqrt(((n - 1) / n * wv + b_over_n) / wv))
+
+
+@dataclass
 class ChainStats:
     """What MotifSampler.runSweepsBatchedStats gathered over the counted sweeps of R chains
     (MotifSampler.runSweepsStats: of the single chain, R = 1).
@@ -172,6 +226,49 @@ class ChainStats:
             out.append(createMotifIndex(m[k], [] if k == 0 else [k - 1]))
         return out
 
+    def agreement(self, pooled=None) -> ChainAgreement:
+        """The chains against their pool, from the bins, in integers: what
+        Context.occupancy_agreement and MotifSampler.runSweepsBatchedAgreement compute on the
+        device without the bins coming down.  pooled[R] (non-zero = pooled) replaces
+        finished() as the choice of the pool."""
+        occ = np.asarray(self.occupancy, np.int64)
+        off = np.asarray(self.offsets, np.int64)
+        R, N = len(occ), max(len(off) - 1, 0)
+        keep = self.finished() if pooled is None else np.asarray(pooled) != 0
+        idx = np.nonzero(keep)[0]
+        P = len(idx)
+        agree = np.zeros(N, np.int32)
+        spread = np.zeros(N, np.int64)
+        spread_chain = np.full(N, -1, np.int32)
+        chain_agree = np.where(keep, 0, -1).astype(np.int32)
+        chain_dist = np.where(keep, 0, -1).astype(np.int64)
+        if P > 0 and N > 0:
+            start, lens = off[:-1], np.diff(off)
+            rows = occ[idx]                               # [P, H]
+            pool = rows.sum(axis=0)
+            d = np.add.reduceat(np.abs(P * rows - pool), start, axis=1)  # D[P, N]
+            where = np.arange(off[-1], dtype=np.int64)
+
+            def first_max(x):  # the first-maximum bin of every row of x[..., H], per sequence
+                top = np.repeat(np.maximum.reduceat(x, start, axis=-1), lens, axis=-1)
+                return np.minimum.reduceat(np.where(x == top, where, off[-1]), start, axis=-1)
+
+            same = first_max(rows) == first_max(pool)     # [P, N]
+            agree[:] = same.sum(axis=0)
+            spread[:] = d.max(axis=0)
+            spread_chain[:] = idx[d.argmax(axis=0)]       # the first maximum: the lowest chain
+            chain_dist[idx] = d.sum(axis=1)
+            chain_agree[idx] = same.sum(axis=1)
+        return ChainAgreement(agree, spread, spread_chain, chain_agree, chain_dist, P,
+                              int(self.ic.shape[1]))
+
+    def rhat(self) -> float:
+        """The Gelman-Rubin potential scale reduction of the ic trace over the finished
+        chains, in binary64 on the host: m chains of n entries, B / n the variance of the chain
+        means and Wv the mean of the chains' variances (ddof 1), sqrt(((n - 1) / n Wv + B / n)
+        / Wv).  NaN when m < 2, n < 2, Wv == 0 or a finished chain's trace holds a NaN."""
+        return _rhat(self.ic, self.finished())
+
 
 @dataclass
 class ChainSummary:
@@ -199,6 +296,16 @@ class ChainSummary:
     alphabetSize: int
     occupancy: np.ndarray | None = None
     offsets: np.ndarray | None = None
+    #: the chains against their pool, only from MotifSampler.runSweepsBatchedAgreement
+    agreement: ChainAgreement | None = None
+
+    def rhat(self) -> float:
+        """ChainStats.rhat() of the ic trace: over the chains the agreement pooled, or, without
+        an agreement, over every chain (a chain that raised leaves NaN in its trace, and the
+        result is then NaN)."""
+        keep = (np.asarray(self.agreement.chain_dist) >= 0 if self.agreement is not None
+                else np.ones(len(self.ic), bool))
+        return _rhat(self.ic, keep)
 
     def mode(self) -> list[MotifIndex]:
         """ChainStats.mode() of the same chains: each sequence's most frequent pooled bin, the
@@ -464,6 +571,39 @@ class MotifSampler:
                                int(motifLength), len(alphabet_codes(alphabet)),
                                st["occupancy"] if occupancy else None,
                                st.get("offsets") if occupancy else None)
+        return [_motif_indices(pos[r], pwms[r]) for r in range(R)], summary
+
+    @staticmethod
+    def runSweepsBatchedAgreement(motifLength: int, pseudoCount: float, cutOff: float, alphabet,
+                                  sources, sweeps: int, seeds, motifMems=None,
+                                  init_mode: int = 0, first_sweep: int = 0, burn_in: int = 0,
+                                  thin: int = 1, device: int = 0, motifAmount: int = 1):
+        """runSweepsBatchedSummary with the chains' agreement with their pool reduced on the
+        device in the same single call (Context.motif_run_batch_agreement, which is asked for
+        no bins) -> (chains, ChainSummary with its agreement field set): how many chains share
+        the pooled mode of each sequence, how far the farthest chain's marginal is from the
+        pooled one, and every chain's distance summed over the sequences.
+        motifAmount 1 with single positions only."""
+        seeds = [int(s) & (2**64 - 1) for s in seeds]
+        if motifAmount != 1:
+            raise _native.ArgumentError(_native.GS_E_ARG,
+                                        "the chain statistics need motifAmount = 1")
+        pos = _chain_starts(motifMems, seeds, sources, single=True)
+        ctx = _bind(alphabet, sources, device)
+        pos, pwms, status, st = ctx.motif_run_batch_agreement(
+            motifLength, pseudoCount, cutOff, sweeps, seeds, pos, init_mode, first_sweep,
+            burn_in=burn_in, thin=thin, occupancy=False)
+        _raise_failed_chain(status)
+        R = len(seeds)
+        n_counted = st["ic"].shape[1]
+        agreement = ChainAgreement(st["agree"], st["spread"], st["spread_chain"],
+                                   st["chain_agree"], st["chain_dist"],
+                                   int(st["agree_n_pooled"][0]), n_counted)
+        summary = ChainSummary(st["mode_pos"], st["mode_count"], st["counts"], st["pooled_pos"],
+                               st["pooled_count"], st["pooled_counts"], int(st["n_pooled"][0]),
+                               n_counted, st["ic"], st["best_sweep"], _best_states(st),
+                               int(motifLength), len(alphabet_codes(alphabet)),
+                               agreement=agreement)
         return [_motif_indices(pos[r], pwms[r]) for r in range(R)], summary
 
     @staticmethod

@@ -417,6 +417,68 @@ int gs_motif_run_batch_summary(gs_ctx *ctx, int32_t W, double pseudo_count, doub
  * events around its launches; 0 when nothing was reduced. */
 int gs_summary_last_ms(const gs_ctx *ctx, double out[1]);
 
+/* Chain agreement: whether pooling the chains was justified, computed on the device from the
+ * same bins (motifAmount 1, occ[n_chains][H] in the bins of gs_occupancy_offsets(ctx, W, off)).
+ * With a pooled flag f[r] a chain, P the number of pooled chains and pool[b] the sum of
+ * occ[r][b] over the pooled chains in int64, for a pooled chain r and a sequence n:
+ * D(r, n) = the sum over the bins b of row n of |P occ[r][b] - pool[b]| in int64; every row of
+ * a finished chain sums to n_counted, so D / (2 P n_counted) is the total variation distance
+ * between chain r's marginal of sequence n and the pooled marginal.  m(r, n) is the chain's
+ * first-maximum bin of row n and m*(n) that of pool, exactly as the summaries take them.
+ * Per sequence: agree_out[n] the number of pooled r with m(r, n) == m*(n); spread_out[n] the
+ * largest D(r, n) over the pooled r; spread_chain_out[n] the lowest r that has it; with P == 0
+ * the row is (0, 0, -1).  Per chain: chain_dist_out[r] the sum over n of D(r, n),
+ * chain_agree_out[r] the number of n with m(r, n) == m*(n); a chain that is not pooled gets
+ * (-1, -1).  n_pooled_out[0] = P.  The six outputs form one group, nullable as a whole; half
+ * of it given is GS_E_ARG.  Integer sums only: the results are the same on every run.
+ * Chain r is pooled when the bins of local sequence 0 sum to n_counted (the summaries' rule),
+ * or, in gs_occupancy_agreement with pooled non-null, when pooled[r] is non-zero: the mask
+ * serves chains of Positions lists, whose rows do not sum to n_counted (pass which chains
+ * finished), and a split-half check of one chain (two continued gs_run_sweeps_stats calls
+ * uploaded as two chains).
+ * Exact while n_chains times the largest bin stays below 2^62, which bins the library wrote
+ * always do.  Negative bins are the caller's error: the result is unspecified, without a fault;
+ * nothing is indexed by a bin's value.  Without sequences n_pooled = n_chains (or the mask's
+ * count) and every pooled chain reads (0, 0).
+ * gs_occupancy_agreement reduces caller-held bins: it uploads, reduces and downloads, exactly
+ * as gs_occupancy_summary does.  It needs sequences (else GS_E_STATE) but no snapshot, and
+ * leaves the snapshot untouched.  GS_E_ARG: a bad W, occ null with n_chains > 0, n_chains < 0,
+ * n_counted < 0, half of the group given.  n_chains == 0 does nothing.  GS_E_UNSUPPORTED:
+ * sharded sequences or a communicator, or bins and results beyond 4 GiB.
+ * There is no agreement variant of the single-chain or of the list run calls: one chain has
+ * nothing to compare with, and list chains go through gs_occupancy_agreement with the mask. */
+int gs_occupancy_agreement(gs_ctx *ctx, int32_t W,
+        const int32_t *occ,            /* [n_chains][H]                        */
+        int32_t n_chains, int64_t n_counted,
+        const int32_t *pooled,         /* [n_chains], nullable: the rule       */
+        int32_t *agree_out,            /* [n_local], nullable with the next 5  */
+        int64_t *spread_out,           /* [n_local]                            */
+        int32_t *spread_chain_out,     /* [n_local]                            */
+        int32_t *chain_agree_out,      /* [n_chains]                           */
+        int64_t *chain_dist_out,       /* [n_chains]                           */
+        int32_t *n_pooled_out          /* [1]                                  */);
+/* gs_motif_run_batch_summary with the agreement group appended (its pool count as
+ * agree_n_pooled_out); the reduction is enqueued behind the summary's launches, before the
+ * call's single synchronisation, and the bins come down only when occ_out is non-null.
+ * n_counted and the pooled rule are the call's own, so a chain that raised is left out and
+ * reads (-1, -1); with the summary's pooled outputs asked for the pool is decided once, for
+ * both.  With the six agreement outputs null the call is gs_motif_run_batch_summary, bit for
+ * bit.  The extra slabs count toward the 4 GiB of chain slabs. */
+int gs_motif_run_batch_agreement(gs_ctx *ctx, int32_t W, double pseudo_count, double cut_off,
+        int32_t n_sweeps, const uint64_t *seeds, int32_t n_chains, int64_t first_sweep,
+        int32_t init_mode, const double *u, int32_t burn_in, int32_t thin,
+        int32_t *pos_inout, double *pwms_out, int32_t *status_out,
+        int32_t *occ_out, double *ic_out, int64_t *best_sweep_out, int32_t *best_pos_out,
+        double *best_pwms_out,
+        int32_t *mode_pos_out, int32_t *mode_count_out, int64_t *counts_out,
+        int32_t *pool_mode_pos_out, int64_t *pool_mode_count_out, int64_t *pool_counts_out,
+        int32_t *n_pooled_out,
+        int32_t *agree_out, int64_t *spread_out, int32_t *spread_chain_out,
+        int32_t *chain_agree_out, int64_t *chain_dist_out, int32_t *agree_n_pooled_out);
+/* Device time of the last agreement's reduction (either call above), ms, between two events
+ * around its launches; 0 when nothing was reduced. */
+int gs_agreement_last_ms(const gs_ctx *ctx, double out[1]);
+
 /* R independent chains of n_sweeps synchronous sweeps each with Positions lists (any
  * motifAmount) in one call: chain r is exactly n_sweeps calls of gs_motif_sweep_multi(ctx,
  * motif_amount, W, pc, cut_off, cap, ...), each fed the previous output.  init_mode -1:
